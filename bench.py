@@ -11,19 +11,30 @@ L-inf-normalised step), attacked-view forward + full backward, InfoNCE against t
 key all-gather + enqueue, gradient all-reduce (N>1) and the fused AdamW step.  bs=64/GPU, 384x384 + 40
 tokens, bf16 operands / fp32 accumulate, inputs resident in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit/..., plus
+Prints ONE JSON line on rank 0: metric/value/unit/higher_is_better/dtype/ms_per_step (ms of one timed step), step_mfma_frac, ...
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last step (--dump-outputs DIR) and prints that line.
+--full adds the measurements that take runs of their own:
   roofline     - the dominant kernel class (the encoder MLP forward GEMMs, fc1 +bias+GELU+stash and fc2
                  +bias+residual, exactly as the step launches them at M = bs*185): right after the timed
                  steps the two launches are replayed back to back on the launch stream between HIP events
                  (per-launch event brackets inside the step add ~20 us of marker/dispatch latency each, so
                  they over-state the duration rocprofv3 reports); algorithmic FLOPs / average duration vs
-                 the dense bf16 MFMA peak of /opt/skills/guides/MI355X_MICROARCH.md (2.5 PFLOP/s);
-  step_mfma_frac - whole-step EXECUTED FLOPs / step time / peak: (4+2K) forward-equivalents per pair with dropout off (the
-                 clean query forward IS PGD step 0's forward and runs once; SURVEY 8d counts (5+2K)F), each F less the part of
-                 the last block the cls-only tail does not execute (5.9 % of F; F_TAIL_SKIPPED) - work that is skipped is not
-                 credited; `value` (pairs/s) is what the skipping buys;
+                 the dense bf16 MFMA peak of MI355X_MICROARCH.md (2.5 PFLOP/s);
   cpu_baseline - the CPU oracle (port of the reference algorithm, oracle/rmcl_oracle.py) timed on this
-                 host's cores on a bounded sample of the same workload (rank 0, N=1 only).
+                 host's cores on a bounded sample of the same workload (rank 0, N=1 only; --no-cpu-baseline skips it);
+  training_realistic - the same step in the reference's real recipe (realistic_leg; N=1, rmcl_pgd, drop_rate 0; --no-realistic);
+  feed         - host feed rate of the input pipeline (tools/feed_bench.py, before the GPU is touched) and the device side of
+                 the byte path (N=1, rmcl_pgd; --no-feed-bench).
+step_mfma_frac (every run) = whole-step EXECUTED FLOPs / step time / peak: (4+2K) forward-equivalents per pair with dropout off
+(the clean query forward IS PGD step 0's forward and runs once; SURVEY 8d counts (5+2K)F), each F less the part of the last
+block the cls-only tail does not execute (5.9 % of F; F_TAIL_SKIPPED) - work that is skipped is not credited; `value`
+(pairs/s) is what the skipping buys.
+
+--dump-outputs DIR writes, after the timed steps, what the last step left to its caller as float32 / float64 .npy files (56 MiB):
+loss.npy, params.npy / momentum_params.npy (fixed seeded samples of the query and momentum parameter arenas after the step)
+and queue.npy (the whole 128 x 65536 key queue; the models with one).  Inputs are seeded: the same arguments give the same
+inputs in every run, so two builds can be compared output for output (to rounding, not bit for bit: the weight-gradient
+atomics sum in a different order from run to run).
 
 --config rmcl_pgd (default) is BASELINE configs[2] (the metric's configuration; configs[3] at N=8);
 --config itm_clean is BASELINE configs[1] ("clean ITM + contrastive": ITM + word-patch alignment + CE on the clean
@@ -67,6 +78,32 @@ def synthetic_batch(cfg, B, seed, device):
     return {"image": [img.to(device)], "text": ["synthetic"] * B, "text_ids": ids.to(device),
             "text_masks": torch.ones(B, Lt, dtype=torch.int64, device=device),
             "text_labels": torch.full((B, Lt), -100, dtype=torch.int64, device=device)}
+
+
+DUMP_PARAMS, DUMP_MOMENTUM = 1 << 22, 1 << 21       # sampled elements of the query / momentum parameter arenas (16 + 8 MiB)
+
+
+def sample(t, n, seed):
+    """Fixed seeded sample (sorted positions) of a flat device tensor as float32; the whole tensor when it has at most n elements."""
+    t = t.detach().reshape(-1)
+    if t.numel() > n:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        t = t[torch.randint(0, t.numel(), (n,), generator=g).sort().values.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the last timed step left to its caller - the loss, the parameters after AdamW, the momentum encoder
+    and the key queue - as DIR/<name>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    eng = model.engine
+    out = {"loss": np.array([float(loss.detach())], dtype=np.float64),
+           "params": sample(eng.q32, DUMP_PARAMS, 1), "momentum_params": sample(eng.k32, DUMP_MOMENTUM, 2)}
+    if hasattr(model, "proj_queue"):
+        out["queue"] = model.proj_queue.detach().float().cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def mlp_gemm_replay(L, M, dtype, device, reps=40):
@@ -254,6 +291,10 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--adv-steps", type=int, default=3)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline replay, feed rates, training_realistic, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (loss, parameter samples, key queue)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--drop-rate", type=float, default=0.0,
                     help="0 = the parity configuration (headline); 0.1 = the reference's training default (config.py:57)")
@@ -268,17 +309,19 @@ def main():
     ap.add_argument("--grad-overlap", default="on", choices=["on", "off"],
                     help="N > 1: on = per-layer buckets reduced on the communication stream while the backward runs; off = one blocking "
                          "pass over the arena after the backward (the comparison run)")
-    ap.add_argument("--no-feed-bench", action="store_true", help="skip the input-pipeline feed-rate measurement (tools/feed_bench.py, N = 1 only)")
+    ap.add_argument("--no-feed-bench", action="store_true", help="--full: skip the input-pipeline feed-rate measurement (tools/feed_bench.py, N = 1 only)")
     ap.add_argument("--rehearse-short-batch", action="store_true",
                     help="rehearsal runs only: one extra, untimed step on a HALF-size last batch after the timed steps - the gathered keys then "
                          "number world * B / 2 != per_step_bs and the enqueue must be skipped on every rank (objectives.py:242-243)")
     ap.add_argument("--no-realistic", action="store_true",
-                    help="skip the second, short leg of the default run: the same step in the reference's real recipe (drop_rate 0.1 after a "
+                    help="--full: skip the second, short leg: the same step in the reference's real recipe (drop_rate 0.1 after a "
                          "load_path-style checkpoint load, TRAIN.md:21 / config.py:57) -> `training_realistic` in the JSON line")
     ap.add_argument("--padded-images", action="store_true",
                     help="run the general visual_embed path (pixel-mask patch selection + its device-to-host count read per step) on the "
                          "same full-size synthetic batch instead of the dense fast path")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.grad_overlap == "off":
         os.environ["RMCL_NO_GRAD_OVERLAP"] = "1"
@@ -288,7 +331,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     feed = None
-    if world == 1 and not args.no_feed_bench and args.config == "rmcl_pgd":
+    if args.full and world == 1 and not args.no_feed_bench and args.config == "rmcl_pgd":
         # row f3: what the host pipeline can deliver, measured BEFORE this process touches the GPU (the child and its DataLoader
         # workers never do): reference default of 4 workers... and every core of this box's share
         feed = {}
@@ -395,7 +438,9 @@ def main():
     elapsed = time.perf_counter() - t0
     comm = {k: v / args.steps for k, v in StepTimers.totals_ms().items()} if use_dist else {}
     StepTimers.enabled = False
-    kern_ms, kern_n, kern_fl = mlp_gemm_replay(L, B * 185, args.dtype, device) if rank == 0 else (0.0, 0, 0.0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
+    kern_ms, kern_n, kern_fl = mlp_gemm_replay(L, B * 185, args.dtype, device) if rank == 0 and args.full else (0.0, 0, 0.0)
     ingest = None
     if feed is not None:
         # device side of the byte path: pinned uint8 [B,384,384,3] -> H2D -> ONE kernel (normalise + pad + patch rows), per batch
@@ -488,8 +533,15 @@ def main():
             workload = (f"Barlow-Twins variant of the RMCL step: clean projection + PGD K={K} on the cross-correlation loss + attacked view + "
                         f"full backward + AdamW (ViLT-B/32 + 768-8192-8192-8192 BatchNorm head), bs={B}/GPU (objectives.py:449-602)")
             metric = f"image-text pairs/sec, ViLT-B/32 Barlow-Twins step (PGD K={K})"
-        kern_tf = kern_fl / (kern_ms * 1e-3) / 1e12 if kern_n else 0.0
-        traffic, traffic_note = traffic_record("mlp_fwd_pair") if args.dtype == "bf16" and B == 64 else (None, "PMC record exists for bf16, bs=64 only")
+        roofline = {}
+        if args.full:
+            kern_tf = kern_fl / (kern_ms * 1e-3) / 1e12 if kern_n else 0.0
+            traffic, traffic_note = traffic_record("mlp_fwd_pair") if args.dtype == "bf16" and B == 64 else (None, "PMC record exists for bf16, bs=64 only")
+            roofline["roofline"] = {
+                "bound": "mfma", "achieved": round(kern_tf, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s", "frac": round(kern_tf * 1e12 / PEAK_BF16, 4),
+                "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_note": traffic_note, "kernel_build_id": roofline_kernel_build_id(),
+                "kernel": "encoder MLP forward GEMMs (fc1 768->3072 +bias+GELU, fc2 3072->768 +bias+residual), "
+                          f"M={B * 185}; {kern_n} replayed launches, avg {kern_ms / max(kern_n, 1):.4f} ms"}
         out = {
             "metric": metric, "value": round(value, 2), "unit": "pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
@@ -502,12 +554,7 @@ def main():
                        "grad_sync": f"{args.grad_sync}/{args.grad_dtype}", "final_loss": round(final_loss, 4),
                        "images": ("dense fast path (every synthetic image is full-size: no patch selection, no per-step count read)"
                                   if not args.padded_images else "general visual_embed path (pixel-mask selection + count read per step)")},
-            "roofline": {"bound": "mfma", "achieved": round(kern_tf, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
-                         "frac": round(kern_tf * 1e12 / PEAK_BF16, 4),
-                         "traffic": traffic["bytes_per_launch"] if traffic else None,
-                         "traffic_note": traffic_note, "kernel_build_id": roofline_kernel_build_id(),
-                         "kernel": "encoder MLP forward GEMMs (fc1 768->3072 +bias+GELU, fc2 3072->768 +bias+residual), "
-                                   f"M={B * 185}; {kern_n} replayed launches, avg {kern_ms / max(kern_n, 1):.4f} ms"},
+            **roofline,
             "step_mfma_frac": round(step_flops / (elapsed / args.steps) / PEAK_BF16, 4),
         }
         if short is not None:
@@ -530,9 +577,9 @@ def main():
                            "note": "row f3: host pairs/s of the arrow -> batch pipeline (byte path) beside the step's `value`; the step itself is "
                                    "measured on a batch already resident in HBM"}
         out["config"]["ln_fold"] = "on (shift-robust form)" if model.engine.fold else "off"
-        if world == 1 and args.config == "rmcl_pgd" and args.drop_rate == 0 and not args.no_realistic:
+        if args.full and world == 1 and args.config == "rmcl_pgd" and args.drop_rate == 0 and not args.no_realistic:
             out["training_realistic"] = realistic_leg(model, cfg, batch, args, device, ViLTransformerSS)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(K, args.config)
         print(json.dumps(out), flush=True)
     if use_dist:

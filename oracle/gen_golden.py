@@ -282,7 +282,8 @@ def run_moco(tag, cfg, B, seed_w, seed_b, ragged, sizes=None):
     if sizes is not None:
         out["sizes"] = np.array(sizes)
     path = os.path.join(ROOT, "tests", "golden", f"moco_{tag}.npz")
-    np.savez_compressed(path, **out)
+    from tests import golden_util
+    golden_util.save(path, out)         # image_feats go to side files <stem>.partN.npz (golden_util.load joins them)
     print(tag, "moco_loss", out["moco_loss"], "bytes", os.path.getsize(path))
 
 

@@ -79,7 +79,8 @@ def test_host_code_is_clean_under_asan_and_ubsan():
     rt = _asan_runtime()
     if not os.path.isfile(LIB) or rt is None:
         pytest.skip("lib/librmcl_hip_asan.so not built (csrc/build_host_asan.sh; __graft_entry__.build() builds it where hipcc is present)")
-    env = dict(os.environ, LD_PRELOAD=rt, RMCL_LIB=LIB, RMCL_ROOT=ROOT,
+    preload = ":".join(filter(None, [rt, os.environ.get("LD_PRELOAD")]))      # the ASan runtime first, anything preloaded already after it
+    env = dict(os.environ, LD_PRELOAD=preload, RMCL_LIB=LIB, RMCL_ROOT=ROOT,
                ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0:protect_shadow_gap=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "SANITIZED_HOST_OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])

@@ -2,9 +2,9 @@
 """HBM-side traffic of bench.py's roofline kernels from two rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE cost 3 + 2 of
 the 4 TCC slots: they cannot share a pass, MI355X_MICROARCH.md "rocprofv3 PMC slots").
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write --out profiles/roofline_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d prof/pmc_fetch -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d prof/pmc_write -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+    python tools/pmc_traffic.py prof/pmc_fetch prof/pmc_write --out profiles/roofline_traffic.json
 
 Only the REPLAY launches of bench.py's roofline leg are read (the dispatches after the last adamw_kernel: fc1 + fc2 forward
 GEMMs back to back, the launches `roofline.achieved` is measured on).  Correction as the guide's HBM section prescribes for

@@ -8,7 +8,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04p
 mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-feed-bench --no-realistic"
+B="python3 bench.py --full --no-cpu-baseline --no-feed-bench --no-realistic"
 if [ "${1:-a}" == "a" ]; then
 RMCL_LANES=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $B --steps 3 --warmup 1 > $O/bench_trace_onechain.json 2> $O/trace.err
 python tools/step_timeline.py "$O/trace/**/*_kernel_trace.csv" --md $O/r04_step_table.md > /dev/null
@@ -34,14 +34,14 @@ rm -rf $O/pmc_fetch $O/pmc_write
 echo "pmc traffic done"
 tail -c 300 $O/bench_trace_onechain.json
 else
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "default bench done"
 python tools/chain_bench.py > $O/r04_chain_bench.txt 2>&1 || true
 python tools/infonce_bench.py > $O/r04_infonce_bench.txt 2>&1 || true
-python bench.py --drop-rate 0.1 --no-cpu-baseline --no-feed-bench > $O/bench_dropout.json 2>/dev/null || true
-RMCL_LANES=0 python bench.py --no-cpu-baseline --no-feed-bench --no-realistic > $O/bench_onechain.json 2>/dev/null || true
-python bench.py --config itm_clean --no-cpu-baseline --no-feed-bench > $O/bench_itm_clean.json 2>/dev/null
-python bench.py --config full_rmcl --steps 10 --warmup 2 --no-cpu-baseline --no-feed-bench > $O/bench_full_rmcl.json 2>/dev/null
-python bench.py --config barlowtwins --no-cpu-baseline --no-feed-bench > $O/bench_barlowtwins.json 2>/dev/null
+python bench.py --full --drop-rate 0.1 --no-cpu-baseline --no-feed-bench > $O/bench_dropout.json 2>/dev/null || true
+RMCL_LANES=0 python bench.py --full --no-cpu-baseline --no-feed-bench --no-realistic > $O/bench_onechain.json 2>/dev/null || true
+python bench.py --full --config itm_clean --no-cpu-baseline --no-feed-bench > $O/bench_itm_clean.json 2>/dev/null
+python bench.py --full --config full_rmcl --steps 10 --warmup 2 --no-cpu-baseline --no-feed-bench > $O/bench_full_rmcl.json 2>/dev/null
+python bench.py --full --config barlowtwins --no-cpu-baseline --no-feed-bench > $O/bench_barlowtwins.json 2>/dev/null
 tail -c 600 $O/bench_default.json
 fi
