@@ -268,6 +268,35 @@ int rmcl_bt_dz(const float* zk, const float* G, int B, int N, float inv_bs, floa
 /* rows [B,3] = (||q_b - k_b||, cosine(q_b, k_b) eps 1e-6, q_b . k_b): the distance logs of objectives.py:496-498 */
 int rmcl_bt_pair_metrics(const float* q, const float* k, int B, int N, float* rows, void* stream);
 
+/* ---- VQAv2 fine-tuning head ------------------------------------------------------------------------------------------
+ * vqa_classifier (vilt_module.py:164-172): Linear(D,H) - LayerNorm(H, eps 1e-5) - GELU (exact erf) - Linear(H,N), H = 2D,
+ * N = vqav2_label_size (3129).  w0 [H,D], b0 [H], g1 / b1 [H] (LayerNorm), w3 [N,H], b3 [N]: element offsets in ONE fp32 arena
+ * (parameters and, at the same offsets, gradients).  The arena keeps ldl rows for w3: rows N..ldl-1 are zero padding.
+ * ldl: pitch of the logits / dz rows, a multiple of 64 >= N (3136).  D % 16 == 0, H in {512, 768, 1024, 1536, 2048}, N <= 4096,
+ * 1 <= B <= 256.  All head arithmetic is fp32; nothing uses float atomics (two identical calls give identical bits). */
+typedef struct rmcl_vqa_head {
+  int32_t D, H, N, ldl;
+  int64_t w0, b0, g1, b1, w3, b3;
+} rmcl_vqa_head;
+int64_t rmcl_vqa_stash_floats(const rmcl_vqa_head* h, int B);
+/* logits [B, ldl] (columns N..ldl-1 not written) = vqa_classifier(cls [B,D]); `stash` (rmcl_vqa_stash_floats) keeps what
+ * rmcl_vqa_head_backward needs (a copy of cls, the pre-LayerNorm rows, the GELU output, the row statistics).            */
+int rmcl_vqa_head_forward(const rmcl_vqa_head* h, const float* params, const float* cls, int B, float* stash, float* logits, void* stream);
+/* Soft-target BCE of compute_vqa (objectives.py:871-884) on logits [B, ldl] with SPARSE targets: labels [B,A] int32 (-1 = pad),
+ * scores [B,A]; target[b, labels[b,a]] = scores[b,a] in list order (a repeated label keeps its last score).  Per row:
+ * rows[b] = (sum_c max(z,0) - z t + log1p(exp(-|z|)), t[argmax]), argmax[b] = first maximum over the N classes.
+ * loss2 = (sum_b rows[b][0] / B, sum_b rows[b][1] / B): BCE mean x N (the reference's loss) and VQAScore / B.
+ * dz != NULL: dz [B, ldl] = grad_scale s (sigmoid(z) - t) / B, pad columns 0, s = *grad_scale_dev (a device scalar: the
+ * incoming gradient of the loss inside a backward, read on the device) or 1 when grad_scale_dev is NULL.  dz == NULL: evaluation. */
+int rmcl_vqa_bce(const float* logits, int ldl, const int32_t* labels, const float* scores, int A, int B, int N, float grad_scale,
+                 const float* grad_scale_dev, float* dz, float* rows, int32_t* argmax, float* loss2, void* stream);
+/* out [B, ldo] (N columns written): the dense target matrix of the same label / score tables. */
+int rmcl_vqa_targets_dense(const int32_t* labels, const float* scores, int A, int B, int N, float* out, int ldo, void* stream);
+/* dcls [B,D] = d loss / d cls given dz [B, ldl]; G != NULL: weight / bias / LayerNorm gradients are ACCUMULATED into G at the head's
+ * offsets (NULL: data gradient only - the PGD inner loop, attack/pgd_attack_vilt.py:448-466).                          */
+int rmcl_vqa_head_backward(const rmcl_vqa_head* h, const float* params, float* stash, const float* dz, int B, float* G, float* dcls,
+                           void* stream);
+
 /* One joint text+image encoder forward up to transformer.norm: replaces ViLTransformerSS.infer /
  * infer_k (vilt_module.py:275-418) minus the pooler.  params32: fp32 arena; params_lp: bf16
  * shadow arena (NULL when dtype is F32).  text_ids/text_mask [B,L] int64; patches [B*P,patch_k]

@@ -53,6 +53,12 @@ class BtHead(C.Structure):
                 ("w3", C.c_int64)]
 
 
+class VqaHead(C.Structure):
+    """include/rmcl.h rmcl_vqa_head: widths of the VQA classifier, the logits pitch and the arena offsets of its tensors."""
+    _fields_ = [("D", C.c_int32), ("H", C.c_int32), ("N", C.c_int32), ("ldl", C.c_int32),
+                ("w0", C.c_int64), ("b0", C.c_int64), ("g1", C.c_int64), ("b1", C.c_int64), ("w3", C.c_int64), ("b3", C.c_int64)]
+
+
 class RmclError(RuntimeError):
     pass
 
@@ -65,7 +71,8 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     lib.rmcl_last_error.restype = C.c_char_p
     for name in ("rmcl_stash_bytes", "rmcl_workspace_bytes", "rmcl_heads_stash_bytes", "rmcl_infonce_ws_bytes",
-                 "rmcl_attention_scratch_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats"):
+                 "rmcl_attention_scratch_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats",
+                 "rmcl_vqa_stash_floats"):
         getattr(lib, name).restype = C.c_int64
     return lib
 
@@ -83,6 +90,7 @@ EXPORTS = (
     "rmcl_attention_bwd",
     "rmcl_bt_stash_floats", "rmcl_bt_head_forward", "rmcl_bt_head_backward", "rmcl_bt_corr", "rmcl_bt_loss_ws_floats", "rmcl_bt_loss",
     "rmcl_bt_dz", "rmcl_bt_pair_metrics",
+    "rmcl_vqa_stash_floats", "rmcl_vqa_head_forward", "rmcl_vqa_bce", "rmcl_vqa_targets_dense", "rmcl_vqa_head_backward",
 )
 
 

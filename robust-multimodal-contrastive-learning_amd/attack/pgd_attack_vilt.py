@@ -2,7 +2,8 @@
 reference (class names, constructor keys, ``pgd_attack(pl_module, batch, k_modality)`` -> delta),
 but runs K x (encoder forward, InfoNCE, data-gradient backward, L-inf-normalised ascent step,
 eps-projection) as HIP kernels with no deepcopy of the encoder and no weight-gradient work.
-``PGDAttack_bartlowtwins`` (sic, :178-236) is the same loop on the Barlow-Twins cross-correlation loss."""
+``PGDAttack_bartlowtwins`` (sic, :178-236) is the same loop on the Barlow-Twins cross-correlation loss, ``PGDAttack_vqa``
+(:418-483) on the VQA soft-target BCE."""
 from __future__ import annotations
 
 import torch
@@ -202,5 +203,57 @@ class PGDAttack_bartlowtwins(PGDAttack):
             img_init = img_init.to(eng.device).float_image()
         pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init, tag="bt")
         delta_p = self.attack_patches(pl_module, pb, k_modality.to(eng.device, torch.float32).contiguous(), keep_prev=True)
+        batch["image"][0] = img_init.to(eng.device) + eng.patches_to_image(pb.delta_prev, pb)
+        return eng.patches_to_image(delta_p, pb)
+
+
+class PGDAttack_vqa(PGDAttack):
+    """attack/pgd_attack_vilt.py:418-483: K steps of (forward at img + delta, vqa_classifier, BCE-with-logits x vqav2_label_size - NOT
+    divided by K, data gradient, L-inf-normalised ascent step with the 1e-8 clamp, clip to eps).  The reference runs the live
+    module and its backward() also leaves weight gradients in .grad; under its fp16 recipe those are removed by the loss scale
+    (INTEGRATION.md), so here the loop runs data gradients only: encoder MODE_DATA, head backward without weight gradients -
+    nothing is written into the gradient arena."""
+
+    def __init__(self, config):
+        super().__init__(config, "vqa")
+
+    def attack_patches(self, pl_module, pb, vb_tables, clean_op=None, keep_prev=False):
+        """Leaves delta_K in ``pb.delta`` and the attacked view's operand cast(img + delta_{K-1} + delta_K) (compute_pgd,
+        objectives.py:176) in ``pb.patchesT_full``.  ``vb_tables``: VqaBuffers holding this batch's label / score tables
+        (Engine.vqa_targets); the loop's head passes run in them."""
+        eng = pl_module.engine
+        K = self.adv_steps_img
+        pb0 = pb
+        pb = eng.pgd_bufs(pb)                                 # fp32 twin when the engine runs PGD in fp32
+        vb = vb_tables
+        op = clean_op if (clean_op is not None and pb is pb0) else eng.make_operand(pb)      # delta_0 = 0
+        for step in range(K):
+            last = step == K - 1
+            eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
+            eng.heads_forward(pb, key=False, want_q=False, wgrad=False)
+            eng.vqa_forward(vb, pb.cls)
+            eng.vqa_bce(vb, 1.0, want_dz=True)                                        # :444-460, d loss / d logits
+            dcls = eng.vqa_backward(vb, vb.dz, with_grads=False)
+            eng.heads_backward(pb, None, dcls, with_grads=False)
+            eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=pb.gpatch)
+            if last and keep_prev:
+                if K > 1:
+                    pb.delta_prev.copy_(pb.delta)
+                else:
+                    pb.delta_prev.zero_()
+            op = pb0.patchesT_full if last else pb.patchesT
+            eng.pgd_step(pb, self.adv_lr_img, self.adv_max_norm_img, first=step == 0, out=op, sum_prev=last)   # :464-481
+        return pb.delta
+
+    def pgd_attack(self, pl_module, batch, k_modality=None):
+        eng = pl_module.engine
+        img_init = batch["image"][0]
+        if hasattr(img_init, "tables"):
+            img_init = eng.resize_raw(img_init)
+        if hasattr(img_init, "float_image"):
+            img_init = img_init.to(eng.device).float_image()
+        pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init, tag="vqa_att")
+        vb = eng.vqa_targets(eng.vqa_bufs(pb.B, "pgd"), batch["vqa_labels"], batch["vqa_scores"])
+        delta_p = self.attack_patches(pl_module, pb, vb, keep_prev=True)
         batch["image"][0] = img_init.to(eng.device) + eng.patches_to_image(pb.delta_prev, pb)
         return eng.patches_to_image(delta_p, pb)

@@ -114,6 +114,47 @@ class BtBuffers:
         self.loss2 = f32(2)
 
 
+def vqa_layout(cfg: dict, base: int):
+    """vqa_classifier (vilt_module.py:164-172: Linear(D, 2D) - LayerNorm(2D) - GELU - Linear(2D, vqav2_label_size)) appended to the
+    parameter arena at element offset `base`: returns (rmcl_vqa_head struct, specs, elements used).  The last weight keeps ldl rows
+    in the arena (ldl = the logits pitch, a multiple of 64): rows N..ldl-1 stay zero (no gradient reaches them, AdamW leaves a zero
+    parameter with a zero gradient at zero), so the data gradient dz W3 runs on the padded width."""
+    D = cfg["hidden_size"]
+    H, N = 2 * D, int(cfg["vqav2_label_size"])
+    ldl = (N + 63) // 64 * 64
+    n = "vqa_classifier."
+    shapes = [("w0", n + "0.weight", (H, D), H * D), ("b0", n + "0.bias", (H,), H), ("g1", n + "1.weight", (H,), H),
+              ("b1", n + "1.bias", (H,), H), ("w3", n + "3.weight", (N, H), ldl * H), ("b3", n + "3.bias", (N,), N)]
+    off, offs, specs = base, {}, []
+    for key, name, shape, cnt in shapes:
+        offs[key] = off
+        specs.append((name, off, shape))
+        off += (cnt + 63) // 64 * 64
+    return L.VqaHead(D=D, H=H, N=N, ldl=ldl, **offs), specs, off - base
+
+
+class VqaBuffers:
+    """Per-pass buffers of the VQA head: its stash, the pitched logits and dz, the row outputs, and the label / score tables of the
+    batch (one pinned host buffer, one asynchronous copy: ``Engine.vqa_targets``)."""
+
+    def __init__(self, eng: "Engine", B: int):
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=eng.device)
+        h = eng.vqa
+        self.B = B
+        self.stash = f32(int(lib.rmcl_vqa_stash_floats(C.byref(h), B)))
+        self.logits_p = f32(B, h.ldl)
+        self.logits = self.logits_p[:, : h.N]                  # the public [B, N] view
+        self.dz = f32(B, h.ldl)
+        self.dcls = f32(B, h.D)
+        self.rows = f32(B, 2)
+        self.argmax = torch.empty(B, dtype=torch.int32, device=eng.device)
+        self.loss2 = f32(2)
+        self.A = 0
+        self.tab = None                                         # device [2, B, A] int32: labels, then the scores' bits
+        self.labels = self.scores = None
+        self._host = None
+
+
 class PassBuffers:
     """Everything sized by the per-GPU batch B (allocated once, reused every step)."""
 
@@ -239,6 +280,13 @@ class Engine:
             self.bt_corr = torch.empty(H.H3, H.H3, dtype=torch.float32, device=self.device)
             self.bt_ws = torch.empty(int(lib.rmcl_bt_loss_ws_floats(H.H3)), dtype=torch.float32, device=self.device)
             self._bt_bufs = {}
+        # optional VQA classifier (loss_names["vqa"] / ["vqa_attacked"] > 0): appended behind the same arena, like the Barlow-Twins head
+        self.vqa, self.vqa_specs = None, []
+        ln = cfg.get("loss_names", {})
+        if ln.get("vqa", 0) > 0 or ln.get("vqa_attacked", 0) > 0:
+            self.vqa, self.vqa_specs, n_vqa = vqa_layout(cfg, int(lay.total) + extra)
+            extra += n_vqa
+            self._vqa_bufs = {}
         self.total = int(lay.total) + extra
         self.q32 = z(self.total)
         self.k32 = z(lay.ema_end)
@@ -257,7 +305,7 @@ class Engine:
         # transposed bf16 shadows of the layer weights for the data-gradient GEMMs (include/rmcl.h rmcl_weight_transpose_bf16)
         self.q_lpT = z(lay.total, torch.bfloat16) if (self.dtype == L.BF16 and os.environ.get("RMCL_NO_WT", "0") != "1") else None
         self.lpT_stale = True
-        self.specs = param_specs(cfg, lay) + self.bt_specs
+        self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs
         self._bufs: Dict[tuple, PassBuffers] = {}
         self.lp_stale = True
         self.drop_p = float(cfg.get("drop_rate", 0.0))
@@ -689,6 +737,80 @@ class Engine:
     def bt_pair_metrics(self, bb: BtBuffers, zk: torch.Tensor):
         check(lib.rmcl_bt_pair_metrics(P(bb.z), P(zk), bb.B, self.bt.H3, P(bb.rows), stream_ptr()), "bt_pair_metrics")
         return bb.rows
+
+    # ---- VQA head (include/rmcl.h rmcl_vqa_*) ------------------------------------------------------------------------
+    def vqa_bufs(self, B: int, tag: str) -> VqaBuffers:
+        if (B, tag) not in self._vqa_bufs:
+            self._vqa_bufs[(B, tag)] = VqaBuffers(self, B)
+        return self._vqa_bufs[(B, tag)]
+
+    def vqa_targets(self, vb: VqaBuffers, labels, scores):
+        """Packs the per-sample label / score lists (``batch["vqa_labels"]`` / ``["vqa_scores"]``, rows may be empty) into ONE pinned
+        host buffer [2, B, A] (int32 labels padded with -1, then the fp32 scores' bits) and sends it with one asynchronous copy.
+        A label outside [0, vqav2_label_size) is a ValueError (an IndexError in the reference's dense fill, objectives.py:875-877)."""
+        B, N = vb.B, self.vqa.N
+        if len(labels) != B or len(scores) != B:
+            raise ValueError(f"vqa_labels / vqa_scores must have one entry per sample ({len(labels)} / {len(scores)} for a batch of {B})")
+        rows_l = [[int(x) for x in (l.tolist() if torch.is_tensor(l) else l)] for l in labels]
+        rows_s = [[float(x) for x in (s.tolist() if torch.is_tensor(s) else s)] for s in scores]
+        A = max([1] + [len(r) for r in rows_l])
+        for b, (rl, rs) in enumerate(zip(rows_l, rows_s)):
+            if len(rl) != len(rs):
+                raise ValueError(f"sample {b}: {len(rl)} vqa_labels but {len(rs)} vqa_scores")
+            bad = [x for x in rl if x < 0 or x >= N]
+            if bad:
+                raise ValueError(f"sample {b}: vqa label(s) {bad} outside [0, {N}) (vqav2_label_size)")
+        if vb._host is None or vb._host.numel() < 2 * B * A:
+            vb._host = torch.empty(2 * B * A, dtype=torch.int32, pin_memory=True)
+            vb.tab = torch.empty(2 * B * A, dtype=torch.int32, device=self.device)
+            vb._copied = None
+        self._vqa_host_free(vb)
+        host = vb._host[: 2 * B * A].view(2, B, A)
+        host[0].fill_(-1)
+        host[1].zero_()
+        sco = host[1].view(torch.float32)
+        for b, (rl, rs) in enumerate(zip(rows_l, rows_s)):
+            if rl:
+                host[0, b, : len(rl)] = torch.tensor(rl, dtype=torch.int32)
+                sco[b, : len(rs)] = torch.tensor(rs, dtype=torch.float32)
+        dev = vb.tab[: 2 * B * A].view(2, B, A)
+        dev.copy_(host, non_blocking=True)
+        vb._copied = torch.cuda.Event()
+        vb._copied.record()
+        vb.A = A
+        vb.labels, vb.scores = dev[0], dev[1].view(torch.float32)
+        return vb
+
+    @staticmethod
+    def _vqa_host_free(vb: VqaBuffers):
+        """the pinned table is rewritten only after the previous batch's copy out of it has completed"""
+        ev = getattr(vb, "_copied", None)
+        if ev is not None:
+            ev.synchronize()
+
+    def vqa_forward(self, vb: VqaBuffers, cls: torch.Tensor):
+        check(lib.rmcl_vqa_head_forward(C.byref(self.vqa), P(self.q32), P(cls), vb.B, P(vb.stash), P(vb.logits_p), stream_ptr()),
+              "vqa_head_forward")
+        return vb.logits
+
+    def vqa_bce(self, vb: VqaBuffers, grad_scale: float, want_dz: bool, scale_dev: torch.Tensor = None, loss2: torch.Tensor = None):
+        """loss2 = (vqa_loss, VQAScore) of the batch; rows / argmax per sample; dz (want_dz) = grad_scale [* scale_dev, a device scalar]
+        d vqa_loss / d logits."""
+        loss2 = vb.loss2 if loss2 is None else loss2
+        check(lib.rmcl_vqa_bce(P(vb.logits_p), self.vqa.ldl, P(vb.labels), P(vb.scores), vb.A, vb.B, self.vqa.N, F(grad_scale), P(scale_dev),
+                               P(vb.dz if want_dz else None), P(vb.rows), P(vb.argmax), P(loss2), stream_ptr()), "vqa_bce")
+        return loss2
+
+    def vqa_backward(self, vb: VqaBuffers, dz: torch.Tensor, with_grads: bool):
+        check(lib.rmcl_vqa_head_backward(C.byref(self.vqa), P(self.q32), P(vb.stash), P(dz), vb.B, P(self.g32 if with_grads else None),
+                                         P(vb.dcls), stream_ptr()), "vqa_head_backward")
+        return vb.dcls
+
+    def vqa_targets_dense(self, vb: VqaBuffers) -> torch.Tensor:
+        out = torch.empty(vb.B, self.vqa.N, dtype=torch.float32, device=self.device)
+        check(lib.rmcl_vqa_targets_dense(P(vb.labels), P(vb.scores), vb.A, vb.B, self.vqa.N, P(out), self.vqa.N, stream_ptr()),
+              "vqa_targets_dense")
+        return out
 
     def pgd_step(self, pb: PassBuffers, lr: float, eps: float, first: bool = False, out: torch.Tensor = None, sum_prev: bool = False):
         """delta <- clamp(delta + lr g / max|g|, +-eps) (pgd_attack_vilt.py:162-173).  ``out``: also written in the same pass,

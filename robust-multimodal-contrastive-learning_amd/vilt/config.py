@@ -56,3 +56,36 @@ def task_barlowtwins(**over):
     )
     cfg.update(over)
     return cfg
+
+
+def task_finetune_vqa(**over):
+    """reference config.py:289-302: VQAv2 fine-tuning (vqa_classifier + soft-target BCE).  max_steps None as in the reference:
+    set_schedule then needs it from the caller."""
+    cfg = default_config(
+        exp_name="finetune_vqa", datasets=["vqa"], loss_names=_loss_names({"vqa": 1}), batch_size=256, max_epoch=10,
+        max_steps=None, warmup_steps=0.1, draw_false_image=0, learning_rate=1e-4, val_check_interval=0.1, lr_mult=10,
+    )
+    cfg.update(over)
+    return cfg
+
+
+def task_finetune_vqa_randaug(**over):
+    """reference config.py:305-317: as task_finetune_vqa with the RandAugment train transform (the transform itself is the caller's)."""
+    cfg = task_finetune_vqa(exp_name="finetune_vqa_randaug", train_transform_keys=["pixelbert_randaug"])
+    cfg.update(over)
+    return cfg
+
+
+def task_finetune_vqa_randaug_attacked(**over):
+    """reference config.py:319-348: adversarial VQAv2 fine-tuning.  Both views default to False as in the reference, which then fails
+    in compute_vqa_attack; here the module refuses that at construction (ValueError): pass image_view=True (PGD on the image)."""
+    cfg = default_config(
+        exp_name="finetune_vqa_randaug_attacked", datasets=["vqa"], train_transform_keys=["pixelbert_randaug"],
+        loss_names=_loss_names({"vqa_attacked": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,
+        draw_false_image=0, learning_rate=1e-4, val_check_interval=0.1, lr_mult=10,
+        text_view=False, image_view=False, adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005,
+        n_candidates=5, max_loops=10, sim_thred=0.5, cos_sim=True, synonym="cos_sim",
+        embedding_path="../attack/counter-fitted-vectors.txt", sim_path="../attack/cos_sim_counter_fitting.npy",
+    )
+    cfg.update(over)
+    return cfg

@@ -478,3 +478,69 @@ def compute_barlowtwins_contrastive(pl_module, batch):
         pl_module.log(f"barlowtwins/{phase}/barlowtwins_loss_invariance_{name}", ret[f"barlowtwins_loss_invariance_{name}"].detach())
         pl_module.log(f"barlowtwins/{phase}/barlowtwins_loss_redundancy_{name}", ret[f"barlowtwins_loss_redundancy_{name}"].detach())
     return ret
+
+
+def _vqa_head_loss(pl_module, pb, op, batch, task, vb_tag, tables=None):
+    """Encoder forward of the view in `op`, pooler, vqa_classifier and the soft-target BCE (objectives.py:813-896): returns the
+    reference's dict with a ``vqa_loss`` whose backward runs BCE gradient -> head -> pooler -> encoder (MODE_FULL) into the
+    gradient arena.  ``tables``: VqaBuffers whose label / score tables this batch already sent (the PGD loop's)."""
+    eng = pl_module.engine
+    need_grad = torch.is_grad_enabled() and pl_module.training
+    eng.encoder_forward(pb, key=False, mode=L.MODE_FULL if need_grad else L.MODE_INFER, patchesT=op, cls_tail=True)
+    eng.heads_forward(pb, key=False, want_q=False, wgrad=need_grad)
+    vb = eng.vqa_bufs(pb.B, vb_tag)
+    if tables is None:
+        eng.vqa_targets(vb, batch["vqa_labels"], batch["vqa_scores"])
+    else:
+        vb.labels, vb.scores, vb.A = tables.labels, tables.scores, tables.A
+    logits = eng.vqa_forward(vb, pb.cls)
+    loss2 = eng.vqa_bce(vb, 1.0, want_dz=False, loss2=torch.empty(2, dtype=torch.float32, device=eng.device))
+    value = _scalar(loss2[0])
+    if need_grad:
+        def backward(grad_out, pb=pb, vb=vb, op=op):
+            g = grad_out.to(torch.float32).reshape(1).contiguous()
+            eng.vqa_bce(vb, 1.0, want_dz=True, scale_dev=g, loss2=torch.empty(2, dtype=torch.float32, device=eng.device))
+            dcls = eng.vqa_backward(vb, vb.dz, with_grads=True)
+            eng.heads_backward(pb, None, dcls, with_grads=True)
+            eng.encoder_backward(pb, L.MODE_FULL, op, pb.dcls, cls_only=True, dpatches=None)
+            pl_module.after_backward(overlap=True)
+
+        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+    ret = {
+        "vqa_loss": value,
+        "vqa_logits": logits,
+        "vqa_targets": eng.vqa_targets_dense(vb),
+        "vqa_labels": batch["vqa_labels"],
+        "vqa_scores": batch["vqa_scores"],
+        "vqa_preds": vb.argmax,                     # (first maximum of the logits: what VQAScore and vqa_test_step read)
+    }
+    phase = "train" if pl_module.training else "val"
+    pl_module.log(f"{task}/{phase}/loss", value.detach())
+    pl_module.log(f"{task}/{phase}/score", loss2[1])
+    return ret
+
+
+def compute_vqa(pl_module, batch):
+    """objectives.py:861-896: vqa_classifier on the pooler output of the clean batch, BCE-with-logits x vqav2_label_size."""
+    eng = pl_module.engine
+    pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], batch["image"][0], tag="vqa")
+    op = eng.make_operand(pb, out=pb.patchesT_full)
+    return _vqa_head_loss(pl_module, pb, op, batch, "vqa", "vqa")
+
+
+def compute_vqa_attack(pl_module, batch):
+    """objectives.py:813-859 (image view): PGD on the VQA loss (PGDAttack_vqa, through compute_pgd's img + delta_{K-1} + delta_K),
+    then the head and the loss on the attacked view.  The batch itself is not modified (the reference attacks a deepcopy)."""
+    eng = pl_module.engine
+    if pl_module.text_view:
+        raise NotImplementedError("vqa_attacked with text_view (GreedyAttack_vqa) is outside the RMCL hot path")
+    phase = "train" if pl_module.training else "val"
+    pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], batch["image"][0], tag="vqa_att")
+    op = eng.make_operand(pb)                                                 # img + delta_0, delta_0 = 0
+    vp = eng.vqa_targets(eng.vqa_bufs(pb.B, "pgd"), batch["vqa_labels"], batch["vqa_scores"])
+    pl_module.pgd_attacker.attack_patches(pl_module, pb, vp, clean_op=op)    # compute_pgd (:816)
+    check(lib.rmcl_delta_channel_norm(P(pb.delta), P(eng.zero_scalar(pb)), I64(pb.delta.shape[0]), 3, pb.d.patch_k // 3,
+                                      stream_ptr()), "delta_norm")
+    n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
+    pl_module.log(f"vqa_attacked_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
+    return _vqa_head_loss(pl_module, pb, pb.patchesT_full, batch, "vqa_attacked", "vqa_att", tables=vp)

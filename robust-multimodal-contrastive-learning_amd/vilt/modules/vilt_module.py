@@ -16,7 +16,7 @@ import torch.nn as nn
 from ... import _lib as L
 from ..._lib import lib, check
 from ...runtime import Engine, EMA_GROUPS
-from ...attack.pgd_attack_vilt import PGDAttack_moco, PGDAttack_bartlowtwins
+from ...attack.pgd_attack_vilt import PGDAttack_moco, PGDAttack_bartlowtwins, PGDAttack_vqa
 from ...attack.greedy_attack_vilt import GreedyAttack_moco, GreedyAttack_barlowtwins
 from . import objectives, vilt_utils, dist_utils
 
@@ -142,6 +142,18 @@ class ViLTransformerSS(nn.Module):
                 self.greedy_attacker = GreedyAttack_barlowtwins(config)
             if self.image_view and not self.augmentation:
                 self.pgd_attacker = PGDAttack_bartlowtwins(config)
+        ln = config["loss_names"]
+        if ln.get("vqa_attacked", 0) > 0:                                  # vilt_module.py:175-191
+            self.image_view = config.get("image_view", False)
+            self.text_view = config.get("text_view", False)
+            if not (self.image_view or self.text_view):
+                # the reference reaches compute_vqa_attack with `infer` unbound (NameError, objectives.py:825) - this default of
+                # task_finetune_vqa_randaug_attacked is refused here, at construction
+                raise ValueError("loss_names['vqa_attacked'] > 0 needs image_view=True (text_view / GreedyAttack_vqa is not built)")
+            if self.text_view:
+                raise NotImplementedError("vqa_attacked with text_view=True (GreedyAttack_vqa) is outside the RMCL hot path")
+            self.pgd_attacker = PGDAttack_vqa(config)
+        self.id2answer = None                      # answer strings of the label ids (test_step); the reference reads them from its datamodule
         self.grad_anchor = torch.zeros((), device=eng.device, requires_grad=True)
         self.sync_grads = True                     # False on the early micro-steps of gradient accumulation (DDP no_sync)
         self.step_sync = dist_utils.StepGradSync(algo=config.get("grad_allreduce_algo", "ring"), compress=config.get("grad_allreduce_dtype"))
@@ -168,8 +180,12 @@ class ViLTransformerSS(nn.Module):
         wrong = [(k, tuple(v.shape), tuple(mine[k].shape)) for k, v in state_dict.items() if k in mine and tuple(mine[k].shape) != tuple(v.shape)]
         if wrong:
             raise RuntimeError("Error(s) in loading state_dict: " + "; ".join(f"size mismatch for {k}: checkpoint {a}, model {b}" for k, a, b in wrong))
-        res = self.load_state_dict({k: v for k, v in state_dict.items() if k in mine}, strict=False)
-        unexpected = sorted(k for k in state_dict if k not in mine)
+        # downstream heads exist only AFTER the training-time load in the reference (vilt_module.py:134-160 loads, :164 builds the VQA
+        # head): a checkpoint's vqa_classifier.* keep their init unless test_only (:254-268 loads after the heads were built)
+        late = () if self.hparams.config.get("test_only", False) else ("vqa_classifier.",)
+        take = {k: v for k, v in state_dict.items() if k in mine and not k.startswith(late)}
+        res = self.load_state_dict(take, strict=False)
+        unexpected = sorted(k for k in state_dict if k not in take)
         self.load_report = {"missing": sorted(res.missing_keys), "unexpected": unexpected}
         if res.missing_keys or unexpected:
             import warnings
@@ -193,7 +209,16 @@ class ViLTransformerSS(nn.Module):
                 continue
             leaf = name.split(".")[-1]
             is_ln = any(t in name for t in ("LayerNorm", "norm1", "norm2", "transformer.norm", "projector.1"))
-            if name.startswith("barlowtwins_head."):
+            if name.startswith("vqa_classifier."):
+                # objectives.init_weights (:1505-1516) applied to the head (vilt_module.py:172): Linear N(0, 0.02) / bias 0, LayerNorm 1 / 0
+                # (the substring rule below would miss the LayerNorm gain "vqa_classifier.1.weight")
+                if name.startswith("vqa_classifier.1."):
+                    p.fill_(1.0 if leaf == "weight" else 0.0)
+                elif leaf == "bias":
+                    p.zero_()
+                else:
+                    p.normal_(mean=0.0, std=0.02)
+            elif name.startswith("barlowtwins_head."):
                 # never passed through init_weights in the reference (vilt_module.py:115): nn.Linear / nn.BatchNorm1d defaults
                 if p.dim() == 2:
                     nn.init.kaiming_uniform_(p, a=math.sqrt(5))
@@ -387,7 +412,11 @@ class ViLTransformerSS(nn.Module):
             ret.update(objectives.compute_moco_contrastive(self, batch))
         if "barlowtwins" in self.current_tasks:
             ret.update(objectives.compute_barlowtwins_contrastive(self, batch))
-        unsupported = [t for t in self.current_tasks if t not in ("itm", "moco", "barlowtwins")]
+        if "vqa" in self.current_tasks:
+            ret.update(objectives.compute_vqa(self, batch))
+        if "vqa_attacked" in self.current_tasks:
+            ret.update(objectives.compute_vqa_attack(self, batch))
+        unsupported = [t for t in self.current_tasks if t not in ("itm", "moco", "barlowtwins", "vqa", "vqa_attacked")]
         if unsupported:
             raise NotImplementedError(f"tasks {unsupported} are outside the RMCL hot path (SURVEY 8)")
         return ret
@@ -413,7 +442,13 @@ class ViLTransformerSS(nn.Module):
         vilt_utils.epoch_wrapup(self)
 
     def test_step(self, batch, batch_idx):
-        return self.validation_step(batch, batch_idx)
+        output = self.validation_step(batch, batch_idx)
+        if "vqa_preds" in output:                                          # vqa_test_step (objectives.py:1519-1530)
+            preds = output["vqa_preds"].tolist()
+            if self.id2answer is not None:
+                preds = [self.id2answer[i] for i in preds]
+            return {"qids": batch["qid"], "preds": preds}
+        return output
 
     def configure_optimizers(self):
         return vilt_utils.set_schedule(self)
