@@ -53,6 +53,12 @@ typedef struct rmcl_dims {
   int exact;    /* 1: force the exact-f32 matrix-core GEMM (bf16 operands widened)   */
   int Pp;       /* patches of the position table ((image_size/patch)^2 = 144); 0 = P. Differs from P for zero-padded
                    batches of smaller images, where P = selected patches per sample (rmcl_ragged)                  */
+  int n_types;  /* rows of token_type_embeddings: 0 or 2 = the pre-training table; 3 = NLVR2 (vilt_module.py:193-231: rows
+                   [old0, old1, old1] after the resize).  Only 3 changes the arena layout (3 D elements for vtype)          */
+  int img_type; /* token-type row added to every image token (vilt_module.py:315-321 image_token_type_idx): 0 or 1 = row 1;
+                   2 = row 2 (n_types 3); -1 = per PAIR (n_types 3, B even): sample b gets row 1 + (b & 1) - the NLVR2 pair
+                   pass with image_0[i] at sample 2i and image_1[i] at 2i + 1.  In FULL mode the token-type gradient of
+                   the image tokens lands in the row(s) used                                                                 */
 } rmcl_dims;
 
 /* Zero-padded batch of smaller images (VisionTransformer.visual_embed, vision_transformer.py:559-677): `patches` then
@@ -139,7 +145,7 @@ int rmcl_l2_prefetch_experiment(const void* A, int64_t lda_bytes, int M, int row
 /* Element offsets into a parameter arena.  Names follow the reference state dict. */
 typedef struct rmcl_layout {
   int64_t word, pos, btype, eln_w, eln_b;      /* text_embeddings.{word,position,token_type}_embeddings, LayerNorm */
-  int64_t vtype;                               /* token_type_embeddings.weight [2,D]                               */
+  int64_t vtype;                               /* token_type_embeddings.weight [2,D] ([3,D] when n_types == 3)     */
   int64_t cls, pos_img, patch_w, patch_b;      /* transformer.{cls_token,pos_embed,patch_embed.proj.*}             */
   int64_t layer0, layer_stride;                /* transformer.blocks.<i> base = layer0 + i*layer_stride            */
   int64_t ln1_w, ln1_b, qkv_w, qkv_b, proj_w, proj_b, ln2_w, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b; /* rel. to block */
@@ -296,6 +302,23 @@ int rmcl_vqa_targets_dense(const int32_t* labels, const float* scores, int A, in
  * offsets (NULL: data gradient only - the PGD inner loop, attack/pgd_attack_vilt.py:448-466).                          */
 int rmcl_vqa_head_backward(const rmcl_vqa_head* h, const float* params, float* stash, const float* dz, int B, float* G, float* dcls,
                            void* stream);
+
+/* ---- NLVR2 fine-tuning ------------------------------------------------------------------------------------------------
+ * nlvr2_classifier (vilt_module.py:193-200): Linear(2D,2D) - LayerNorm(2D) - GELU - Linear(2D,2) is the VQA head above with
+ * D = H = 2 * hidden, N = 2, ldl = 64 (rmcl_vqa_head_forward / _backward on an rmcl_vqa_head describing it).  Its input is the
+ * pair pass's pooled cls [2B, hidden] read as [B, 2 hidden] (image_0's cls, then image_1's: sample 2i / 2i + 1).
+ * Hard-label softmax cross-entropy of compute_nlvr2 / compute_nlvr2_attack / PGDAttack_nlvr2 (objectives.py:898-1060,
+ * pgd_attack_vilt.py:285-300) on logits [B, ldl] (N columns used), labels [B] int32 in [0, N) (the kernel clamps a label outside into
+ * [0, N): callers validate on the host).  One wave per row, one workgroup, no float atomics: two identical
+ * calls give identical bits.  Outputs:
+ *   rows [B]      per-row loss  lse(z) - z[label]
+ *   argmax [B]    first maximum of the row
+ *   stats [3]     (mean loss, rows with argmax == label, rows whose argmax differs from logits_ref's - 0 when logits_ref is NULL)
+ *   dz (optional) [B, ldl] = grad_scale * s * (softmax(z) - onehot) / B, pad columns 0, s = *grad_scale_dev or 1 when NULL.
+ * logits_ref (optional): a second logits buffer [B, ld_ref] - the changed-argmax count of change_rate_cross (my_metrics.py:30-45).
+ * 1 <= N <= 64, N <= ldl, 1 <= B <= 65536.                                                                                 */
+int rmcl_nlvr2_ce(const float* logits, int ldl, const int32_t* labels, int B, int N, float grad_scale, const float* grad_scale_dev,
+                  float* dz, float* rows, int32_t* argmax, const float* logits_ref, int ld_ref, float* stats, void* stream);
 
 /* One joint text+image encoder forward up to transformer.norm: replaces ViLTransformerSS.infer /
  * infer_k (vilt_module.py:275-418) minus the pooler.  params32: fp32 arena; params_lp: bf16

@@ -22,7 +22,7 @@ EPI_LNFOLD, EPI_ROWSTAT = 2048, 4096
 
 class Dims(C.Structure):
     _fields_ = [(n, C.c_int) for n in
-                ("B", "L", "P", "D", "H", "layers", "mlp", "patch_k", "proj", "vocab", "dtype", "exact", "Pp")]
+                ("B", "L", "P", "D", "H", "layers", "mlp", "patch_k", "proj", "vocab", "dtype", "exact", "Pp", "n_types", "img_type")]
 
 
 class Ragged(C.Structure):
@@ -91,6 +91,7 @@ EXPORTS = (
     "rmcl_bt_stash_floats", "rmcl_bt_head_forward", "rmcl_bt_head_backward", "rmcl_bt_corr", "rmcl_bt_loss_ws_floats", "rmcl_bt_loss",
     "rmcl_bt_dz", "rmcl_bt_pair_metrics",
     "rmcl_vqa_stash_floats", "rmcl_vqa_head_forward", "rmcl_vqa_bce", "rmcl_vqa_targets_dense", "rmcl_vqa_head_backward",
+    "rmcl_nlvr2_ce",
 )
 
 

@@ -257,3 +257,103 @@ class PGDAttack_vqa(PGDAttack):
         delta_p = self.attack_patches(pl_module, pb, vb, keep_prev=True)
         batch["image"][0] = img_init.to(eng.device) + eng.patches_to_image(pb.delta_prev, pb)
         return eng.patches_to_image(delta_p, pb)
+
+
+class PGDAttack_nlvr2(PGDAttack):
+    """attack/pgd_attack_vilt.py:241-342: K steps on the pair (image_0 with token type 1, image_1 with token type 2), loss =
+    CE(nlvr2_classifier(cat(cls_0, cls_1)), answers) / K, one delta per image, updated only where config["attack_idx"][i] is set (a
+    non-attacked image keeps delta 0), each step the L-inf-normalised ascent step with the 1e-8 clamp and the clip to eps.  The reference
+    runs a deep copy of the modules, so nothing reaches the live model's gradients: here the loop runs data gradients only (encoder
+    MODE_DATA, head backward without weight gradients) and writes nothing into the gradient arena.  In the pair form both deltas live
+    in one patch-layout buffer of 2B samples: pgd_step's per-sample step is per image."""
+
+    def __init__(self, config):
+        super().__init__(config, "nlvr2")
+        self.attack_idx = [bool(a) for a in config["attack_idx"]]
+
+    def attack_pairs(self, pl_module, npass, nb, keep_prev=False):
+        """Leaves delta_K of every view in ``pv.delta`` and the attacked operand cast(img + delta_{K-1} + delta_K) (compute_pgd,
+        objectives.py:166-174) in ``pv.patchesT_full``; with ``keep_prev`` also delta_{K-1} in ``pv.delta_prev``.  ``nb``: Nlvr2Buffers
+        holding the batch's labels; the loop's head passes run in them."""
+        eng = pl_module.engine
+        K = self.adv_steps_img
+        a0, a1 = self.attack_idx[0], self.attack_idx[1]
+        views = npass.views
+        if npass.pair:
+            attacked = [a0 or a1]
+        else:
+            attacked = [a0, a1]
+        npass.clean_operands(full_buffer=False)                             # img + delta_0, delta_0 = 0 (:266-271)
+        for i, pv in enumerate(views):
+            if not attacked[i]:                                             # never stepped: delta 0, the attacked view is the clean one
+                pv.delta.zero_()
+                pv.delta_prev.zero_()
+                eng.make_operand(pv, out=pv.patchesT_full)
+        for step in range(K):
+            last = step == K - 1
+            cls2 = npass.forward(L.MODE_DATA, wgrad=False)
+            eng.nlvr2_forward(nb, cls2)
+            eng.nlvr2_ce(nb, 1.0 / K, want_dz=True)                          # CE / adv_steps_img (:296)
+            dcls2 = eng.nlvr2_backward(nb, nb.dz, with_grads=False)
+            npass.backward(dcls2, L.MODE_DATA, with_grads=False, dpatches=attacked)
+            for i, pv in enumerate(views):
+                if not attacked[i]:
+                    continue
+                if npass.pair and not (a0 and a1):                          # the image that is not attacked: zero gradient rows -> step 0
+                    pv.gpatch.view(npass.B, 2, -1)[:, 1 if a0 else 0].zero_()
+                if last and keep_prev:
+                    if K > 1:
+                        pv.delta_prev.copy_(pv.delta)
+                    else:
+                        pv.delta_prev.zero_()
+                npass.ops[i] = pv.patchesT_full if last else pv.patchesT
+                eng.pgd_step(pv, self.adv_lr_img, self.adv_max_norm_img, first=step == 0, out=npass.ops[i], sum_prev=last)   # :302-331
+
+    def _image_of(self, eng, npass, pat_attr, shapes):
+        """(image_0 part, image_1 part) of a per-view patch buffer, in the batch's image layouts"""
+        if npass.pair:
+            pv = npass.views[0]
+            img = eng.patches_to_image(getattr(pv, pat_attr), pv)
+            return tuple(img[k::2, :, : shapes[k][2], : shapes[k][3]] for k in range(2))
+        return tuple(eng.patches_to_image(getattr(pv, pat_attr), pv) for pv in npass.views)
+
+    def delta_log(self, pl_module, npass, batch):
+        """(mean_c ||delta_0||_c + mean_c ||delta_1||_c) / sum(attack_idx) (objectives.py:179-184), from the patch-layout deltas."""
+        from .._lib import lib, check, P, I64
+        from ..runtime import stream_ptr
+        eng = pl_module.engine
+        n_att = sum(self.attack_idx)
+        shapes = [tuple(batch["image_0"][0].shape), tuple(batch["image_1"][0].shape)]
+        if npass.pair and shapes[0] != shapes[1]:                            # two padded extents: per-image means of the image tensors
+            d0, d1 = self._image_of(eng, npass, "delta", shapes)
+            return (torch.linalg.norm(d0, dim=1).mean() + torch.linalg.norm(d1, dim=1).mean()) / n_att
+        out = torch.zeros(len(npass.views), dtype=torch.float32, device=eng.device)
+        for i, pv in enumerate(npass.views):                                 # (pair form: one sum over both images of the same extent)
+            check(lib.rmcl_delta_channel_norm(P(pv.delta), P(out[i:i + 1]), I64(pv.delta.shape[0]), 3, pv.d.patch_k // 3, stream_ptr()),
+                  "delta_norm")
+        n_pix = [float(npass.B * sh[2] * sh[3]) for sh in shapes]           # every image of a key: B x H x W pixels
+        return ((out[0] / n_pix[0] if npass.pair else out[0] / n_pix[0] + out[1] / n_pix[1]) / n_att).reshape(())
+
+    def pgd_attack(self, pl_module, batch, k_modality=None):
+        """The reference's public form: returns (delta_0, delta_1) in image layout and leaves image_k = img_k + delta_{K-1} in the batch."""
+        from ..vilt.modules.objectives import Nlvr2Pass
+        eng = pl_module.engine
+        imgs = []
+        for key in ("image_0", "image_1"):
+            im = batch[key][0]
+            if hasattr(im, "tables"):
+                im = eng.resize_raw(im)
+            if hasattr(im, "float_image"):
+                im = im.to(eng.device).float_image()
+            imgs.append(im.to(eng.device, torch.float32))
+        b2 = dict(batch, image_0=[imgs[0]], image_1=[imgs[1]])
+        npass = Nlvr2Pass.bind(pl_module, b2, "nlvr2_att_0").twin("nlvr2_att")
+        nb = eng.nlvr2_bufs(npass.B, "pgd")
+        eng.nlvr2_labels(nb, batch["answers"])
+        self.attack_pairs(pl_module, npass, nb, keep_prev=True)
+        shapes = [tuple(i.shape) for i in imgs]
+        deltas = self._image_of(eng, npass, "delta", shapes)
+        prevs = self._image_of(eng, npass, "delta_prev", shapes)
+        batch["image_0"][0] = imgs[0] + prevs[0]
+        batch["image_1"][0] = imgs[1] + prevs[1]
+        return deltas[0].contiguous(), deltas[1].contiguous()

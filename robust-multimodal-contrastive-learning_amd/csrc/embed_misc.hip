@@ -175,6 +175,8 @@ int rmcl_rows_scatter_cast(const float* in, void* out, int dt, int R, int D, lon
 //   x[b*N + L]         = cls + pos[0] + vtype[1]
 //   x[b*N + L + 1 + p] = pe[b*P + p] + pos[1+p] + vtype[1]      (pe already holds conv bias)
 // ---------------------------------------------------------------------------------------------
+// PAIR (NLVR2 pair pass, rmcl_dims.img_type = -1): sample b adds row 1 + (b & 1), i.e. vtype1 + (b & 1) * D
+template <bool PAIR>
 __global__ __launch_bounds__(256) void image_assemble_fwd_kernel(const float* __restrict__ pe, const float* __restrict__ cls,
                                                                  const float* __restrict__ pos, const float* __restrict__ vtype1,
                                                                  float* __restrict__ x, int B, int P, int L, int N, int D,
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) void image_assemble_fwd_kernel(const float* __
                             : *reinterpret_cast<const float4*>(pe + ((long)b * P + tok - 1) * D + c);
   // pos_bstride = 0: the shared position table; (P+1)*D: per-sample rows (zero-padded batches: resized per image)
   const float4 p = *reinterpret_cast<const float4*>(pos + (long)b * pos_bstride + (long)tok * D + c);
-  const float4 t = *reinterpret_cast<const float4*>(vtype1 + c);
+  const float4 t = *reinterpret_cast<const float4*>(vtype1 + (PAIR ? (b & 1) * D : 0) + c);
   float4 o = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
   if (dthresh) {                                              // pos_drop (vision_transformer.py:667), before the token type
     const uint32_t di = (uint32_t)(((long)b * (P + 1) + tok) * D + c);
@@ -197,43 +199,55 @@ __global__ __launch_bounds__(256) void image_assemble_fwd_kernel(const float* __
   *reinterpret_cast<float4*>(x + ((long)b * N + L + tok) * D + c) = make_float4(o.x + t.x, o.y + t.y, o.z + t.z, o.w + t.w);
 }
 int rmcl_image_assemble_fwd(const float* pe, const float* cls, const float* pos, const float* vtype1, float* x, int B, int P,
-                            int L, int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, int pos_per_sample, hipStream_t s) {
+                            int L, int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, int pos_per_sample, int pair, hipStream_t s) {
   RMCL_REQUIRE(D % 4 == 0, "image_assemble: D%4");
-  RMCL_LAUNCH(image_assemble_fwd_kernel, dim3(cdiv((long)B * (P + 1) * (D / 4), 256)), dim3(256), 0, s, pe, cls, pos, vtype1, x, B, P, L, N, D,
-              dseed, dthresh, dinv, pos_per_sample ? (long)(P + 1) * D : 0L);
+  RMCL_REQUIRE(!pair || B % 2 == 0, "image_assemble: the pair form needs an even B");
+  const dim3 grid(cdiv((long)B * (P + 1) * (D / 4), 256));
+  const long pbs = pos_per_sample ? (long)(P + 1) * D : 0L;
+  if (pair) RMCL_LAUNCH(image_assemble_fwd_kernel<true>, grid, dim3(256), 0, s, pe, cls, pos, vtype1, x, B, P, L, N, D, dseed, dthresh, dinv, pbs);
+  else RMCL_LAUNCH(image_assemble_fwd_kernel<false>, grid, dim3(256), 0, s, pe, cls, pos, vtype1, x, B, P, L, N, D, dseed, dthresh, dinv, pbs);
   RMCL_CHECK_LAUNCH();
   return 0;
 }
 
 // backward: dpe[b*P+p] = dx[b*N+L+1+p] (as T);  optional param grads:
 //   dpos[tok] += sum_b dx[b, L+tok];  dcls += sum_b dx[b, L];  dvtype1 += sum over all image tokens
-template <typename T>
+// PAIR: the token-type gradient of even samples goes to dvtype1 (row 1), of odd samples to dvtype1 + D (row 2)
+template <typename T, bool PAIR>
 __global__ __launch_bounds__(256) void image_assemble_bwd_kernel(const float* __restrict__ dx, T* __restrict__ dpe,
                                                                  float* __restrict__ dpos, float* __restrict__ dcls,
                                                                  float* __restrict__ dvtype1, int B, int P, int L, int N, int D,
                                                                  uint32_t dseed, uint32_t dthresh, float dinv, float* __restrict__ dpos_tok) {
   const int tok = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
   if (c >= D) return;
-  float acc = 0.f, acc_raw = 0.f;
+  float acc = 0.f, acc_raw = 0.f, acc_raw2 = 0.f;
   for (int b = 0; b < B; ++b) {
     const float raw = dx[((long)b * N + L + tok) * D + c];
     const float v = dthresh ? raw * drop_scale(dseed, (uint32_t)(((long)b * (P + 1) + tok) * D + c), dthresh, dinv) : raw;
     acc += v;
-    acc_raw += raw;
+    if (PAIR && (b & 1)) acc_raw2 += raw;
+    else acc_raw += raw;
     if (tok > 0) dpe[((long)b * P + tok - 1) * D + c] = from_f32<T>(v);
     if (dpos_tok) dpos_tok[((long)b * (P + 1) + tok) * D + c] = v;     // per-sample position rows: scattered by pos_resize_bwd
   }
   if (dpos) {
     if (!dpos_tok) atomicAdd(dpos + (long)tok * D + c, acc);
     atomicAdd(dvtype1 + c, acc_raw);                         // the token type is added after pos_drop
+    if (PAIR) atomicAdd(dvtype1 + D + c, acc_raw2);
     if (tok == 0) atomicAdd(dcls + c, acc);
   }
 }
 int rmcl_image_assemble_bwd(const float* dx, void* dpe, int dt, float* dpos, float* dcls, float* dvtype1, int B, int P, int L,
-                            int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, float* dpos_tok, hipStream_t s) {
+                            int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, float* dpos_tok, int pair, hipStream_t s) {
   dim3 grid(P + 1, cdiv(D, 256));
-  if (dt == RMCL_F32) RMCL_LAUNCH(image_assemble_bwd_kernel<float>, grid, dim3(256), 0, s, dx, (float*)dpe, dpos, dcls, dvtype1, B, P, L, N, D, dseed, dthresh, dinv, dpos_tok);
-  else RMCL_LAUNCH(image_assemble_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, dx, (bf16_t*)dpe, dpos, dcls, dvtype1, B, P, L, N, D, dseed, dthresh, dinv, dpos_tok);
+  RMCL_REQUIRE(!pair || B % 2 == 0, "image_assemble_bwd: the pair form needs an even B");
+  if (pair) {
+    if (dt == RMCL_F32) RMCL_LAUNCH((image_assemble_bwd_kernel<float, true>), grid, dim3(256), 0, s, dx, (float*)dpe, dpos, dcls, dvtype1, B, P, L, N, D, dseed, dthresh, dinv, dpos_tok);
+    else RMCL_LAUNCH((image_assemble_bwd_kernel<bf16_t, true>), grid, dim3(256), 0, s, dx, (bf16_t*)dpe, dpos, dcls, dvtype1, B, P, L, N, D, dseed, dthresh, dinv, dpos_tok);
+  } else {
+    if (dt == RMCL_F32) RMCL_LAUNCH((image_assemble_bwd_kernel<float, false>), grid, dim3(256), 0, s, dx, (float*)dpe, dpos, dcls, dvtype1, B, P, L, N, D, dseed, dthresh, dinv, dpos_tok);
+    else RMCL_LAUNCH((image_assemble_bwd_kernel<bf16_t, false>), grid, dim3(256), 0, s, dx, (bf16_t*)dpe, dpos, dcls, dvtype1, B, P, L, N, D, dseed, dthresh, dinv, dpos_tok);
+  }
   RMCL_CHECK_LAUNCH();
   return 0;
 }

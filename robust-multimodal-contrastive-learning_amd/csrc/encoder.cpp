@@ -142,6 +142,10 @@ int check_dims(const rmcl_dims* d) {
   RMCL_REQUIRE(d->D % 64 == 0 && d->D <= 1024 && d->mlp % 64 == 0 && d->patch_k % 64 == 0, "D/mlp/patch_k must be multiples of 64 (D <= 1024)");
   RMCL_REQUIRE(d->dtype == RMCL_F32 || d->dtype == RMCL_BF16, "bad dtype");
   RMCL_REQUIRE(d->L + 1 + d->P <= 512, "sequence too long (N <= 512)");
+  RMCL_REQUIRE(d->n_types == 0 || d->n_types == 2 || d->n_types == 3, "n_types must be 0, 2 or 3");
+  RMCL_REQUIRE(d->img_type >= -1 && d->img_type <= 2, "img_type must be -1, 0, 1 or 2");
+  RMCL_REQUIRE((d->img_type != 2 && d->img_type != -1) || d->n_types == 3, "img_type 2 / -1 (NLVR2) needs n_types = 3");
+  RMCL_REQUIRE(d->img_type != -1 || d->B % 2 == 0, "img_type -1 (pair pass) needs an even B");
   return 0;
 }
 
@@ -317,7 +321,7 @@ void rmcl_param_layout(const rmcl_dims* d, rmcl_layout* o) {
   o->pos = take((int64_t)d->L * D);
   o->btype = take(2 * D);
   o->eln_w = take(D); o->eln_b = take(D);
-  o->vtype = take(2 * D);
+  o->vtype = take((d->n_types == 3 ? 3 : 2) * D);     // NLVR2: [3, D] (the pre-training layout is unchanged otherwise)
   o->cls = take(D);
   o->pos_img = take((int64_t)((d->Pp > 0 ? d->Pp : d->P) + 1) * D);
   o->patch_w = take(D * d->patch_k);
@@ -391,8 +395,10 @@ int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, co
     RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
                                  ragged->pos_tok, s));
   }
-  RMCL_TRY(rmcl_image_assemble_fwd(w.pe, c.V(y.cls), ragged ? ragged->pos_tok : c.V(y.pos_img), c.V(y.vtype) + D, x0, B, P, L, N, D,
-                                   rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, ragged ? 1 : 0, s));
+  // image token type (vilt_module.py:315-321): row 1, row 2 (img_type 2), or row 1 + (b & 1) per pair (img_type -1)
+  RMCL_TRY(rmcl_image_assemble_fwd(w.pe, c.V(y.cls), ragged ? ragged->pos_tok : c.V(y.pos_img), c.V(y.vtype) + (d->img_type == 2 ? 2 : 1) * D,
+                                   x0, B, P, L, N, D, rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, ragged ? 1 : 0,
+                                   d->img_type == -1 ? 1 : 0, s));
   RMCL_TRY(rmcl_co_mask((const long*)text_mask, patches, dt, co_mask, B, L, P, 3, d->patch_k / 3, s));
 
   // LayerNorm folded into the consuming GEMMs (gemm.h EPI_LNFOLD / EPI_ROWSTAT): passes that keep no LayerNorm output
@@ -803,8 +809,9 @@ int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, c
 
   // ---- embeddings ----
   RMCL_TRY(rmcl_image_assemble_bwd(w.dx, w.dpe, dt, full ? Gp(y.pos_img) : nullptr, full ? Gp(y.cls) : nullptr,
-                                   full ? Gp(y.vtype) + D : nullptr, B, P, L, N, D, rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv,
-                                   (ragged && full) ? ragged->dpos_tok : nullptr, s));
+                                   full ? Gp(y.vtype) + (d->img_type == 2 ? 2 : 1) * D : nullptr, B, P, L, N, D,
+                                   rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, (ragged && full) ? ragged->dpos_tok : nullptr,
+                                   d->img_type == -1 ? 1 : 0, s));
   if (ragged && full)                                          // position-table gradient through the per-sample resize
     RMCL_TRY(rmcl_pos_resize_bwd(ragged->dpos_tok, ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
                                  Gp(y.pos_img), s));

@@ -89,10 +89,11 @@ int rmcl_gather_rows(const float* in, float* out, int R, int D, int rows_per, lo
 int rmcl_scatter_rows(const float* in, float* out, int R, int D, int rows_per, long stride_outer, long off, int add, hipStream_t s);
 int rmcl_rows_gather_cast(const void* in, int dt, float* out, int R, int D, long stride, long off, hipStream_t s);
 int rmcl_rows_scatter_cast(const float* in, void* out, int dt, int R, int D, long stride, long off, hipStream_t s);
+// pair = 1 (NLVR2 pair pass): sample b adds the token-type row vtype1 + (b & 1) * D (rows 1 / 2) and, backward, its gradient lands there
 int rmcl_image_assemble_fwd(const float* pe, const float* cls, const float* pos, const float* vtype1, float* x, int B, int P,
-                            int L, int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, int pos_per_sample, hipStream_t s);
+                            int L, int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, int pos_per_sample, int pair, hipStream_t s);
 int rmcl_image_assemble_bwd(const float* dx, void* dpe, int dt, float* dpos, float* dcls, float* dvtype1, int B, int P, int L,
-                            int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, float* dpos_tok, hipStream_t s);
+                            int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, float* dpos_tok, int pair, hipStream_t s);
 int rmcl_weight_transpose(const unsigned short* src, unsigned short* dst, long layer0, long stride, int layers, const long* offs, const int* rows,
                           const int* cols, hipStream_t s);
 int rmcl_patch_select(const float* img, int B, int C, int Hh, int Ww, int ps, int* sel, int* counts, int* hw, hipStream_t s);

@@ -27,13 +27,21 @@ def stream_ptr() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def is_nlvr2(cfg: dict) -> bool:
+    """NLVR2 fine-tuning (loss_names nlvr2 / nlvr2_attacked): a 3-row token_type_embeddings and the nlvr2_classifier head."""
+    ln = cfg.get("loss_names", {})
+    return ln.get("nlvr2", 0) > 0 or ln.get("nlvr2_attacked", 0) > 0
+
+
 def make_dims(cfg: dict, B: int, dtype: int, exact: bool, P: int = None) -> L.Dims:
-    """P: image patches per sample in this pass (default: the full grid); the position table always has the full grid."""
+    """P: image patches per sample in this pass (default: the full grid); the position table always has the full grid.
+    n_types = 3 for an NLVR2 model (include/rmcl.h rmcl_dims); img_type starts at 0 (row 1) and is set per pass."""
     ps = cfg["patch_size"]
     g = cfg["image_size"] // ps
     return L.Dims(B=B, L=cfg["max_text_len"], P=g * g if P is None else P, D=cfg["hidden_size"], H=cfg["num_heads"],
                   layers=cfg["num_layers"], mlp=cfg["hidden_size"] * cfg["mlp_ratio"], patch_k=3 * ps * ps,
-                  proj=128, vocab=cfg["vocab_size"], dtype=dtype, exact=int(exact), Pp=g * g)
+                  proj=128, vocab=cfg["vocab_size"], dtype=dtype, exact=int(exact), Pp=g * g, n_types=3 if is_nlvr2(cfg) else 0,
+                  img_type=0)
 
 
 def param_specs(cfg: dict, lay: L.Layout) -> List[Tuple[str, int, Tuple[int, ...]]]:
@@ -48,7 +56,7 @@ def param_specs(cfg: dict, lay: L.Layout) -> List[Tuple[str, int, Tuple[int, ...
         ("text_embeddings.token_type_embeddings.weight", lay.btype, (2, D)),
         ("text_embeddings.LayerNorm.weight", lay.eln_w, (D,)),
         ("text_embeddings.LayerNorm.bias", lay.eln_b, (D,)),
-        ("token_type_embeddings.weight", lay.vtype, (2, D)),
+        ("token_type_embeddings.weight", lay.vtype, (3 if is_nlvr2(cfg) else 2, D)),
         ("transformer.cls_token", lay.cls, (1, 1, D)),
         ("transformer.pos_embed", lay.pos_img, (1, g * g + 1, D)),
         ("transformer.patch_embed.proj.weight", lay.patch_w, (D, 3, ps, ps)),
@@ -153,6 +161,41 @@ class VqaBuffers:
         self.tab = None                                         # device [2, B, A] int32: labels, then the scores' bits
         self.labels = self.scores = None
         self._host = None
+
+
+def nlvr2_layout(cfg: dict, base: int):
+    """nlvr2_classifier (vilt_module.py:193-200: Linear(2D, 2D) - LayerNorm(2D) - GELU - Linear(2D, 2)) appended to the parameter arena
+    at element offset `base`: the VQA head struct with D = H = 2 hidden, N = 2 and a logits pitch of 64 (include/rmcl.h).  Returns
+    (rmcl_vqa_head struct, specs, elements used).  As for vqa_layout, the last weight keeps ldl rows (rows 2..63 stay zero)."""
+    D2 = 2 * cfg["hidden_size"]
+    N, ldl = 2, 64
+    n = "nlvr2_classifier."
+    shapes = [("w0", n + "0.weight", (D2, D2), D2 * D2), ("b0", n + "0.bias", (D2,), D2), ("g1", n + "1.weight", (D2,), D2),
+              ("b1", n + "1.bias", (D2,), D2), ("w3", n + "3.weight", (N, D2), ldl * D2), ("b3", n + "3.bias", (N,), N)]
+    off, offs, specs = base, {}, []
+    for key, name, shape, cnt in shapes:
+        offs[key] = off
+        specs.append((name, off, shape))
+        off += (cnt + 63) // 64 * 64
+    return L.VqaHead(D=D2, H=D2, N=N, ldl=ldl, **offs), specs, off - base
+
+
+class Nlvr2Buffers:
+    """Per-pass buffers of the NLVR2 head (B = pairs): its stash, the pitched logits and dz, the CE row outputs and the labels."""
+
+    def __init__(self, eng: "Engine", B: int):
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=eng.device)
+        h = eng.nlvr2
+        self.B = B
+        self.stash = f32(int(lib.rmcl_vqa_stash_floats(C.byref(h), B)))
+        self.logits_p = f32(B, h.ldl)
+        self.logits = self.logits_p[:, : h.N]                  # the public [B, 2] view
+        self.dz = f32(B, h.ldl)
+        self.dcls = f32(B, h.D)                                # [B, 2 hidden] = the pair pass's [2B, hidden] cls gradient
+        self.rows = f32(B)
+        self.argmax = torch.empty(B, dtype=torch.int32, device=eng.device)
+        self.stats = f32(3)
+        self.labels = torch.empty(B, dtype=torch.int32, device=eng.device)
 
 
 class PassBuffers:
@@ -287,6 +330,13 @@ class Engine:
             self.vqa, self.vqa_specs, n_vqa = vqa_layout(cfg, int(lay.total) + extra)
             extra += n_vqa
             self._vqa_bufs = {}
+        # optional NLVR2 classifier (loss_names["nlvr2"] / ["nlvr2_attacked"] > 0): behind the other heads; the 3-row token-type table
+        # of these models is part of the C layout (rmcl_dims.n_types = 3, make_dims)
+        self.nlvr2, self.nlvr2_specs = None, []
+        if is_nlvr2(cfg):
+            self.nlvr2, self.nlvr2_specs, n_nl = nlvr2_layout(cfg, int(lay.total) + extra)
+            extra += n_nl
+            self._nlvr2_bufs = {}
         self.total = int(lay.total) + extra
         self.q32 = z(self.total)
         self.k32 = z(lay.ema_end)
@@ -305,7 +355,7 @@ class Engine:
         # transposed bf16 shadows of the layer weights for the data-gradient GEMMs (include/rmcl.h rmcl_weight_transpose_bf16)
         self.q_lpT = z(lay.total, torch.bfloat16) if (self.dtype == L.BF16 and os.environ.get("RMCL_NO_WT", "0") != "1") else None
         self.lpT_stale = True
-        self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs
+        self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs + self.nlvr2_specs
         self._bufs: Dict[tuple, PassBuffers] = {}
         self.lp_stale = True
         self.drop_p = float(cfg.get("drop_rate", 0.0))
@@ -343,6 +393,7 @@ class Engine:
         geom = pb.geom if (pb.geom is None or owner is None) else pb.geom.take(owner)
         pv = self.bufs(B, tag, dtype, None if pb.geom is None else pb.geom.n)
         self._set_geometry(pv, geom)
+        pv.d.img_type = pb.d.img_type                       # (the same images: the same token-type rows)
         return pv
 
     def _set_geometry(self, pb: PassBuffers, geom):
@@ -378,10 +429,13 @@ class Engine:
             return None
         if mode != "1" and pb.B < 32:
             return None
+        if pb.d.img_type == -1 and (pb.B // n) % 2:                      # an NLVR2 pair pass is never split inside a pair
+            return None
         ls = getattr(pb, "_lanes", None)
         if ls is None or len(ls) != n:
             ls = pb._lanes = [PassBuffers(self, pb.B // n, pb.dtype, None, lane_of=pb, lane=i) for i in range(n)]
         for i, ln in enumerate(ls):                                          # the text tensors are new every step
+            ln.d.img_type = pb.d.img_type
             ln.text_ids = pb.text_ids[i * ln.B:(i + 1) * ln.B]
             ln.text_mask = pb.text_mask[i * ln.B:(i + 1) * ln.B]
             ln.k = pb.k[i * ln.B:(i + 1) * ln.B]                             # (pb.k may have been re-pointed: compute_moco_contrastive)
@@ -503,6 +557,7 @@ class Engine:
         geom = self.patch_geometry(img, select)
         pb = self.bufs(B, tag, None, None if geom is None else geom.n)
         self._set_geometry(pb, geom)
+        pb.d.img_type = 0                                                  # token-type row 1; callers that need another row set it after
         pb.text_ids = text_ids.to(self.device, torch.int64).contiguous()
         pb.text_mask = text_mask.to(self.device, torch.int64).contiguous()
         if geom is None:
@@ -510,6 +565,57 @@ class Engine:
         else:
             check(lib.rmcl_im2patch_sel(P(img), P(pb.patches32), P(geom.sel), P(geom.counts), geom.sel.shape[1], B, geom.n, 3, Hh, Ww,
                                         ps, 0, stream_ptr()), "im2patch_sel")
+        return pb
+
+    @staticmethod
+    def _pad_to(img: torch.Tensor, H: int, W: int) -> torch.Tensor:
+        """zero-pad a collated batch bottom / right to (H, W), like BaseDataset.collate pads every image of a batch (base_dataset.py:192-206)"""
+        if img.shape[2] == H and img.shape[3] == W:
+            return img
+        return torch.nn.functional.pad(img, (0, W - img.shape[3], 0, H - img.shape[2]))
+
+    def _full_geometry(self, B: int, gh: int, gw: int) -> RaggedGeometry:
+        """selection of a batch whose every patch is valid (the ragged form of a full-size image, for a pair with one ragged key)"""
+        sel = torch.arange(gh * gw, dtype=torch.int32, device=self.device).repeat(B, 1).contiguous()
+        counts = torch.full((B,), gh * gw, dtype=torch.int32, device=self.device)
+        hw = torch.tensor([gh, gw], dtype=torch.int32, device=self.device).repeat(B, 1).contiguous()
+        return RaggedGeometry(sel, counts, hw, gh * gw, gh, gw, (B, 3, gh * self.cfg["patch_size"], gw * self.cfg["patch_size"]))
+
+    def bind_pair(self, text_ids: torch.Tensor, text_mask: torch.Tensor, image0, image1, tag: str = "nlvr2") -> PassBuffers:
+        """The NLVR2 pair pass (DESIGN.md "NLVR2 fine-tuning"): ONE batch of 2B sequences, sample 2b = (text b, image_0[b]) with token
+        type 1 and sample 2b + 1 = (text b, image_1[b]) with token type 2 (rmcl_dims.img_type = -1).  The pooled cls [2B, D] of that pass
+        is then, as a view, the [B, 2D] concatenation nlvr2_classifier reads (objectives.py:1006-1010).  The patch geometry is drawn per
+        image key in the reference's order (all of image_0, then all of image_1: its two infer calls) and then interleaved."""
+        img0 = image0.to(self.device, torch.float32)
+        img1 = image1.to(self.device, torch.float32)
+        if img0.shape[0] != img1.shape[0]:
+            raise ValueError(f"image_0 / image_1 must hold the same number of pairs ({img0.shape[0]} vs {img1.shape[0]})")
+        B = img0.shape[0]
+        Hm, Wm = max(img0.shape[2], img1.shape[2]), max(img0.shape[3], img1.shape[3])
+        img0, img1 = self._pad_to(img0, Hm, Wm).contiguous(), self._pad_to(img1, Hm, Wm).contiguous()
+        g0 = self.patch_geometry(img0)
+        g1 = self.patch_geometry(img1)
+        ps = self.cfg["patch_size"]
+        geom = None
+        if g0 is not None or g1 is not None:
+            gh, gw = Hm // ps, Wm // ps
+            g0 = g0 if g0 is not None else self._full_geometry(B, gh, gw)
+            g1 = g1 if g1 is not None else self._full_geometry(B, gh, gw)
+            il = lambda a, b: torch.stack([a, b], dim=1).reshape((2 * B,) + tuple(a.shape[1:])).contiguous()
+            geom = RaggedGeometry(il(g0.sel, g1.sel), il(g0.counts, g1.counts), il(g0.hw, g1.hw), max(g0.n, g1.n), gh, gw,
+                                  (2 * B, 3, Hm, Wm))
+        img = torch.stack([img0, img1], dim=1).reshape(2 * B, 3, Hm, Wm)
+        pb = self.bufs(2 * B, tag, None, None if geom is None else geom.n)
+        self._set_geometry(pb, geom)
+        pb.d.img_type = -1
+        pb.text_ids = text_ids.to(self.device, torch.int64).repeat_interleave(2, dim=0).contiguous()
+        pb.text_mask = text_mask.to(self.device, torch.int64).repeat_interleave(2, dim=0).contiguous()
+        if geom is None:
+            check(lib.rmcl_im2patch_f32(P(img), P(pb.patches32), 2 * B, 3, Hm, Wm, ps, 0, stream_ptr()), "im2patch")
+        else:
+            check(lib.rmcl_im2patch_sel(P(img), P(pb.patches32), P(geom.sel), P(geom.counts), geom.sel.shape[1], 2 * B, geom.n, 3, Hm, Wm,
+                                        ps, 0, stream_ptr()), "im2patch_sel")
+        pb.keep_alive = (img,)
         return pb
 
     def _h2d(self, t: torch.Tensor) -> torch.Tensor:
@@ -580,6 +686,7 @@ class Engine:
             geom = RaggedGeometry(sel.to(self.device), counts.to(self.device), hw.to(self.device), n, gh, gw, (B, 3, Hh, Ww))
         pb = self.bufs(B, tag, None, None if geom is None else geom.n)
         self._set_geometry(pb, geom)
+        pb.d.img_type = 0                                                  # token-type row 1; callers that need another row set it after
         pb.text_ids = text_ids.to(self.device, torch.int64).contiguous()
         pb.text_mask = text_mask.to(self.device, torch.int64).contiguous()
         sizes = self._h2d(u8.sizes)
@@ -811,6 +918,45 @@ class Engine:
         check(lib.rmcl_vqa_targets_dense(P(vb.labels), P(vb.scores), vb.A, vb.B, self.vqa.N, P(out), self.vqa.N, stream_ptr()),
               "vqa_targets_dense")
         return out
+
+    # ---- NLVR2 head (the VQA head kernels on the nlvr2_classifier struct) + hard-label CE (include/rmcl.h rmcl_nlvr2_ce) ----------
+    def nlvr2_bufs(self, B: int, tag: str) -> Nlvr2Buffers:
+        if (B, tag) not in self._nlvr2_bufs:
+            self._nlvr2_bufs[(B, tag)] = Nlvr2Buffers(self, B)
+        return self._nlvr2_bufs[(B, tag)]
+
+    def nlvr2_labels(self, nb: Nlvr2Buffers, answers):
+        """batch["answers"] (bools, or 0 / 1; objectives.py:1012-1013 casts them to long) -> nb.labels.  Anything else is a ValueError
+        (the reference's cross_entropy raises on a target outside [0, 2))."""
+        vals = answers.tolist() if torch.is_tensor(answers) else list(answers)
+        if len(vals) != nb.B:
+            raise ValueError(f"answers must have one entry per pair ({len(vals)} for {nb.B} pairs)")
+        ints = [int(v) for v in vals]
+        if any(v not in (0, 1) for v in ints):
+            raise ValueError(f"NLVR2 answers must be True / False (got {vals})")
+        nb.labels.copy_(torch.tensor(ints, dtype=torch.int32))
+        return nb.labels
+
+    def nlvr2_forward(self, nb: Nlvr2Buffers, cls2: torch.Tensor):
+        """logits [B, 2] = nlvr2_classifier(cls2 [B, 2 hidden])."""
+        check(lib.rmcl_vqa_head_forward(C.byref(self.nlvr2), P(self.q32), P(cls2), nb.B, P(nb.stash), P(nb.logits_p), stream_ptr()),
+              "nlvr2_head_forward")
+        return nb.logits
+
+    def nlvr2_ce(self, nb: Nlvr2Buffers, grad_scale: float, want_dz: bool, scale_dev: torch.Tensor = None, ref: "Nlvr2Buffers" = None,
+                 stats: torch.Tensor = None):
+        """stats = (mean CE, correct rows, rows whose argmax differs from ref's logits); rows / argmax per pair; dz (want_dz) =
+        grad_scale [* scale_dev] d CE / d logits."""
+        stats = nb.stats if stats is None else stats
+        check(lib.rmcl_nlvr2_ce(P(nb.logits_p), self.nlvr2.ldl, P(nb.labels), nb.B, self.nlvr2.N, F(grad_scale), P(scale_dev),
+                                P(nb.dz if want_dz else None), P(nb.rows), P(nb.argmax), P(ref.logits_p if ref is not None else None),
+                                self.nlvr2.ldl, P(stats), stream_ptr()), "nlvr2_ce")
+        return stats
+
+    def nlvr2_backward(self, nb: Nlvr2Buffers, dz: torch.Tensor, with_grads: bool):
+        check(lib.rmcl_vqa_head_backward(C.byref(self.nlvr2), P(self.q32), P(nb.stash), P(dz), nb.B, P(self.g32 if with_grads else None),
+                                         P(nb.dcls), stream_ptr()), "nlvr2_head_backward")
+        return nb.dcls
 
     def pgd_step(self, pb: PassBuffers, lr: float, eps: float, first: bool = False, out: torch.Tensor = None, sum_prev: bool = False):
         """delta <- clamp(delta + lr g / max|g|, +-eps) (pgd_attack_vilt.py:162-173).  ``out``: also written in the same pass,

@@ -89,3 +89,38 @@ def task_finetune_vqa_randaug_attacked(**over):
     )
     cfg.update(over)
     return cfg
+
+
+def task_finetune_nlvr2(**over):
+    """reference config.py:234-243: NLVR2 fine-tuning (3-row token_type_embeddings, nlvr2_classifier + cross-entropy).  max_steps None as
+    in the reference: set_schedule then needs it from the caller.  nlvr2_pair_pass (not a reference key, default True): the two images
+    of a pair run as ONE encoder pass of 2B sequences; False runs the reference's two infer calls (DESIGN.md "NLVR2 fine-tuning")."""
+    cfg = default_config(
+        exp_name="finetune_nlvr2", datasets=["nlvr2"], loss_names=_loss_names({"nlvr2": 1}), batch_size=128, max_epoch=10,
+        max_steps=None, warmup_steps=0.1, draw_false_image=0, learning_rate=1e-4, nlvr2_pair_pass=True,
+    )
+    cfg.update(over)
+    return cfg
+
+
+def task_finetune_nlvr2_randaug(**over):
+    """reference config.py:245-256: as task_finetune_nlvr2 with the RandAugment train transform (the transform itself is the caller's)."""
+    cfg = task_finetune_nlvr2(exp_name="finetune_nlvr2_randaug", train_transform_keys=["pixelbert_randaug"])
+    cfg.update(over)
+    return cfg
+
+
+def task_finetune_nlvr2_randaug_attacked(**over):
+    """reference config.py:258-288: adversarial NLVR2 fine-tuning.  Both views default to False as in the reference, which then fails
+    (no nlvr2_attacked_loss); here the module refuses that at construction (ValueError): pass image_view=True (PGD on the images
+    selected by attack_idx)."""
+    cfg = default_config(
+        exp_name="finetune_nlvr2_randaug_attacked", datasets=["nlvr2"], train_transform_keys=["pixelbert_randaug"],
+        loss_names=_loss_names({"nlvr2_attacked": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,
+        draw_false_image=0, learning_rate=1e-4, test_only=False, text_view=False, image_view=False,
+        adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005, attack_idx=[True, True],
+        n_candidates=5, max_loops=10, sim_thred=0.5, cos_sim=True, synonym="cos_sim",
+        embedding_path="../attack/counter-fitted-vectors.txt", sim_path="../attack/cos_sim_counter_fitting.npy", nlvr2_pair_pass=True,
+    )
+    cfg.update(over)
+    return cfg

@@ -544,3 +544,151 @@ def compute_vqa_attack(pl_module, batch):
     n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
     pl_module.log(f"vqa_attacked_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
     return _vqa_head_loss(pl_module, pb, pb.patchesT_full, batch, "vqa_attacked", "vqa_att", tables=vp)
+
+
+# ---- NLVR2 (objectives.py:898-1060) ------------------------------------------------------------------------------------------------
+class Nlvr2Pass:
+    """The encoder passes of one NLVR2 batch.  Pair form (config["nlvr2_pair_pass"], default on): ONE pass of 2B sequences, sample 2b =
+    (text b, image_0[b], token type 1), 2b + 1 = (text b, image_1[b], token type 2) - its pooled cls [2B, D] IS the [B, 2D] input of
+    nlvr2_classifier and the head's [B, 2D] gradient IS the pass's cls gradient.  Two-pass form: the reference's two infer calls
+    (image_token_type_idx 1 and 2), one pass of B sequences each, the cls halves concatenated / split by copies."""
+
+    def __init__(self, eng, views, B, pair):
+        self.eng, self.views, self.B, self.pair = eng, views, B, pair
+        self.ops = [None] * len(views)
+
+    @classmethod
+    def bind(cls, pl_module, batch, tag):
+        eng = pl_module.engine
+        img0, img1 = batch["image_0"][0], batch["image_1"][0]
+        B = int(img0.shape[0])
+        if pl_module.hparams.config.get("nlvr2_pair_pass", True):
+            return cls(eng, [eng.bind_pair(batch["text_ids"], batch["text_masks"], img0, img1, tag=tag)], B, True)
+        views = []
+        for t, img in ((1, img0), (2, img1)):                  # geometry drawn in the reference's order: image_0, then image_1
+            pv = eng.bind_batch(batch["text_ids"], batch["text_masks"], img, tag=f"{tag}_{t}")
+            pv.d.img_type = t
+            views.append(pv)
+        return cls(eng, views, B, False)
+
+    def twin(self, tag):
+        """the same pairs in buffers of their own (the attacked pass): shares the text, the clean patch rows and the geometry"""
+        vs = []
+        for i, pv in enumerate(self.views):
+            pt = self.eng.twin(pv, f"{tag}_{i}")
+            pt.text_ids, pt.text_mask, pt.patches32 = pv.text_ids, pv.text_mask, pv.patches32
+            vs.append(pt)
+        return Nlvr2Pass(self.eng, vs, self.B, self.pair)
+
+    def clean_operands(self, full_buffer=True):
+        self.ops = [self.eng.make_operand(pv, out=pv.patchesT_full if full_buffer else None) for pv in self.views]
+        return self.ops
+
+    def forward(self, mode, wgrad):
+        eng = self.eng
+        for pv, op in zip(self.views, self.ops):
+            eng.encoder_forward(pv, key=False, mode=mode, patchesT=op, cls_tail=True)
+            eng.heads_forward(pv, key=False, want_q=False, wgrad=wgrad)
+        if self.pair:
+            return self.views[0].cls.view(self.B, -1)                         # [2B, D] -> [B, 2D]: no copy
+        return torch.cat([pv.cls for pv in self.views], dim=1)
+
+    def backward(self, dcls2, mode, with_grads, dpatches=False):
+        eng = self.eng
+        D = self.views[0].d.D
+        for i, (pv, op) in enumerate(zip(self.views, self.ops)):
+            dc = dcls2.view(2 * self.B, D) if self.pair else dcls2[:, i * D:(i + 1) * D].contiguous()
+            eng.heads_backward(pv, None, dc, with_grads=with_grads)
+            want = dpatches if isinstance(dpatches, bool) else dpatches[i]
+            eng.encoder_backward(pv, mode, op, pv.dcls, cls_only=True, dpatches=pv.gpatch if want else None)
+
+
+def _nlvr2_loss(pl_module, npass, batch, nb_tag, labels_from=None, ref=None):
+    """Forward of the pass on its operands, nlvr2_classifier and the CE: (value with a deferred backward, logits, Nlvr2Buffers)."""
+    eng = pl_module.engine
+    need_grad = torch.is_grad_enabled() and pl_module.training
+    mode = L.MODE_FULL if need_grad else L.MODE_INFER
+    cls2 = npass.forward(mode, wgrad=need_grad)
+    nb = eng.nlvr2_bufs(npass.B, nb_tag)
+    if labels_from is None:
+        eng.nlvr2_labels(nb, batch["answers"])
+    else:
+        nb.labels.copy_(labels_from.labels)
+    logits = eng.nlvr2_forward(nb, cls2)
+    stats = eng.nlvr2_ce(nb, 1.0, want_dz=False, ref=ref, stats=torch.empty(3, dtype=torch.float32, device=eng.device))
+    value = _scalar(stats[0])
+    if need_grad:
+        def backward(grad_out, npass=npass, nb=nb):
+            g = grad_out.to(torch.float32).reshape(1).contiguous()
+            eng.nlvr2_ce(nb, 1.0, want_dz=True, scale_dev=g, stats=torch.empty(3, dtype=torch.float32, device=eng.device))
+            dcls2 = eng.nlvr2_backward(nb, nb.dz, with_grads=True)
+            npass.backward(dcls2, L.MODE_FULL, with_grads=True)
+            pl_module.after_backward(overlap=True)
+
+        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+    return value, logits, nb, stats
+
+
+def _split_rows(batch):
+    """dev / test rows of a validation batch (objectives.py:1036-1037, selected by table_name)"""
+    names = batch.get("table_name", [])
+    return {"dev": [i for i, n in enumerate(names) if "dev" in n], "test": [i for i, n in enumerate(names) if "test" in n]}
+
+
+def _log_split(pl_module, batch, task, nb, ref_nb=None):
+    dev = nb.rows.device
+    for split, idx in _split_rows(batch).items():
+        if not idx:
+            continue
+        ix = torch.tensor(idx, dtype=torch.int64, device=dev)
+        pl_module.log(f"{task}/{split}/loss", nb.rows.index_select(0, ix).mean())
+        pl_module.log(f"{task}/{split}/accuracy", (nb.argmax.index_select(0, ix) == nb.labels.index_select(0, ix)).float().mean())
+        if ref_nb is not None:                                               # change_rate (my_metrics.py:30-45): attacked vs clean argmax
+            pl_module.log(f"{task}/{split}/change_rate_cross",
+                          (nb.argmax.index_select(0, ix) != ref_nb.argmax.index_select(0, ix)).float().mean())
+
+
+def compute_nlvr2(pl_module, batch):
+    """objectives.py:1002-1060: CE(nlvr2_classifier(cat(cls(image_0, type 1), cls(image_1, type 2))), answers)."""
+    eng = pl_module.engine
+    npass = Nlvr2Pass.bind(pl_module, batch, "nlvr2")
+    npass.clean_operands()
+    value, logits, nb, stats = _nlvr2_loss(pl_module, npass, batch, "nlvr2")
+    ret = {"nlvr2_loss": value, "nlvr2_logits": logits, "nlvr2_labels": nb.labels.to(torch.int64)}
+    if pl_module.training:
+        pl_module.log("nlvr2/train/loss", value.detach())
+        pl_module.log("nlvr2/train/accuracy", _scalar(stats[1]) / float(npass.B))
+    else:
+        _log_split(pl_module, batch, "nlvr2", nb)
+    return ret
+
+
+def compute_nlvr2_attack(pl_module, batch):
+    """objectives.py:898-1000 (image view): the clean pair (nlvr2_original_*), PGDAttack_nlvr2 on the CE (compute_pgd's
+    img + delta_{K-1} + delta_K per image), the attacked pair (nlvr2_attacked_*).  Both losses carry a backward (training_step sums every
+    key with "loss").  The reference's train branch reads the never-set ret["nlvr2_attacked_labels"] (defect (a)): the
+    labels are ret["nlvr2_labels"] here.  The batch itself is not modified (the reference attacks a deepcopy)."""
+    eng = pl_module.engine
+    if pl_module.text_view:
+        raise NotImplementedError("nlvr2_attacked with text_view (GreedyAttack_nlvr2) is outside the RMCL hot path")
+    phase = "train" if pl_module.training else "val"
+    npass = Nlvr2Pass.bind(pl_module, batch, "nlvr2_clean")
+    npass.clean_operands()
+    v_clean, lg_clean, nb_c, _ = _nlvr2_loss(pl_module, npass, batch, "clean")
+    ret = {"nlvr2_original_logits": lg_clean, "nlvr2_original_loss": v_clean, "nlvr2_labels": nb_c.labels.to(torch.int64)}
+    apass = npass.twin("nlvr2_att")
+    npg = eng.nlvr2_bufs(npass.B, "pgd")
+    npg.labels.copy_(nb_c.labels)
+    pl_module.pgd_attacker.attack_pairs(pl_module, apass, npg)                # compute_pgd (:914)
+    pl_module.log(f"nlvr2_attacked_attack/{phase}/delta", pl_module.pgd_attacker.delta_log(pl_module, apass, batch))
+    apass.ops = [pv.patchesT_full for pv in apass.views]                      # img + delta_{K-1} + delta_K, left by the last step
+    v_att, lg_att, nb_a, st_a = _nlvr2_loss(pl_module, apass, batch, "att", labels_from=nb_c, ref=nb_c)
+    ret["nlvr2_attacked_logits"] = lg_att
+    ret["nlvr2_attacked_loss"] = v_att
+    if phase == "train":
+        pl_module.log("nlvr2_attacked/train/loss", v_att.detach())
+        pl_module.log("nlvr2_attacked/train/accuracy", _scalar(st_a[1]) / float(npass.B))
+    else:
+        _log_split(pl_module, batch, "nlvr2_original", nb_c)
+        _log_split(pl_module, batch, "nlvr2_attacked", nb_a, ref_nb=nb_c)
+    return ret

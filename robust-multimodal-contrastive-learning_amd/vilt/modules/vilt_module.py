@@ -16,7 +16,7 @@ import torch.nn as nn
 from ... import _lib as L
 from ..._lib import lib, check
 from ...runtime import Engine, EMA_GROUPS
-from ...attack.pgd_attack_vilt import PGDAttack_moco, PGDAttack_bartlowtwins, PGDAttack_vqa
+from ...attack.pgd_attack_vilt import PGDAttack_moco, PGDAttack_bartlowtwins, PGDAttack_vqa, PGDAttack_nlvr2
 from ...attack.greedy_attack_vilt import GreedyAttack_moco, GreedyAttack_barlowtwins
 from . import objectives, vilt_utils, dist_utils
 
@@ -153,6 +153,19 @@ class ViLTransformerSS(nn.Module):
             if self.text_view:
                 raise NotImplementedError("vqa_attacked with text_view=True (GreedyAttack_vqa) is outside the RMCL hot path")
             self.pgd_attacker = PGDAttack_vqa(config)
+        if ln.get("nlvr2_attacked", 0) > 0:                                # vilt_module.py:211-231
+            self.image_view = config.get("image_view", False)
+            self.text_view = config.get("text_view", False)
+            if not (self.image_view or self.text_view):
+                # the reference returns no nlvr2_attacked_loss then and its logging raises a KeyError (defect (b))
+                raise ValueError("loss_names['nlvr2_attacked'] > 0 needs image_view=True (text_view / GreedyAttack_nlvr2 is not built)")
+            if self.text_view:
+                raise NotImplementedError("nlvr2_attacked with text_view=True (GreedyAttack_nlvr2) is outside the RMCL hot path")
+            self.attack_idx = [bool(a) for a in config.get("attack_idx", [False, False])]   # (reference default: config.py:92)
+            if len(self.attack_idx) != 2 or not any(self.attack_idx):
+                # compute_pgd divides the delta log by sum(attack_idx) (objectives.py:183): [False, False] is a division by zero (defect (c))
+                raise ValueError(f"nlvr2_attacked with image_view needs attack_idx with at least one True of two (got {config.get('attack_idx')})")
+            self.pgd_attacker = PGDAttack_nlvr2(config)
         self.id2answer = None                      # answer strings of the label ids (test_step); the reference reads them from its datamodule
         self.grad_anchor = torch.zeros((), device=eng.device, requires_grad=True)
         self.sync_grads = True                     # False on the early micro-steps of gradient accumulation (DDP no_sync)
@@ -175,6 +188,12 @@ class ViLTransformerSS(nn.Module):
                     state_dict["itm_score.fc.bias"] = c2["itm_score.fc.bias"]
                     break
         mine = self.state_dict()
+        nl3 = self.engine.nlvr2 is not None and not self.hparams.config.get("test_only", False)
+        if nl3:
+            # NLVR2 (vilt_module.py:134-160 then :193-231): the training-time load fills the PRE-resize 2-row table; the resize then keeps
+            # rows 0 / 1 and copies row 1 into row 2.  A 3-row table in that position is a size mismatch, as in the reference
+            mine = dict(mine)
+            mine["token_type_embeddings.weight"] = mine["token_type_embeddings.weight"][:2]
         # a tensor of another shape (position table at another resolution, text positions at another max_text_len) is an ERROR like
         # in the reference, whose load_state_dict(strict=False) raises on size mismatches (vilt_module.py:159-160) - not a silent skip
         wrong = [(k, tuple(v.shape), tuple(mine[k].shape)) for k, v in state_dict.items() if k in mine and tuple(mine[k].shape) != tuple(v.shape)]
@@ -182,9 +201,17 @@ class ViLTransformerSS(nn.Module):
             raise RuntimeError("Error(s) in loading state_dict: " + "; ".join(f"size mismatch for {k}: checkpoint {a}, model {b}" for k, a, b in wrong))
         # downstream heads exist only AFTER the training-time load in the reference (vilt_module.py:134-160 loads, :164 builds the VQA
         # head): a checkpoint's vqa_classifier.* keep their init unless test_only (:254-268 loads after the heads were built)
-        late = () if self.hparams.config.get("test_only", False) else ("vqa_classifier.",)
+        late = () if self.hparams.config.get("test_only", False) else ("vqa_classifier.", "nlvr2_classifier.")
         take = {k: v for k, v in state_dict.items() if k in mine and not k.startswith(late)}
+        tt = take.pop("token_type_embeddings.weight", None) if nl3 else None
         res = self.load_state_dict(take, strict=False)
+        if nl3:
+            with torch.no_grad():
+                w = dict(self.named_parameters())["token_type_embeddings.weight"]
+                if tt is not None:
+                    w[:2].copy_(tt)
+                w[2].copy_(w[1])                                        # rows [0, 1, 1] (vilt_module.py:202-205)
+                self.engine.lp_stale = True
         unexpected = sorted(k for k in state_dict if k not in take)
         self.load_report = {"missing": sorted(res.missing_keys), "unexpected": unexpected}
         if res.missing_keys or unexpected:
@@ -209,10 +236,10 @@ class ViLTransformerSS(nn.Module):
                 continue
             leaf = name.split(".")[-1]
             is_ln = any(t in name for t in ("LayerNorm", "norm1", "norm2", "transformer.norm", "projector.1"))
-            if name.startswith("vqa_classifier."):
-                # objectives.init_weights (:1505-1516) applied to the head (vilt_module.py:172): Linear N(0, 0.02) / bias 0, LayerNorm 1 / 0
-                # (the substring rule below would miss the LayerNorm gain "vqa_classifier.1.weight")
-                if name.startswith("vqa_classifier.1."):
+            if name.startswith(("vqa_classifier.", "nlvr2_classifier.")):
+                # objectives.init_weights (:1505-1516) applied to the head (vilt_module.py:172, :200): Linear N(0, 0.02) / bias 0, LayerNorm
+                # 1 / 0 (the substring rule below would miss the LayerNorm gain "vqa_classifier.1.weight")
+                if name.startswith(("vqa_classifier.1.", "nlvr2_classifier.1.")):
                     p.fill_(1.0 if leaf == "weight" else 0.0)
                 elif leaf == "bias":
                     p.zero_()
@@ -241,6 +268,8 @@ class ViLTransformerSS(nn.Module):
                 nn.init.trunc_normal_(p, std=0.02)
             else:
                 p.normal_(mean=0.0, std=0.02)
+            if name == "token_type_embeddings.weight" and p.shape[0] == 3:
+                p[2].copy_(p[1])                  # NLVR2: Embedding(3, D) with rows [old0, old1, old1] (vilt_module.py:201-205)
         self.engine.lp_stale = True
 
     @torch.no_grad()
@@ -315,9 +344,13 @@ class ViLTransformerSS(nn.Module):
             raise NotImplementedError("MLM/MPP masking is outside the RMCL hot path")
         if image_embeds is not None or image_masks is not None:
             raise NotImplementedError("image_embeds shortcut is not on the RMCL hot path")
-        if image_token_type_idx != 1:
-            raise NotImplementedError("image_token_type_idx != 1 (NLVR2) is outside the RMCL hot path")
+        if image_token_type_idx not in (1, 2):
+            raise NotImplementedError(f"image_token_type_idx={image_token_type_idx}: only 1 and 2 (NLVR2) exist")
         eng = self.engine
+        if image_token_type_idx == 2 and eng.nlvr2 is None:
+            # the reference's 2-row Embedding raises an IndexError for row 2: only NLVR2 models have the third row
+            raise ValueError("image_token_type_idx=2 needs an NLVR2 model (loss_names nlvr2 / nlvr2_attacked: 3-row token_type_embeddings)")
+        imgkey = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"   # vilt_module.py:284-287
         eng.dropout_on = self.training and eng.drop_p > 0
         text_ids, text_masks = batch["text_ids"], batch["text_masks"]
         # the reference's infer is an ordinary differentiable forward (vilt_module.py:275-351): with autograd on, the query pass keeps
@@ -328,7 +361,8 @@ class ViLTransformerSS(nn.Module):
         # size must not overwrite the activations the first one's backward will read); the slot is returned by the backward, or
         # when autograd drops the graph
         slot = self._infer_slot_take() if need_grad else None
-        pb = eng.bind_batch(text_ids, text_masks, batch["image"][0], tag=f"infer{slot}" if need_grad else "moco")
+        pb = eng.bind_batch(text_ids, text_masks, batch[imgkey][0], tag=f"infer{slot}" if need_grad else "moco")
+        pb.d.img_type = image_token_type_idx
         op = eng.make_operand(pb)
         eng.encoder_forward(pb, key=key, mode=L.MODE_FULL if need_grad else L.MODE_INFER, patchesT=op)
         eng.heads_forward(pb, key=key, want_q=False)
@@ -416,7 +450,11 @@ class ViLTransformerSS(nn.Module):
             ret.update(objectives.compute_vqa(self, batch))
         if "vqa_attacked" in self.current_tasks:
             ret.update(objectives.compute_vqa_attack(self, batch))
-        unsupported = [t for t in self.current_tasks if t not in ("itm", "moco", "barlowtwins", "vqa", "vqa_attacked")]
+        if "nlvr2" in self.current_tasks:
+            ret.update(objectives.compute_nlvr2(self, batch))
+        if "nlvr2_attacked" in self.current_tasks:
+            ret.update(objectives.compute_nlvr2_attack(self, batch))
+        unsupported = [t for t in self.current_tasks if t not in ("itm", "moco", "barlowtwins", "vqa", "vqa_attacked", "nlvr2", "nlvr2_attacked")]
         if unsupported:
             raise NotImplementedError(f"tasks {unsupported} are outside the RMCL hot path (SURVEY 8)")
         return ret
