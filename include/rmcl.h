@@ -333,6 +333,47 @@ int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, co
                          int32_t* co_mask, void* stash, void* workspace, float* xn,
                          uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold, void* stream);
 
+/* ---- Image-text retrieval (IRTR) ---------------------------------------------------------------------------------------
+ * The image side of VisionTransformer.visual_embed (vision_transformer.py:559-677, mask_it = False) for the patch rows of
+ * rmcl_encoder_forward: patch GEMM + (resized) position rows + cls token, WITHOUT the token-type row (the reference adds it in infer,
+ * vilt_module.py:315-321).  out [B, 1 + P, D] f32, masks [B, 1 + P] int32 (cls 1, then the patch mask rmcl_encoder_forward derives).
+ * workspace: rmcl_workspace_bytes(d).  ragged as for rmcl_encoder_forward (dpos_tok is not used).                             */
+int rmcl_visual_embed(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
+                      void* workspace, float* out, int32_t* masks, void* stream);
+
+/* The image tokens of a rank pass come from a device-resident cache of rmcl_visual_embed outputs instead of pixels
+ * (compute_irtr_recall, objectives.py:1226-1346: every image against every caption).  embeds [n_img, ld_tok, D] f32 and
+ * masks [n_img, ld_tok] int32 hold one image per slot (rows behind an image's own tokens: zeros, mask 0); img_of [B] int32 names the
+ * slot of every sequence of the pass, so one pass holds ANY set of (image, caption) pairs.                                      */
+typedef struct rmcl_rank_src {
+  const float* embeds;
+  const int32_t* masks;
+  const int32_t* img_of;
+  int32_t n_img;
+  int32_t ld_tok;           /* token rows per cache slot, >= 1 + d->P */
+} rmcl_rank_src;
+/* rmcl_encoder_forward in INFER mode (RMCL_MODE_CLS_TAIL may be OR-ed in) whose sequence b is text b + the first 1 + d->P cached token
+ * rows of image img_of[b] + token-type row 1; co_mask [B, N] = text mask | cached image mask.  No dropout, no stash.  A sequence whose
+ * img_of is outside [0, n_img) gets zero image rows and a zero image mask.                                                      */
+int rmcl_encoder_forward_rank(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                              const int64_t* text_mask, const rmcl_rank_src* src, int32_t* co_mask, void* workspace, float* xn,
+                              const rmcl_fold* fold, void* stream);
+/* rank_output (vilt_module.py:233-239: Linear(D, 1) whose weight / bias are row 1 of itm_score.fc): scores[o] = cls[i] . w + b with
+ * o = out_index[i] (int32, e.g. img * n_txt + txt of the recall score matrix) or i when out_index is NULL.  cls rows have pitch ld_cls;
+ * scores holds out_n floats and an index outside [0, out_n) is dropped.  One wave per sequence.                                 */
+int rmcl_irtr_score(const float* cls, int64_t ld_cls, const float* w, const float* bias, int S, int D, float* scores,
+                    const int32_t* out_index, int64_t out_n, void* stream);
+/* compute_irtr's loss (objectives.py:1211-1214): cross-entropy against answer 0 over each of the B groups of R consecutive scores
+ * (the true caption first, then draw_false_text false ones; R <= 64).  stats [2] = (mean loss, groups whose first maximum is score 0);
+ * rows [B] (optional) per-group loss; dscore [B * R] (optional) = grad_scale * s * (softmax - onehot_0) / B with s = *grad_scale_dev or 1.
+ * One workgroup, fixed reduction order, no float atomics.                                                                       */
+int rmcl_irtr_ce(const float* scores, int B, int R, float grad_scale, const float* grad_scale_dev, float* dscore, float* rows, float* stats,
+                 void* stream);
+/* dcls [S, D] = dscore[i] * w;  dw [D] += sum_i dscore[i] * cls[i, :] (i ascending);  db [1] += sum_i dscore[i].  dw / db may be NULL
+ * (data gradient only).  No float atomics.                                                                                      */
+int rmcl_irtr_bwd(const float* dscore, const float* cls, int64_t ld_cls, const float* w, int S, int D, float* dcls, float* dw, float* db,
+                  void* stream);
+
 /* Backward of the above.  dxn: gradient wrt xn, [B*N,D] f32, or [B,D] (row 0 of every sample)
  * when cls_only=1; cls_only=2: the same [B,D] gradient for a stash whose forward ran with RMCL_MODE_CLS_TAIL (compact last
  * layer).  dpatches (optional) receives d loss/d patches [B*P,patch_k] in `dtype`

@@ -59,6 +59,11 @@ class VqaHead(C.Structure):
                 ("w0", C.c_int64), ("b0", C.c_int64), ("g1", C.c_int64), ("b1", C.c_int64), ("w3", C.c_int64), ("b3", C.c_int64)]
 
 
+class RankSrc(C.Structure):
+    """include/rmcl.h rmcl_rank_src: the cache of visual_embed outputs a rank pass gathers its image tokens from (device pointers)."""
+    _fields_ = [("embeds", C.c_void_p), ("masks", C.c_void_p), ("img_of", C.c_void_p), ("n_img", C.c_int32), ("ld_tok", C.c_int32)]
+
+
 class RmclError(RuntimeError):
     pass
 
@@ -92,6 +97,7 @@ EXPORTS = (
     "rmcl_bt_dz", "rmcl_bt_pair_metrics",
     "rmcl_vqa_stash_floats", "rmcl_vqa_head_forward", "rmcl_vqa_bce", "rmcl_vqa_targets_dense", "rmcl_vqa_head_backward",
     "rmcl_nlvr2_ce",
+    "rmcl_visual_embed", "rmcl_encoder_forward_rank", "rmcl_irtr_score", "rmcl_irtr_ce", "rmcl_irtr_bwd",
 )
 
 

@@ -351,13 +351,16 @@ void rmcl_param_layout(const rmcl_dims* d, rmcl_layout* o) {
 int64_t rmcl_stash_bytes(const rmcl_dims* d, int mode) { return (int64_t)carve_stash(*d, mode, nullptr, nullptr) + 256; }
 int64_t rmcl_workspace_bytes(const rmcl_dims* d) { return (int64_t)carve_work(*d, nullptr, nullptr) + 256; }
 
-int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
-                         const int64_t* text_mask, const void* patches, int32_t* co_mask, void* stash, void* workspace,
-                         float* xn, uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold, void* stream) {
+// rank != NULL: the image tokens and their mask come from a cache of rmcl_visual_embed outputs (rmcl_encoder_forward_rank); `patches`
+// and `ragged` are then unused
+static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                                const int64_t* text_mask, const void* patches, int32_t* co_mask, void* stash, void* workspace,
+                                float* xn, uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold,
+                                const rmcl_rank_src* rank, void* stream) {
   RMCL_TRY(check_dims(d));
   RMCL_REQUIRE(!ragged || (ragged->sel && ragged->counts && ragged->hw && ragged->pos_tok), "encoder_forward: incomplete rmcl_ragged");
-  RMCL_REQUIRE(ragged || d->Pp == 0 || d->Pp == d->P, "encoder_forward: P != Pp needs the rmcl_ragged selection");
-  RMCL_REQUIRE(params32 && text_ids && text_mask && patches && co_mask && workspace && xn, "encoder_forward: NULL argument");
+  RMCL_REQUIRE(rank || ragged || d->Pp == 0 || d->Pp == d->P, "encoder_forward: P != Pp needs the rmcl_ragged selection");
+  RMCL_REQUIRE(params32 && text_ids && text_mask && (patches || rank) && co_mask && workspace && xn, "encoder_forward: NULL argument");
   RMCL_REQUIRE(d->dtype == RMCL_F32 || params_lp, "encoder_forward: bf16 mode needs the bf16 shadow arena");
   const bool tail_req = (mode & RMCL_MODE_CLS_TAIL) != 0;     // only the cls rows of xn will be read (include/rmcl.h)
   mode &= ~RMCL_MODE_CLS_TAIL;
@@ -384,22 +387,26 @@ int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, co
   RMCL_TRY(rmcl_text_embed_fwd((const long*)text_ids, c.V(y.word), c.V(y.pos), c.V(y.btype), c.V(y.eln_w), c.V(y.eln_b),
                                c.V(y.vtype), 1e-12f, x0, keep ? st.text_e : nullptr, keep ? st.text_mean : nullptr,
                                keep ? st.text_rstd : nullptr, B, L, N, D, rmcl_site_seed(drop_seed, 0, DROP_SITE_TEXT), dth, dinv, s));
-  {
+  if (rank) {
+    RMCL_TRY(rmcl_rank_assemble(rank->embeds, rank->masks, rank->img_of, rank->n_img, rank->ld_tok, (const long*)text_mask, c.V(y.vtype) + D,
+                                x0, co_mask, B, P, L, N, D, s));
+  } else {
+    // the pixel path: patch GEMM, (resized) position rows, cls + token type, mask from the patch rows
     GemmArgs g = gemm_args(patches, c.W(y.patch_w), w.pe, B * P, D, d->patch_k, d->patch_k, d->patch_k, D);
     g.epi = EPI_BIAS; g.bias = c.V(y.patch_b); g.tag = GEMM_TAG_PATCH;
     RMCL_TRY(gemm(c, g, dt, RMCL_F32, 1, 1));
+    if (ragged) {
+      // zero-padded batch: per-sample position rows = the table resized to each image's (h, w), gathered at its selected
+      // patches (vision_transformer.py:570-600, 645-650); recomputed every pass from the arena of THIS pass (query or momentum)
+      RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
+                                   ragged->pos_tok, s));
+    }
+    // image token type (vilt_module.py:315-321): row 1, row 2 (img_type 2), or row 1 + (b & 1) per pair (img_type -1)
+    RMCL_TRY(rmcl_image_assemble_fwd(w.pe, c.V(y.cls), ragged ? ragged->pos_tok : c.V(y.pos_img), c.V(y.vtype) + (d->img_type == 2 ? 2 : 1) * D,
+                                     x0, B, P, L, N, D, rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, ragged ? 1 : 0,
+                                     d->img_type == -1 ? 1 : 0, s));
+    RMCL_TRY(rmcl_co_mask((const long*)text_mask, patches, dt, co_mask, B, L, P, 3, d->patch_k / 3, s));
   }
-  if (ragged) {
-    // zero-padded batch: per-sample position rows = the table resized to each image's (h, w), gathered at its selected
-    // patches (vision_transformer.py:570-600, 645-650); recomputed every pass from the arena of THIS pass (query or momentum)
-    RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
-                                 ragged->pos_tok, s));
-  }
-  // image token type (vilt_module.py:315-321): row 1, row 2 (img_type 2), or row 1 + (b & 1) per pair (img_type -1)
-  RMCL_TRY(rmcl_image_assemble_fwd(w.pe, c.V(y.cls), ragged ? ragged->pos_tok : c.V(y.pos_img), c.V(y.vtype) + (d->img_type == 2 ? 2 : 1) * D,
-                                   x0, B, P, L, N, D, rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, ragged ? 1 : 0,
-                                   d->img_type == -1 ? 1 : 0, s));
-  RMCL_TRY(rmcl_co_mask((const long*)text_mask, patches, dt, co_mask, B, L, P, 3, d->patch_k / 3, s));
 
   // LayerNorm folded into the consuming GEMMs (gemm.h EPI_LNFOLD / EPI_ROWSTAT): passes that keep no LayerNorm output
   // (INFER, DATA), bf16, dropout off, and only where every GEMM involved runs on the 192-row tile kernels
@@ -528,6 +535,52 @@ int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, co
   }
   RMCL_TRY(rmcl_ln_fwd(x, D, c.V(y.norm_w), c.V(y.norm_b), 1e-6f, xn, D, RMCL_F32, keep ? st.meanF : w.stat,
                        keep ? st.rstdF : w.stat + M, M, D, 0, s));
+  return 0;
+}
+
+int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                         const int64_t* text_mask, const void* patches, int32_t* co_mask, void* stash, void* workspace,
+                         float* xn, uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold, void* stream) {
+  return encoder_forward_impl(d, mode, params32, params_lp, text_ids, text_mask, patches, co_mask, stash, workspace, xn, drop_seed, drop_p,
+                              ragged, fold, nullptr, stream);
+}
+
+int rmcl_encoder_forward_rank(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                              const int64_t* text_mask, const rmcl_rank_src* src, int32_t* co_mask, void* workspace, float* xn,
+                              const rmcl_fold* fold, void* stream) {
+  RMCL_REQUIRE(d && src && src->embeds && src->masks && src->img_of, "encoder_forward_rank: NULL argument");
+  RMCL_REQUIRE((mode & ~RMCL_MODE_CLS_TAIL) == RMCL_MODE_INFER, "encoder_forward_rank: INFER mode only (the rank pass keeps no stash)");
+  RMCL_REQUIRE(src->n_img >= 1 && d->P >= 1 && d->P + 1 <= src->ld_tok, "encoder_forward_rank: the cache slots hold fewer than 1 + P token rows");
+  RMCL_REQUIRE(d->img_type == 0 || d->img_type == 1, "encoder_forward_rank: image tokens take token-type row 1");
+  return encoder_forward_impl(d, mode, params32, params_lp, text_ids, text_mask, nullptr, co_mask, nullptr, workspace, xn, 0u, 0.f, nullptr,
+                              fold, src, stream);
+}
+
+int rmcl_visual_embed(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
+                      void* workspace, float* out, int32_t* masks, void* stream) {
+  RMCL_TRY(check_dims(d));
+  RMCL_REQUIRE(params32 && patches && workspace && out && masks, "visual_embed: NULL argument");
+  RMCL_REQUIRE(!ragged || (ragged->sel && ragged->counts && ragged->hw && ragged->pos_tok), "visual_embed: incomplete rmcl_ragged");
+  RMCL_REQUIRE(ragged || d->Pp == 0 || d->Pp == d->P, "visual_embed: P != Pp needs the rmcl_ragged selection");
+  RMCL_REQUIRE(d->dtype == RMCL_F32 || params_lp, "visual_embed: bf16 mode needs the bf16 shadow arena");
+  Ctx c{*d, params32, params_lp, {}, (hipStream_t)stream, d->dtype};
+  rmcl_param_layout(d, &c.lay);
+  const rmcl_layout& y = c.lay;
+  Work w{};
+  carve_work(*d, workspace, &w);
+  const int B = d->B, P = d->P, D = d->D;
+  {
+    GemmArgs g = gemm_args(patches, c.W(y.patch_w), w.pe, B * P, D, d->patch_k, d->patch_k, d->patch_k, D);
+    g.epi = EPI_BIAS; g.bias = c.V(y.patch_b); g.tag = GEMM_TAG_PATCH;
+    RMCL_TRY(gemm(c, g, d->dtype, RMCL_F32, 1, 1));
+  }
+  if (ragged) {
+    RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
+                                 ragged->pos_tok, c.s));
+  }
+  RMCL_TRY(rmcl_visual_assemble(w.pe, c.V(y.cls), ragged ? ragged->pos_tok : c.V(y.pos_img), ragged ? 1 : 0, out, B, P, D, c.s));
+  // the mask of rmcl_encoder_forward's image tokens (L = 0: no text columns; the text-mask pointer is never read)
+  RMCL_TRY(rmcl_co_mask(nullptr, patches, d->dtype, masks, B, 0, P, 3, d->patch_k / 3, c.s));
   return 0;
 }
 

@@ -141,3 +141,7 @@ int rmcl_itm_head_fwd(const float* cls, const float* W, const float* bias, const
                       float* loss_sum, int B, int D, float gscale, hipStream_t s);
 int rmcl_itm_head_bwd(const float* dl, const float* cls, const float* W, float* dcls, float* dW, float* db, int B, int D, float scale,
                       hipStream_t s);
+// irtr.hip: the image side of visual_embed without the token-type row, and the token assembly of the cached rank pass
+int rmcl_visual_assemble(const float* pe, const float* cls, const float* pos, int pos_per_sample, float* out, int B, int P, int D, hipStream_t s);
+int rmcl_rank_assemble(const float* embeds, const int* masks, const int* img_of, int n_img, int ld_tok, const long* text_mask,
+                       const float* vtype1, float* x, int* co, int B, int P, int L, int N, int D, hipStream_t s);

@@ -33,6 +33,20 @@ def is_nlvr2(cfg: dict) -> bool:
     return ln.get("nlvr2", 0) > 0 or ln.get("nlvr2_attacked", 0) > 0
 
 
+def is_irtr(cfg: dict) -> bool:
+    """IRTR fine-tuning (loss_names irtr): rank_output = row 1 of the ITM head (vilt_module.py:233-239)."""
+    return cfg.get("loss_names", {}).get("irtr", 0) > 0
+
+
+def irtr_alias_specs(cfg: dict, lay: L.Layout) -> List[Tuple[str, int, Tuple[int, ...]]]:
+    """rank_output.weight / .bias of an IRTR model: VIEWS of row 1 of the ITM head's slots (vilt_module.py:233-236) - no arena space of
+    their own.  Empty for every other model."""
+    if not is_irtr(cfg):
+        return []
+    D = int(cfg["hidden_size"])
+    return [("rank_output.weight", int(lay.itm_w) + D, (1, D)), ("rank_output.bias", int(lay.itm_b) + 1, (1,))]
+
+
 def make_dims(cfg: dict, B: int, dtype: int, exact: bool, P: int = None) -> L.Dims:
     """P: image patches per sample in this pass (default: the full grid); the position table always has the full grid.
     n_types = 3 for an NLVR2 model (include/rmcl.h rmcl_dims); img_type starts at 0 (row 1) and is set per pass."""
@@ -279,6 +293,36 @@ class PassBuffers:
         self.tail = {}
 
 
+class RankPass:
+    """Buffers of the cached rank pass (inference only: a workspace, the mask, xn, the pooled cls rows).  ONE set,
+    grown to the largest (sequences, patches) asked for and viewed at every smaller shape, so tiles of any padded length share it
+    (DESIGN.md "IRTR fine-tuning and recall")."""
+
+    def __init__(self, eng: "Engine"):
+        self.eng = eng
+        self.geom = self.ragged = None
+        self._ws = self._hst = self._co = self._xn = self._cls = None
+
+    def _grow(self, name, n, dtype):
+        t = getattr(self, name)
+        if t is None or t.numel() < n:
+            t = torch.empty(int(n), dtype=dtype, device=self.eng.device)
+            setattr(self, name, t)
+        return t
+
+    def shape(self, B: int, P: int) -> "RankPass":
+        eng = self.eng
+        d = eng.dims(B, None, P)
+        N = d.L + 1 + d.P
+        self.B, self.d, self.dtype = B, d, eng.dtype
+        self.workspace = self._grow("_ws", lib.rmcl_workspace_bytes(C.byref(d)), torch.uint8)
+        self.hstash_q = self._grow("_hst", lib.rmcl_heads_stash_bytes(C.byref(d)), torch.uint8)
+        self.co_mask = self._grow("_co", B * N, torch.int32)[: B * N].view(B, N)
+        self.xn = self._grow("_xn", B * N * d.D, torch.float32)[: B * N * d.D].view(B * N, d.D)
+        self.cls = self._grow("_cls", B * d.D, torch.float32)[: B * d.D].view(B, d.D)
+        return self
+
+
 class RaggedGeometry:
     """Patch selection of a zero-padded batch [B,3,Hmax,Wmax] (VisionTransformer.visual_embed, vision_transformer.py:559-651):
     sel [B, cap] int32 flat patch indices (valid patches row-major, then pads), counts [B], hw [B,2] = (x_h, x_w), n slots."""
@@ -337,6 +381,11 @@ class Engine:
             self.nlvr2, self.nlvr2_specs, n_nl = nlvr2_layout(cfg, int(lay.total) + extra)
             extra += n_nl
             self._nlvr2_bufs = {}
+        # IRTR (loss_names["irtr"] > 0): rank_output.weight / .bias ARE row 1 of the ITM head's slots (vilt_module.py:233-239 makes them
+        # views of itm_score.fc): no arena space of their own; `specs` keeps its entries, the aliases are listed apart
+        self.irtr = is_irtr(cfg)
+        self.alias_specs = irtr_alias_specs(cfg, lay)
+        self._rank_pass = None
         self.total = int(lay.total) + extra
         self.q32 = z(self.total)
         self.k32 = z(lay.ema_end)
@@ -500,7 +549,7 @@ class Engine:
         self.g32.zero_()
 
     # ---- per-step data -------------------------------------------------------------------------
-    def patch_geometry(self, img: torch.Tensor, select: torch.Tensor = None):
+    def patch_geometry(self, img: torch.Tensor, select: torch.Tensor = None, max_image_len=None, check_tokens: bool = True):
         """None for a batch of full-size images (every patch of the image_size x image_size grid valid), else the
         RaggedGeometry of the zero-padded batch.  One device->host copy of B counts (n sizes the launches).
         config["dense_images"] = True skips the check for image_size x image_size inputs (synthetic benchmarks)."""
@@ -523,10 +572,10 @@ class Engine:
         if Hh == S and Ww == S and select is None and bool((cnt == gh * gw).all()):
             return None
         n = int(cnt.max())
-        mil = self.cfg.get("max_image_len", -1)
+        mil = self.cfg.get("max_image_len", -1) if max_image_len is None else max_image_len
         if isinstance(mil, int) and mil > 0:
             n = min(n, mil)                                                # vision_transformer.py:602-616
-        if n + 1 + self.cfg["max_text_len"] > 256 and self.dtype == L.BF16:
+        if check_tokens and n + 1 + self.cfg["max_text_len"] > 256 and self.dtype == L.BF16:
             raise NotImplementedError(f"{n} image patches + text exceed the 256-token limit of the fused attention kernels")
         if select is not None:                                             # the caller's draw (parity tests: the reference's)
             sel = select.to(self.device, torch.int32).contiguous()
@@ -957,6 +1006,110 @@ class Engine:
         check(lib.rmcl_vqa_head_backward(C.byref(self.nlvr2), P(self.q32), P(nb.stash), P(dz), nb.B, P(self.g32 if with_grads else None),
                                          P(nb.dcls), stream_ptr()), "nlvr2_head_backward")
         return nb.dcls
+
+    # ---- IRTR: rank head, visual_embed, the cached rank pass (include/rmcl.h "Image-text retrieval") ------------------------------------
+    def rank_params(self, arena: torch.Tensor = None):
+        """(weight [D], bias [1]) of rank_output = row 1 of the ITM head's slots, in `arena` (default: the parameters)."""
+        a = self.q32 if arena is None else arena
+        lay, D = self.layout, int(self.cfg["hidden_size"])
+        return a[lay.itm_w + D:lay.itm_w + 2 * D], a[lay.itm_b + 1:lay.itm_b + 2]
+
+    def irtr_score(self, cls: torch.Tensor, scores: torch.Tensor, out_index: torch.Tensor = None):
+        """scores[out_index[i] or i] = rank_output(cls[i])."""
+        w, b = self.rank_params()
+        check(lib.rmcl_irtr_score(P(cls), I64(cls.stride(0)), P(w), P(b), cls.shape[0], cls.shape[1], P(scores), P(out_index),
+                                  I64(scores.numel()), stream_ptr()), "irtr_score")
+        return scores
+
+    def irtr_ce(self, scores: torch.Tensor, B: int, R: int, grad_scale: float, dscore=None, scale_dev=None, rows=None, stats=None):
+        stats = torch.empty(2, dtype=torch.float32, device=self.device) if stats is None else stats
+        check(lib.rmcl_irtr_ce(P(scores), B, R, F(grad_scale), P(scale_dev), P(dscore), P(rows), P(stats), stream_ptr()), "irtr_ce")
+        return stats
+
+    def irtr_backward(self, dscore: torch.Tensor, cls: torch.Tensor, dcls: torch.Tensor, with_grads: bool):
+        w, _ = self.rank_params()
+        gw, gb = self.rank_params(self.g32) if with_grads else (None, None)
+        check(lib.rmcl_irtr_bwd(P(dscore), P(cls), I64(cls.stride(0)), P(w), cls.shape[0], cls.shape[1], P(dcls), P(gw), P(gb), stream_ptr()),
+              "irtr_bwd")
+        return dcls
+
+    def token_limit_error(self, n_patches: int):
+        """the message of a rank pass / recall evaluation that cannot run: names the two ways out"""
+        Lt = int(self.cfg["max_text_len"])
+        return NotImplementedError(
+            f"{n_patches} image patches + 1 cls + {Lt} text tokens = {n_patches + 1 + Lt} tokens exceed the 256-token limit of the fused bf16 "
+            f"attention kernels: set max_image_len <= {255 - Lt}, or build the model with compute_dtype='f32' (the fp32 engine has no such limit)")
+
+    def visual_embed(self, images: torch.Tensor, max_image_len=None, select: torch.Tensor = None):
+        """VisionTransformer.visual_embed (vision_transformer.py:559-677, mask_it=False): (embeds [B, 1 + n, D] f32 WITHOUT the token-type
+        row, masks [B, 1 + n] int64, patch_index [B, n, 2]).  No token limit applies here (the pass has no text): the rank pass checks.
+        Runs once per image, so its buffers are allocated per call (the caching allocator hands the same blocks back)."""
+        if self.lp_stale:
+            self.refresh_shadows()
+        img = images.to(self.device, torch.float32).contiguous()
+        B, _, Hh, Ww = img.shape
+        ps = self.cfg["patch_size"]
+        geom = self.patch_geometry(img, select, max_image_len=max_image_len, check_tokens=False)
+        g = self.cfg["image_size"] // ps
+        n = g * g if geom is None else geom.n
+        d = self.dims(B, None, n)
+        ws = torch.empty(int(lib.rmcl_workspace_bytes(C.byref(d))), dtype=torch.uint8, device=self.device)
+        pat32 = torch.empty(B * n, d.patch_k, dtype=torch.float32, device=self.device)
+        op = pat32 if self.dtype == L.F32 else torch.empty(B * n, d.patch_k, dtype=torch.bfloat16, device=self.device)
+        rg = None
+        if geom is None:
+            check(lib.rmcl_im2patch_f32(P(img), P(pat32), B, 3, Hh, Ww, ps, 0, stream_ptr()), "im2patch")
+            ii, jj = torch.meshgrid(torch.arange(g), torch.arange(g), indexing="ij")
+            patch_index = torch.stack([ii, jj], dim=-1).reshape(1, g * g, 2).expand(B, -1, -1)
+        else:
+            check(lib.rmcl_im2patch_sel(P(img), P(pat32), P(geom.sel), P(geom.counts), geom.sel.shape[1], B, n, 3, Hh, Ww, ps, 0,
+                                        stream_ptr()), "im2patch_sel")
+            pos_tok = torch.empty(B, n + 1, d.D, dtype=torch.float32, device=self.device)
+            rg = L.Ragged(sel=geom.sel.data_ptr(), counts=geom.counts.data_ptr(), hw=geom.hw.data_ptr(), sel_ld=geom.sel.shape[1],
+                          gw=geom.gw, G0=g, pos_tok=pos_tok.data_ptr(), dpos_tok=0)
+            sel = geom.sel[:, :n].to(torch.int64)
+            patch_index = torch.stack([sel // geom.gw, sel % geom.gw], dim=-1)
+        if self.dtype != L.F32:
+            check(lib.rmcl_add_cast_f32(P(pat32), None, None, P(op), self.dtype, I64(pat32.numel()), stream_ptr()), "add_cast")
+        out = torch.empty(B, n + 1, d.D, dtype=torch.float32, device=self.device)
+        masks = torch.empty(B, n + 1, dtype=torch.int32, device=self.device)
+        check(lib.rmcl_visual_embed(C.byref(d), P(self.q32), P(self.q_lp), P(op), C.byref(rg) if rg is not None else None, P(ws), P(out),
+                                    P(masks), stream_ptr()), "visual_embed")
+        return out, masks.to(torch.int64), patch_index
+
+    def rank_forward(self, text_ids: torch.Tensor, text_mask: torch.Tensor, embeds: torch.Tensor, masks: torch.Tensor, img_of: torch.Tensor,
+                     n_patches: int, cls_tail: bool = True) -> RankPass:
+        """One encoder pass over the sequences (text b, cached image img_of[b]) and the pooler: embeds [n_img, ld_tok, D] f32 / masks
+        [n_img, ld_tok] int32 are the cache of visual_embed outputs, n_patches <= ld_tok - 1 the padded image length of THIS pass.
+        Returns the pass buffers (.cls [B, D] pooled, .xn, .co_mask)."""
+        if self.lp_stale:
+            self.refresh_shadows()
+        B = int(text_ids.shape[0])
+        if embeds.dtype != torch.float32 or masks.dtype != torch.int32 or img_of.dtype != torch.int32 or not (
+                embeds.is_contiguous() and masks.is_contiguous() and img_of.is_contiguous()):
+            raise ValueError("rank_forward: embeds f32 [n_img, ld_tok, D], masks / img_of int32, all contiguous")
+        n_img, ld_tok, D = embeds.shape
+        if tuple(masks.shape) != (n_img, ld_tok) or img_of.numel() != B or n_patches + 1 > ld_tok or n_patches < 1 or D != self.cfg["hidden_size"]:
+            raise ValueError(f"rank_forward: shapes do not fit (embeds {tuple(embeds.shape)}, masks {tuple(masks.shape)}, {B} sequences, "
+                             f"{n_patches} patches)")
+        if n_patches + 1 + self.cfg["max_text_len"] > 256 and self.dtype == L.BF16:
+            raise self.token_limit_error(n_patches)
+        if self._rank_pass is None:
+            self._rank_pass = RankPass(self)
+        rp = self._rank_pass.shape(B, n_patches)
+        rp.text_ids = text_ids.to(self.device, torch.int64).contiguous()
+        rp.text_mask = text_mask.to(self.device, torch.int64).contiguous()
+        if tuple(rp.text_ids.shape) != (B, rp.d.L) or tuple(rp.text_mask.shape) != (B, rp.d.L):
+            raise ValueError(f"rank_forward: text must be [B, max_text_len={rp.d.L}]")
+        src = L.RankSrc(embeds=embeds.data_ptr(), masks=masks.data_ptr(), img_of=img_of.data_ptr(), n_img=n_img, ld_tok=ld_tok)
+        tail = bool(cls_tail) and B <= 1024 and os.environ.get("RMCL_NO_CLS_TAIL", "0") != "1"
+        fold = self.fold_of(False) if rp.dtype == L.BF16 else None
+        check(lib.rmcl_encoder_forward_rank(C.byref(rp.d), L.MODE_INFER | (L.MODE_CLS_TAIL if tail else 0), P(self.q32), P(self.q_lp),
+                                            P(rp.text_ids), P(rp.text_mask), C.byref(src), P(rp.co_mask), P(rp.workspace), P(rp.xn), fold,
+                                            stream_ptr()), "encoder_forward_rank")
+        rp.keep_alive = (embeds, masks, img_of)
+        self.heads_forward(rp, key=False, want_q=False, wgrad=False)
+        return rp
 
     def pgd_step(self, pb: PassBuffers, lr: float, eps: float, first: bool = False, out: torch.Tensor = None, sum_prev: bool = False):
         """delta <- clamp(delta + lr g / max|g|, +-eps) (pgd_attack_vilt.py:162-173).  ``out``: also written in the same pass,

@@ -124,3 +124,46 @@ def task_finetune_nlvr2_randaug_attacked(**over):
     )
     cfg.update(over)
     return cfg
+
+
+def task_finetune_irtr_coco(**over):
+    """reference config.py:349-360: image-text retrieval fine-tuning on COCO (itm + irtr: rank_output on row 1 of the ITM head, 15 false
+    captions per image, recalls at every validation end).  max_steps None as in the reference: set_schedule then needs it from the caller."""
+    cfg = default_config(
+        exp_name="finetune_irtr_coco", datasets=["coco"], loss_names=_loss_names({"itm": 0.5, "irtr": 1}), batch_size=256, max_epoch=128,
+        max_steps=None, warmup_steps=0.1, get_recall_metric=True, draw_false_text=15, learning_rate=1e-4,
+    )
+    cfg.update(over)
+    return cfg
+
+
+def task_finetune_irtr_coco_randaug(**over):
+    """reference config.py:363-375 (the RandAugment train transform itself is the caller's)."""
+    cfg = default_config(
+        exp_name="finetune_irtr_coco_randaug", datasets=["coco"], train_transform_keys=["pixelbert_randaug"],
+        loss_names=_loss_names({"itm": 0.5, "irtr": 1}), batch_size=128, max_epoch=2, max_steps=None, warmup_steps=0.1,
+        get_recall_metric=True, draw_false_text=15, learning_rate=1e-4,
+    )
+    cfg.update(over)
+    return cfg
+
+
+def task_finetune_irtr_f30k(**over):
+    """reference config.py:408-419: image-text retrieval fine-tuning on Flickr30k."""
+    cfg = default_config(
+        exp_name="finetune_irtr_f30k", datasets=["f30k"], loss_names=_loss_names({"itm": 0.5, "irtr": 1}), batch_size=128, max_epoch=10,
+        max_steps=None, warmup_steps=0.1, get_recall_metric=True, draw_false_text=15, learning_rate=1e-4,
+    )
+    cfg.update(over)
+    return cfg
+
+
+def task_finetune_irtr_f30k_randaug(**over):
+    """reference config.py:422-434 (the RandAugment train transform itself is the caller's)."""
+    cfg = default_config(
+        exp_name="finetune_irtr_f30k_randaug", datasets=["f30k"], train_transform_keys=["pixelbert_randaug"],
+        loss_names=_loss_names({"itm": 0.5, "irtr": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,
+        get_recall_metric=True, draw_false_text=15, learning_rate=1e-4,
+    )
+    cfg.update(over)
+    return cfg

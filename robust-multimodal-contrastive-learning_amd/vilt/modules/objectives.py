@@ -171,6 +171,10 @@ def compute_itm_wpa(pl_module, batch):
             dl = dlogits * g[0]
             dcls_itm = torch.empty(Bn, D, device=dev)
             gw, gb = eng.g32[lay.itm_w:lay.itm_w + 2 * D], eng.g32[lay.itm_b:lay.itm_b + 2]
+            if eng.irtr:
+                # an IRTR model freezes itm_score (vilt_module.py:237-239): the ITM loss trains the encoder but writes no gradient into the
+                # head - nor, through the alias, into rank_output
+                gw = gb = None
             check(lib.rmcl_itm_bwd(P(dl), P(pb.cls), P(w_itm), P(dcls_itm), P(gw), P(gb), Bn, D, F(1.0), st2), "itm_bwd")
             eng.heads_backward(pb, None, dcls_itm, with_grads=True)
             ds = dsim * g[1]
@@ -692,3 +696,204 @@ def compute_nlvr2_attack(pl_module, batch):
         _log_split(pl_module, batch, "nlvr2_original", nb_c)
         _log_split(pl_module, batch, "nlvr2_attacked", nb_a, ref_nb=nb_c)
     return ret
+
+
+def compute_irtr(pl_module, batch):
+    """objectives.py:1180-1223: every image against its true caption and draw_false_text false ones (true first), ONE pass of B * R
+    sequences (R = 1 + draw_false_text), score = rank_output(cls_feats)[:, 0] as [B, R], cross-entropy against answer 0.  The images are
+    bound once; the patch rows of image b are replicated R times on the device (the reference expands the pixels)."""
+    eng = pl_module.engine
+    if not eng.irtr:
+        raise ValueError("compute_irtr needs a model built with loss_names['irtr'] > 0 (rank_output)")
+    Fn = int(pl_module.hparams.config["draw_false_text"])
+    R = Fn + 1
+    if R > 64:
+        raise ValueError(f"draw_false_text = {Fn}: at most 63 false texts per image (include/rmcl.h rmcl_irtr_ce)")
+    dev = eng.device
+    ids = torch.stack([batch["text_ids"]] + [batch[f"false_text_{i}_ids"] for i in range(Fn)], dim=1).to(dev)
+    msk = torch.stack([batch["text_masks"]] + [batch[f"false_text_{i}_masks"] for i in range(Fn)], dim=1).to(dev)
+    B = int(ids.shape[0])
+    S = B * R
+    pimg = eng.bind_batch(batch["text_ids"], batch["text_masks"], batch["image"][0], tag="irtr_img")
+    owner = torch.arange(B, device=dev).repeat_interleave(R)
+    pb = eng.twin(pimg, "irtr", owner=owner)
+    pb.d.img_type = 0
+    pb.text_ids = ids.reshape(S, -1).to(torch.int64).contiguous()
+    pb.text_mask = msk.reshape(S, -1).to(torch.int64).contiguous()
+    per = pimg.d.P * pimg.d.patch_k
+    torch.index_select(pimg.patches32.view(B, per), 0, owner, out=pb.patches32.view(S, per))
+    need_grad = torch.is_grad_enabled() and pl_module.training
+    op = eng.make_operand(pb, out=pb.patchesT_full)
+    eng.encoder_forward(pb, key=False, mode=L.MODE_FULL if need_grad else L.MODE_INFER, patchesT=op, cls_tail=True)
+    eng.heads_forward(pb, key=False, want_q=False, wgrad=need_grad)
+    scores = torch.empty(S, dtype=torch.float32, device=dev)
+    eng.irtr_score(pb.cls, scores)
+    stats = eng.irtr_ce(scores, B, R, 1.0)
+    value = _scalar(stats[0])
+    if need_grad:
+        def backward(grad_out, pb=pb, op=op, scores=scores):
+            g = grad_out.to(torch.float32).reshape(1).contiguous()
+            dscore = torch.empty(S, dtype=torch.float32, device=dev)
+            eng.irtr_ce(scores, B, R, 1.0, dscore=dscore, scale_dev=g)
+            dcls = eng.irtr_backward(dscore, pb.cls, torch.empty(S, pb.d.D, dtype=torch.float32, device=dev), with_grads=True)
+            eng.heads_backward(pb, None, dcls, with_grads=True)
+            eng.encoder_backward(pb, L.MODE_FULL, op, pb.dcls, cls_only=True, dpatches=None)
+            pl_module.after_backward()
+
+        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+    phase = "train" if pl_module.training else "val"
+    pl_module.log(f"irtr/{phase}/irtr_loss", value.detach())
+    return {"irtr_loss": value, "irtr_scores": scores.view(B, R)}
+
+
+# ---- IRTR recall evaluation (objectives.py:1226-1346) ---------------------------------------------------------------------------------
+def irtr_rank_split(n: int, world_size: int, rank: int) -> list:
+    """Indices of the images rank `rank` scores: torch.utils.data.DistributedSampler(dataset of n, shuffle=False, drop_last=False),
+    INCLUDING its wrap-around padding to ceil(n / world_size) * world_size (the reference's gathered score matrix then holds
+    duplicate image rows, and its recall means count them)."""
+    if n < 1 or world_size < 1 or not 0 <= rank < world_size:
+        raise ValueError(f"irtr_rank_split: n={n}, world_size={world_size}, rank={rank}")
+    per = -(-n // world_size)
+    total = per * world_size
+    idx = list(range(n))
+    pad = total - n
+    if pad <= n:
+        idx += idx[:pad]
+    else:
+        idx += (idx * (-(-pad // n)))[:pad]
+    return idx[rank:total:world_size]
+
+
+def irtr_recall_from_scores(scores: torch.Tensor, iids: torch.Tensor, tiids: torch.Tensor):
+    """(ir_r1, ir_r5, ir_r10, tr_r1, tr_r5, tr_r10) of a score matrix [rows = images (iids), columns = captions (tiids = the image
+    index of every caption)], exactly as objectives.py:1318-1344: top-k over rows (text retrieval) and over columns (image retrieval)."""
+    iids, tiids = iids.to(scores.device).view(-1), tiids.to(scores.device).view(-1)
+    if scores.dim() != 2 or tuple(scores.shape) != (iids.numel(), tiids.numel()):
+        raise ValueError(f"scores must be [images, captions] = [{iids.numel()}, {tiids.numel()}] (got {tuple(scores.shape)})")
+    if min(scores.shape) < 10:
+        raise ValueError(f"R@10 needs at least 10 images and 10 captions (got {tuple(scores.shape)}); the reference's topk(10) fails likewise")
+    match = iids.view(-1, 1) == tiids.view(1, -1)                      # [images, captions]: the caption belongs to the image
+    rec = {}
+    n_i, n_t = match.shape
+    # hits / n divided ONCE, on the host (a device division by a constant may multiply by its rounded reciprocal): fp32 scalars with
+    # the bits of the reference's CPU means
+    share = lambda hits, n: torch.tensor(int(hits.sum()) / n, dtype=torch.float32)
+    for k in (1, 5, 10):
+        best_txt = scores.topk(k, dim=1).indices                        # per image, its k best captions
+        rec[f"tr{k}"] = share(match.gather(1, best_txt).any(dim=1), n_i)
+        best_img = scores.topk(k, dim=0).indices                        # per caption, its k best images
+        rec[f"ir{k}"] = share(match.gather(0, best_img).any(dim=0), n_t)
+    return (rec["ir1"], rec["ir5"], rec["ir10"], rec["tr1"], rec["tr5"], rec["tr10"])
+
+
+def irtr_tiles(counts, n_txt: int, tile_images: int, tile_texts: int):
+    """Schedule of the rank passes: images sorted by patch count (stable) and cut into groups of `tile_images`, so a tile is padded only
+    to ITS OWN longest image; every group meets the captions in chunks of `tile_texts`.  Yields (image slots, padded patch count,
+    first caption, end caption)."""
+    order = sorted(range(len(counts)), key=lambda i: (counts[i], i))
+    for g0 in range(0, len(order), tile_images):
+        grp = order[g0:g0 + tile_images]
+        n = max(counts[i] for i in grp)
+        for t0 in range(0, n_txt, tile_texts):
+            yield grp, n, t0, min(n_txt, t0 + tile_texts)
+
+
+def _irtr_batches(dset, indices, batch_size, mlm_collator):
+    """collated batches of dset[indices]: a dataset with the reference's protocol (__getitem__ + collate), or a sequence of batches that
+    are already collated (one image per entry on the image side)"""
+    if hasattr(dset, "collate"):
+        for i in range(0, len(indices), batch_size):
+            yield dset.collate([dset[j] for j in indices[i:i + batch_size]], mlm_collator=mlm_collator)
+    else:
+        for j in indices:
+            yield dset[j]
+
+
+@torch.no_grad()
+def irtr_score_matrix(pl_module, embeds, masks, counts, text_ids, text_masks, tile_images: int, tile_texts: int) -> torch.Tensor:
+    """scores [n_img, n_txt] of every cached image against every caption, tile by tile (irtr_tiles) through the cached rank pass;
+    the score kernel writes straight into the matrix."""
+    eng = pl_module.engine
+    dev = eng.device
+    n_img, n_txt = int(embeds.shape[0]), int(text_ids.shape[0])
+    if n_img * n_txt >= 2 ** 31:
+        raise ValueError(f"score matrix of {n_img} x {n_txt} exceeds the int32 index of the score kernel")
+    scores = torch.full((n_img, n_txt), float("nan"), dtype=torch.float32, device=dev)
+    flat = scores.view(-1)
+    for grp, n, t0, t1 in irtr_tiles(counts, n_txt, tile_images, tile_texts):
+        T = t1 - t0
+        slots = torch.tensor(grp, dtype=torch.int32, device=dev)
+        img_of = slots.repeat_interleave(T).contiguous()
+        ids = text_ids[t0:t1].repeat(len(grp), 1)
+        msk = text_masks[t0:t1].repeat(len(grp), 1)
+        out_index = (img_of * n_txt + torch.arange(t0, t1, dtype=torch.int32, device=dev).repeat(len(grp))).contiguous()
+        rp = eng.rank_forward(ids, msk, embeds, masks, img_of, n, cls_tail=True)
+        eng.irtr_score(rp.cls, flat, out_index)
+    return scores
+
+
+@torch.no_grad()
+def compute_irtr_recall(pl_module, text_dset=None, image_dset=None, tile_images: int = 4, tile_texts: int = 64, return_scores: bool = False):
+    """objectives.py:1226-1346.  Every image of the validation split against every caption: the image side (visual_embed) runs once per
+    image into a device cache, the captions are cached too, and the n_img x n_txt forward passes run as tiles of tile_images x
+    tile_texts (image, caption) pairs through the cached rank pass (the reference: one image x 64 captions per pass).  Without
+    arguments the datasets come from pl_module.trainer.datamodule.dms[0].make_no_false_val_dset(max_num=500) like the reference's.
+    Images are split over ranks as DistributedSampler(shuffle=False) does (irtr_rank_split) and the rows gathered in rank order.
+    Returns (ir_r1, ir_r5, ir_r10, tr_r1, tr_r5, tr_r10); return_scores=True appends (scores, iids, tiids)."""
+    eng = pl_module.engine
+    if not eng.irtr:
+        raise ValueError("compute_irtr_recall needs a model built with loss_names['irtr'] > 0 (rank_output)")
+    dev = eng.device
+    cfg = pl_module.hparams.config
+    mlm = None
+    if text_dset is None or image_dset is None:
+        dm = pl_module.trainer.datamodule.dms[0]
+        mlm = getattr(dm, "mlm_collator", None)
+        if text_dset is None:
+            text_dset = dm.make_no_false_val_dset(max_num=500)
+            text_dset.tokenizer = dm.tokenizer
+        if image_dset is None:
+            image_dset = dm.make_no_false_val_dset(image_only=True, max_num=500)
+            image_dset.tokenizer = dm.tokenizer
+    ids, msks, tiids = [], [], []
+    for b in _irtr_batches(text_dset, list(range(len(text_dset))), 64, mlm):
+        ids.append(b["text_ids"].to(dev))
+        msks.append(b["text_masks"].to(dev))
+        tiids += [int(i) for i in b["img_index"]]
+    text_ids, text_masks = torch.cat(ids).to(torch.int64), torch.cat(msks).to(torch.int64)
+    dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
+    world, rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if dist_on else (1, 0)
+    mine = irtr_rank_split(len(image_dset), world, rank)
+    per_image, iids = [], []
+    for b in _irtr_batches(image_dset, mine, 1, mlm):
+        ie, im, _, _ = pl_module.visual_embed(b["image"][0].to(dev), max_image_len=cfg["max_image_len"], mask_it=False)
+        per_image.append((ie, im))
+        iids.append(int(b["img_index"][0]))
+    counts = [int(ie.shape[1]) - 1 for ie, _ in per_image]
+    n_max = max(counts)
+    if world > 1:
+        # every rank sees the longest image of the WHOLE split: all of them raise below, none is left waiting in the gather
+        longest = torch.tensor([n_max], dtype=torch.int64, device=dev)
+        torch.distributed.all_reduce(longest, op=torch.distributed.ReduceOp.MAX)
+        n_max = int(longest)
+    # the token limit is checked HERE, on the whole image cache, before the first pair is scored
+    if eng.dtype == L.BF16 and n_max + 1 + int(cfg["max_text_len"]) > 256:
+        raise eng.token_limit_error(n_max)
+    embeds = torch.zeros(len(per_image), n_max + 1, int(cfg["hidden_size"]), dtype=torch.float32, device=dev)
+    masks = torch.zeros(len(per_image), n_max + 1, dtype=torch.int32, device=dev)
+    for i, (ie, im) in enumerate(per_image):
+        embeds[i, : ie.shape[1]] = ie[0]
+        masks[i, : im.shape[1]] = im[0].to(torch.int32)
+    del per_image
+    scores = irtr_score_matrix(pl_module, embeds, masks, counts, text_ids, text_masks, int(tile_images), int(tile_texts))
+    iids_t = torch.tensor(iids, dtype=torch.int64, device=dev)
+    if world > 1:
+        torch.distributed.barrier()
+        parts = [torch.empty_like(scores) for _ in range(world)]
+        iparts = [torch.empty_like(iids_t) for _ in range(world)]
+        torch.distributed.all_gather(parts, scores)
+        torch.distributed.all_gather(iparts, iids_t)
+        scores, iids_t = torch.cat(parts), torch.cat(iparts)
+    tiids_t = torch.tensor(tiids, dtype=torch.int64, device=dev)
+    rec = irtr_recall_from_scores(scores, iids_t, tiids_t)
+    return rec + (scores, iids_t, tiids_t) if return_scores else rec

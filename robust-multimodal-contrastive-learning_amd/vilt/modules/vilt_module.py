@@ -79,6 +79,11 @@ class ViLTransformerSS(nn.Module):
         super().__init__()
         self.hparams = types.SimpleNamespace(config=config)
         self.config = config
+        if config["loss_names"].get("irtr_attacked", 0) > 0:
+            # PGDAttack_irtr.pgd_attack reads the undefined name `text_representation` (pgd_attack_vilt.py:391): the reference has no
+            # arithmetic an attacked IRTR step (or compute_attacked_irtr_recall / GreedyAttack_irtr) could be pinned to
+            raise NotImplementedError("loss_names['irtr_attacked'] > 0: the reference's PGDAttack_irtr.pgd_attack reads the undefined name "
+                                      "`text_representation` (attack/pgd_attack_vilt.py:391), so there is nothing to reproduce; use loss_names['irtr']")
         self.engine = Engine(config, device, compute_dtype, exact, pgd_dtype)
         eng = self.engine
         if config.get("ln_fold") is False:
@@ -92,9 +97,22 @@ class ViLTransformerSS(nn.Module):
                 continue
             if name.startswith("moco_head") and config["loss_names"].get("moco", 0) <= 0:
                 continue
+            if name.startswith("itm_score") and eng.irtr:
+                # vilt_module.py:237-239: the ITM head is frozen in an IRTR model (its row 1 still moves: rank_output below IS that row)
+                _attach(self, name, nn.Parameter(eng.view(eng.q32, off, shape), requires_grad=False))
+                continue
             p = nn.Parameter(eng.view(eng.q32, off, shape))
             p.grad = eng.view(eng.g32, off, shape)
             _attach(self, name, p)
+        for name, off, shape in eng.alias_specs:
+            # rank_output = Linear(D, 1) whose weight / bias are VIEWS of row 1 of itm_score.fc (vilt_module.py:233-236): same storage, so
+            # an optimizer step on rank_output moves itm_score.fc.weight[1] and the state dict holds both
+            if config["loss_names"].get("itm", 0) <= 0:
+                raise ValueError("loss_names['irtr'] > 0 needs loss_names['itm'] > 0: rank_output is row 1 of itm_score.fc (vilt_module.py:233-236)")
+            p = nn.Parameter(eng.view(eng.q32, off, shape))
+            p.grad = eng.view(eng.g32, off, shape)
+            _attach(self, name, p)
+        self.transformer.visual_embed = self.visual_embed                # the reference's pl_module.transformer.visual_embed
         self.init_weights()
         if config["loss_names"].get("moco", 0) > 0:
             self.multimodal = config.get("Multimodal", True)
@@ -201,7 +219,9 @@ class ViLTransformerSS(nn.Module):
             raise RuntimeError("Error(s) in loading state_dict: " + "; ".join(f"size mismatch for {k}: checkpoint {a}, model {b}" for k, a, b in wrong))
         # downstream heads exist only AFTER the training-time load in the reference (vilt_module.py:134-160 loads, :164 builds the VQA
         # head): a checkpoint's vqa_classifier.* keep their init unless test_only (:254-268 loads after the heads were built)
-        late = () if self.hparams.config.get("test_only", False) else ("vqa_classifier.", "nlvr2_classifier.")
+        # rank_output likewise (:233-236, built after the load as a view of the loaded itm_score row 1); under test_only the file's own
+        # rank_output.* load after itm_score.* (module order), so they win on row 1
+        late = () if self.hparams.config.get("test_only", False) else ("vqa_classifier.", "nlvr2_classifier.", "rank_output.")
         take = {k: v for k, v in state_dict.items() if k in mine and not k.startswith(late)}
         tt = take.pop("token_type_embeddings.weight", None) if nl3 else None
         res = self.load_state_dict(take, strict=False)
@@ -343,7 +363,7 @@ class ViLTransformerSS(nn.Module):
         if mask_text or mask_image:
             raise NotImplementedError("MLM/MPP masking is outside the RMCL hot path")
         if image_embeds is not None or image_masks is not None:
-            raise NotImplementedError("image_embeds shortcut is not on the RMCL hot path")
+            return self._infer_embeds(batch, key, image_token_type_idx, image_embeds, image_masks)
         if image_token_type_idx not in (1, 2):
             raise NotImplementedError(f"image_token_type_idx={image_token_type_idx}: only 1 and 2 (NLVR2) exist")
         eng = self.engine
@@ -414,6 +434,55 @@ class ViLTransformerSS(nn.Module):
             ret["text_labels"] = batch.get("text_labels")
         return ret
 
+    def _infer_embeds(self, batch, key, image_token_type_idx, image_embeds, image_masks):
+        """infer(batch, image_embeds=..., image_masks=...) (vilt_module.py:296-313): the image tokens are a visual_embed output instead
+        of pixels.  Inference only, like every use the reference makes of it (compute_irtr_recall, under no_grad)."""
+        if key:
+            raise NotImplementedError("infer_k(image_embeds=...) is not built (the reference never calls it)")
+        if torch.is_grad_enabled():
+            raise ValueError("infer(image_embeds=..., image_masks=...) runs only under torch.no_grad(): the cached rank pass keeps no "
+                             "activations for a backward (the reference uses this shortcut in compute_irtr_recall only, under no_grad)")
+        if image_embeds is None or image_masks is None:
+            raise ValueError("infer: image_embeds and image_masks must be given together")
+        if image_token_type_idx != 1:
+            raise NotImplementedError("infer(image_embeds=...): only image_token_type_idx=1")
+        eng = self.engine
+        eng.dropout_on = False
+        text_ids, text_masks = batch["text_ids"], batch["text_masks"]
+        B = int(text_ids.shape[0])
+        if image_embeds.dim() != 3 or image_embeds.shape[0] != B or tuple(image_masks.shape) != tuple(image_embeds.shape[:2]):
+            raise ValueError(f"infer: image_embeds [B, 1 + n, D] / image_masks [B, 1 + n] expected for {B} texts (got {tuple(image_embeds.shape)}, "
+                             f"{tuple(image_masks.shape)})")
+        if B > 1 and image_embeds.stride(0) == 0 and image_masks.stride(0) == 0:
+            # one image expanded over the batch (compute_irtr_recall's `_ie.expand(fblen, l, c)`): one cache slot, every sequence names it
+            emb, msk = image_embeds[:1], image_masks[:1]
+            img_of = torch.zeros(B, dtype=torch.int32, device=eng.device)
+        else:
+            emb, msk = image_embeds, image_masks
+            img_of = torch.arange(B, dtype=torch.int32, device=eng.device)
+        emb = emb.to(eng.device, torch.float32).contiguous()
+        msk = msk.to(eng.device, torch.int32).contiguous()
+        n = int(emb.shape[1]) - 1
+        rp = eng.rank_forward(text_ids, text_masks, emb, msk, img_of, n, cls_tail=False)
+        d = rp.d
+        x = rp.xn.view(B, d.L + 1 + d.P, d.D)
+        return {
+            "text_feats": x[:, : d.L].clone(), "image_feats": x[:, d.L:].clone(), "cls_feats": rp.cls.clone(), "raw_cls_feats": x[:, 0].clone(),
+            "image_labels": None, "image_masks": rp.co_mask[:, d.L:].to(torch.int64), "text_labels": batch.get("text_labels"),
+            "text_ids": text_ids, "text_masks": text_masks, "patch_index": None,
+        }
+
+    @torch.no_grad()
+    def visual_embed(self, images, max_image_len=None, mask_it=False, select=None):
+        """VisionTransformer.visual_embed (vision_transformer.py:559-677) as the reference's compute_irtr_recall calls it: patch embedding
+        + resized position rows + cls token, WITHOUT the token-type row.  Returns (image_embeds [B, 1 + n, D] fp32, image_masks [B, 1 + n],
+        (patch_index, (H, W)), None).  max_image_len None: the config's.  select: the caller's patch draw (parity tests)."""
+        if mask_it:
+            raise NotImplementedError("visual_embed(mask_it=True) (MPP masking) is outside the RMCL hot path")
+        emb, msk, patch_index = self.engine.visual_embed(images, max_image_len=max_image_len, select=select)
+        ps = self.config["patch_size"]
+        return emb, msk, (patch_index, (int(images.shape[2]) // ps, int(images.shape[3]) // ps)), None
+
     def _infer_slot_take(self) -> int:
         for slot in range(self.MAX_PENDING_INFER):
             if slot not in self._infer_busy:
@@ -426,7 +495,7 @@ class ViLTransformerSS(nn.Module):
         """vilt_module.py:275-351.  Differentiable like the reference's when autograd is on (``text_feats`` / ``image_feats`` /
         ``cls_feats`` / ``raw_cls_feats`` back-propagate into every query parameter's ``.grad``); ``torch.no_grad()`` gives the
         stash-free inference pass.  The ``image_embeds`` shortcut (pre-computed visual_embed output, used by the reference's
-        downstream tasks only) is not built."""
+        downstream tasks only) runs under ``torch.no_grad()`` only (``_infer_embeds``)."""
         return self._infer(batch, False, mask_text, mask_image, image_token_type_idx, image_embeds, image_masks)
 
     @torch.no_grad()
@@ -454,7 +523,9 @@ class ViLTransformerSS(nn.Module):
             ret.update(objectives.compute_nlvr2(self, batch))
         if "nlvr2_attacked" in self.current_tasks:
             ret.update(objectives.compute_nlvr2_attack(self, batch))
-        unsupported = [t for t in self.current_tasks if t not in ("itm", "moco", "barlowtwins", "vqa", "vqa_attacked", "nlvr2", "nlvr2_attacked")]
+        if "irtr" in self.current_tasks:
+            ret.update(objectives.compute_irtr(self, batch))
+        unsupported = [t for t in self.current_tasks if t not in ("itm", "moco", "barlowtwins", "vqa", "vqa_attacked", "nlvr2", "nlvr2_attacked", "irtr")]
         if unsupported:
             raise NotImplementedError(f"tasks {unsupported} are outside the RMCL hot path (SURVEY 8)")
         return ret

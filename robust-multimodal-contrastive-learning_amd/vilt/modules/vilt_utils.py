@@ -31,8 +31,40 @@ def epoch_wrapup(pl_module):
     phase = "train" if pl_module.training else "val"
     out = {k: (float(v) if torch.is_tensor(v) and v.numel() == 1 else v) for k, v in pl_module.logged.items()}
     pl_module.logged = {}
+    if pl_module.hparams.config.get("get_recall_metric", False) and not pl_module.training:
+        # vilt_utils.py:90-97: image-text retrieval recalls at the end of a validation / test epoch; ir_r1 + tr_r1 joins the_metric.
+        # The datasets come from pl_module.irtr_eval_dsets = (text_dset, image_dset) when set, else from the trainer's datamodule
+        from . import objectives
+        text_dset, image_dset = getattr(pl_module, "irtr_eval_dsets", None) or (None, None)
+        rec = objectives.compute_irtr_recall(pl_module, text_dset, image_dset)
+        for name, v in zip(("ir_r1", "ir_r5", "ir_r10", "tr_r1", "tr_r5", "tr_r10"), rec):
+            out[f"recalls/{name}"] = float(v)
+        out["the_metric"] = out.get("the_metric", 0.0) + out["recalls/ir_r1"] + out["recalls/tr_r1"]
     pl_module.last_epoch_metrics = {"phase": phase, **out}
     return pl_module.last_epoch_metrics
+
+
+def adamw_segments(specs, total, wd, lr_mult, irtr=False):
+    """(segment ends, learning-rate multipliers, weight decays) of the fused AdamW over the arena: one segment per parameter tensor
+    (vilt_utils.py:335-393: no decay for biases / LayerNorm, lr x lr_mult for the heads in HEAD_NAMES).  irtr (vilt_module.py:233-239):
+    the ITM head is frozen, so row 0 of its weight takes no step and no weight decay (a parameter without a gradient is skipped by
+    AdamW); row 1 IS rank_output.weight - not in head_names: base learning rate, decayed.  itm_score.fc.bias needs no split: biases
+    are not decayed and bias[0] never receives a gradient (m = v = 0: no step)."""
+    ends, mults, wds = [], [], []
+    specs = sorted(specs, key=lambda s: s[1])
+    for i, (name, off, shape) in enumerate(specs):
+        end = specs[i + 1][1] if i + 1 < len(specs) else total
+        decay = not any(nd in name for nd in NO_DECAY)
+        head = any(bb in name for bb in HEAD_NAMES)
+        if irtr and name == "itm_score.fc.weight":
+            ends += [off + int(shape[1]), end]
+            mults += [0.0, 1.0]
+            wds += [0.0, wd]
+            continue
+        ends.append(end)
+        mults.append(lr_mult if head else 1.0)
+        wds.append(wd if decay else 0.0)
+    return ends, mults, wds
 
 
 class FusedAdamW:
@@ -46,15 +78,7 @@ class FusedAdamW:
         self.m = torch.zeros_like(eng.q32)
         self.v = torch.zeros_like(eng.q32)
         self.t = 0
-        ends, mults, wds = [], [], []
-        specs = sorted(eng.specs, key=lambda s: s[1])
-        for i, (name, off, shape) in enumerate(specs):
-            end = specs[i + 1][1] if i + 1 < len(specs) else eng.total
-            decay = not any(nd in name for nd in NO_DECAY)
-            head = any(bb in name for bb in HEAD_NAMES)
-            ends.append(end)
-            mults.append(lr_mult if head else 1.0)
-            wds.append(wd if decay else 0.0)
+        ends, mults, wds = adamw_segments(eng.specs, eng.total, wd, lr_mult, eng.irtr)
         dev = eng.device
         self.seg_end = torch.tensor(ends, dtype=torch.int64, device=dev)
         self.seg_mult = torch.tensor(mults, dtype=torch.float32, device=dev)
