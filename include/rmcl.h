@@ -320,6 +320,44 @@ int rmcl_vqa_head_backward(const rmcl_vqa_head* h, const float* params, float* s
 int rmcl_nlvr2_ce(const float* logits, int ldl, const int32_t* labels, int B, int N, float grad_scale, const float* grad_scale_dev,
                   float* dz, float* rows, int32_t* argmax, const float* logits_ref, int ld_ref, float* stats, void* stream);
 
+/* ---- Masked language modelling (task_mlm_itm) ---------------------------------------------------------------------------
+ * mlm_score (heads.py:183-195, vilt_module.py:56): transform = Linear(D,D) - GELU (exact erf) - LayerNorm(D, eps 1e-12), then
+ * decoder = Linear(D, V, no bias) + bias [V]; loss = cross_entropy over the rows whose label is not -100 (objectives.py:604-630).
+ * tw [D,D], tb [D], lg / lb [D] (LayerNorm), dw [V,D] (decoder.weight, NOT tied to the word embeddings), db [V] (mlm_score.bias):
+ * element offsets in ONE fp32 arena (parameters and, at the same offsets, gradients).  D in {256, 768}.
+ * The training path runs on the COMPACTED rows with a label and never holds a [rows, V] logits tensor; `rows` below is the launch
+ * extent of the compacted buffers: a multiple of 128 that is >= the number n of rows with a label (n itself stays on the device).
+ * dtype: operand type of the decoder products - RMCL_BF16 (h in bf16, W = the bf16 shadow arena params_lp at the same offset) or
+ * RMCL_F32 (fp32 operands, params_lp may be NULL); accumulation and the softmax statistics are fp32; the transform is exact fp32.
+ * Nothing here uses float atomics: every output has one owner and a fixed summation order (two identical calls: identical bits). */
+typedef struct rmcl_mlm_head {
+  int32_t D, V;
+  int64_t tw, tb, lg, lb, dw, db;
+} rmcl_mlm_head;
+/* floats of the workspace `ws` shared by forward / backward / logits for this launch extent (monotone in rows) */
+int64_t rmcl_mlm_ws_floats(const rmcl_mlm_head* h, int rows);
+/* labels [M = B L] int64 -> idx [M] int32: row b * N + l of xn [B N, D] for the j-th position (ascending) whose label lies in [0, V);
+ * lab [M] its label; count [1] = n.  Entries behind n: idx -1, lab -100.  Any other label (-100, or outside [0, V): callers validate
+ * on the host) is skipped.  all_rows = 1: every position is listed (the dense-logits pass), lab keeps -100 where there is no label. */
+int rmcl_mlm_compact(const int64_t* labels, int M, int L, int N, int V, int all_rows, int32_t* idx, int32_t* lab, int32_t* count, void* stream);
+/* WT [D, ldv] in `dtype` = decoder.weight^T of the fp32 masters, ldv = V rounded up to 128 (pad columns zero): the operand of dh = dz W */
+int rmcl_mlm_weight_transpose(const rmcl_mlm_head* h, const float* params, void* WT, int dtype, void* stream);
+/* gather xn[idx] -> transform -> fused decoder + cross-entropy.  Per compacted row r < n: lse[r], rowloss[r] = lse - z[label], argmax[r]
+ * (first maximum); rows >= n: 0 / 0 / -1.  stats [3] = (sum rowloss / n, rows with argmax == label, n); n = 0 gives a NaN loss like
+ * F.cross_entropy over an all-ignored batch.  `ws` keeps what the backward / the logits writer need. */
+int rmcl_mlm_forward(const rmcl_mlm_head* h, const float* params, const void* params_lp, int dtype, const float* xn, const int32_t* idx,
+                     const int32_t* lab, const int32_t* count, int rows, float* ws, float* lse, float* rowloss, int32_t* argmax, float* stats,
+                     void* stream);
+/* dz = grad_scale s (softmax(z) - onehot) / n recomputed from ws and lse (s = *grad_scale_dev, the incoming gradient read on the device,
+ * or 1 when NULL); G != NULL: every head gradient is ACCUMULATED into G at the head's offsets; dxn != NULL: the gradient of the gathered
+ * rows is stored to dxn[idx[r]] (dxn [B N, D] zero-filled by the caller).  n = 0 leaves G's decoder slots and dxn untouched. */
+int rmcl_mlm_backward(const rmcl_mlm_head* h, const float* params, const void* params_lp, const void* WT, int dtype, const int32_t* idx,
+                      const int32_t* lab, const int32_t* count, int rows, float* ws, const float* lse, float grad_scale,
+                      const float* grad_scale_dev, float* G, float* dxn, void* stream);
+/* logits [rows_out, ldl] (V columns written) of the first rows_out compacted rows of the last rmcl_mlm_forward on `ws` */
+int rmcl_mlm_logits(const rmcl_mlm_head* h, const float* params, const void* params_lp, int dtype, float* ws, int rows, int rows_out,
+                    float* logits, int64_t ldl, void* stream);
+
 /* One joint text+image encoder forward up to transformer.norm: replaces ViLTransformerSS.infer /
  * infer_k (vilt_module.py:275-418) minus the pooler.  params32: fp32 arena; params_lp: bf16
  * shadow arena (NULL when dtype is F32).  text_ids/text_mask [B,L] int64; patches [B*P,patch_k]

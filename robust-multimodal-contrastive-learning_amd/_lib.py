@@ -59,6 +59,12 @@ class VqaHead(C.Structure):
                 ("w0", C.c_int64), ("b0", C.c_int64), ("g1", C.c_int64), ("b1", C.c_int64), ("w3", C.c_int64), ("b3", C.c_int64)]
 
 
+class MlmHead(C.Structure):
+    """include/rmcl.h rmcl_mlm_head: widths of mlm_score and the arena offsets of its six tensors."""
+    _fields_ = [("D", C.c_int32), ("V", C.c_int32),
+                ("tw", C.c_int64), ("tb", C.c_int64), ("lg", C.c_int64), ("lb", C.c_int64), ("dw", C.c_int64), ("db", C.c_int64)]
+
+
 class RankSrc(C.Structure):
     """include/rmcl.h rmcl_rank_src: the cache of visual_embed outputs a rank pass gathers its image tokens from (device pointers)."""
     _fields_ = [("embeds", C.c_void_p), ("masks", C.c_void_p), ("img_of", C.c_void_p), ("n_img", C.c_int32), ("ld_tok", C.c_int32)]
@@ -77,7 +83,7 @@ def _load():
     lib.rmcl_last_error.restype = C.c_char_p
     for name in ("rmcl_stash_bytes", "rmcl_workspace_bytes", "rmcl_heads_stash_bytes", "rmcl_infonce_ws_bytes",
                  "rmcl_attention_scratch_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats",
-                 "rmcl_vqa_stash_floats"):
+                 "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats"):
         getattr(lib, name).restype = C.c_int64
     return lib
 
@@ -98,6 +104,7 @@ EXPORTS = (
     "rmcl_vqa_stash_floats", "rmcl_vqa_head_forward", "rmcl_vqa_bce", "rmcl_vqa_targets_dense", "rmcl_vqa_head_backward",
     "rmcl_nlvr2_ce",
     "rmcl_visual_embed", "rmcl_encoder_forward_rank", "rmcl_irtr_score", "rmcl_irtr_ce", "rmcl_irtr_bwd",
+    "rmcl_mlm_ws_floats", "rmcl_mlm_compact", "rmcl_mlm_weight_transpose", "rmcl_mlm_forward", "rmcl_mlm_backward", "rmcl_mlm_logits",
 )
 
 

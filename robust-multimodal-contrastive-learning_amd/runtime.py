@@ -212,6 +212,44 @@ class Nlvr2Buffers:
         self.labels = torch.empty(B, dtype=torch.int32, device=eng.device)
 
 
+def mlm_layout(cfg: dict, base: int):
+    """mlm_score (heads.py:183-195, built WITHOUT a tied weight at vilt_module.py:56: decoder.weight [vocab, D] is a parameter of its
+    own) appended to the parameter arena at element offset `base`: returns (rmcl_mlm_head struct, specs, elements used)."""
+    D, V = int(cfg["hidden_size"]), int(cfg["vocab_size"])
+    n = "mlm_score."
+    shapes = [("tw", n + "transform.dense.weight", (D, D)), ("tb", n + "transform.dense.bias", (D,)),
+              ("lg", n + "transform.LayerNorm.weight", (D,)), ("lb", n + "transform.LayerNorm.bias", (D,)),
+              ("dw", n + "decoder.weight", (V, D)), ("db", n + "bias", (V,))]
+    off, offs, specs = base, {}, []
+    for key, name, shape in shapes:
+        offs[key] = off
+        specs.append((name, off, shape))
+        cnt = 1
+        for v in shape:
+            cnt *= v
+        off += (cnt + 63) // 64 * 64
+    return L.MlmHead(D=D, V=V, **offs), specs, off - base
+
+
+class MlmBuffers:
+    """Per-(batch, tag) buffers of the MLM head for M = B x L text positions: the compaction (row list, labels, device-side count),
+    the per-row outputs and the workspace the forward leaves for the backward.  ``rows``: launch extent of the compacted buffers for
+    the bound batch (a multiple of 128 >= the number of labelled rows)."""
+
+    def __init__(self, eng: "Engine", B: int):
+        dev = eng.device
+        self.B, self.L = B, int(eng.cfg["max_text_len"])
+        self.M = B * self.L
+        self.cap = (self.M + 127) // 128 * 128
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
+        self.idx, self.lab, self.count = i32(self.cap), i32(self.cap), i32(1)
+        self.lse, self.rowloss, self.argmax = f32(self.cap), f32(self.cap), i32(self.cap)
+        self.ws = f32(int(lib.rmcl_mlm_ws_floats(C.byref(eng.mlm), self.cap)))
+        self.rows = self.cap
+        self.labels = None                                      # the bound [B, L] int64 labels on the device
+
+
 class PassBuffers:
     """Everything sized by the per-GPU batch B (allocated once, reused every step)."""
 
@@ -381,6 +419,14 @@ class Engine:
             self.nlvr2, self.nlvr2_specs, n_nl = nlvr2_layout(cfg, int(lay.total) + extra)
             extra += n_nl
             self._nlvr2_bufs = {}
+        # optional MLM head (loss_names["mlm"] > 0): behind the other heads; a model without it keeps its arena size and specs
+        self.mlm, self.mlm_specs = None, []
+        if ln.get("mlm", 0) > 0:
+            self.mlm, self.mlm_specs, n_mlm = mlm_layout(cfg, int(lay.total) + extra)
+            extra += n_mlm
+            self._mlm_bufs = {}
+            self.mlm_wT = None                                  # decoder.weight^T in the operand type (rmcl_mlm_weight_transpose)
+            self.mlm_wt_stale = True
         # IRTR (loss_names["irtr"] > 0): rank_output.weight / .bias ARE row 1 of the ITM head's slots (vilt_module.py:233-239 makes them
         # views of itm_score.fc): no arena space of their own; `specs` keeps its entries, the aliases are listed apart
         self.irtr = is_irtr(cfg)
@@ -404,7 +450,7 @@ class Engine:
         # transposed bf16 shadows of the layer weights for the data-gradient GEMMs (include/rmcl.h rmcl_weight_transpose_bf16)
         self.q_lpT = z(lay.total, torch.bfloat16) if (self.dtype == L.BF16 and os.environ.get("RMCL_NO_WT", "0") != "1") else None
         self.lpT_stale = True
-        self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs + self.nlvr2_specs
+        self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs + self.nlvr2_specs + self.mlm_specs
         self._bufs: Dict[tuple, PassBuffers] = {}
         self.lp_stale = True
         self.drop_p = float(cfg.get("drop_rate", 0.0))
@@ -515,6 +561,7 @@ class Engine:
         self.lp_stale = False
         self.fold_stale = {"q": True, "k": True}
         self.lpT_stale = True
+        self.mlm_wt_stale = True
 
     def weights_T(self):
         """transposed bf16 weight shadows of the query arena (None: the backward reads the weights as stored)"""
@@ -1006,6 +1053,67 @@ class Engine:
         check(lib.rmcl_vqa_head_backward(C.byref(self.nlvr2), P(self.q32), P(nb.stash), P(dz), nb.B, P(self.g32 if with_grads else None),
                                          P(nb.dcls), stream_ptr()), "nlvr2_head_backward")
         return nb.dcls
+
+    # ---- MLM head (include/rmcl.h rmcl_mlm_*) ------------------------------------------------------------------------
+    def mlm_bufs(self, B: int, tag: str) -> MlmBuffers:
+        if (B, tag) not in self._mlm_bufs:
+            self._mlm_bufs[(B, tag)] = MlmBuffers(self, B)
+        return self._mlm_bufs[(B, tag)]
+
+    def mlm_weights_T(self) -> torch.Tensor:
+        """decoder.weight^T [D, vocab rounded up to 128] in the engine's operand type, re-derived when the masters changed"""
+        if self.lp_stale:
+            self.refresh_shadows()
+        if self.mlm_wT is None:
+            ldv = (self.mlm.V + 127) // 128 * 128
+            self.mlm_wT = torch.empty(self.mlm.D, ldv, dtype=torch.bfloat16 if self.dtype == L.BF16 else torch.float32, device=self.device)
+        if self.mlm_wt_stale:
+            check(lib.rmcl_mlm_weight_transpose(C.byref(self.mlm), P(self.q32), P(self.mlm_wT), self.dtype, stream_ptr()), "mlm_weight_transpose")
+            self.mlm_wt_stale = False
+        return self.mlm_wT
+
+    def mlm_bind(self, mb: MlmBuffers, labels: torch.Tensor, N: int, all_rows: bool = False) -> MlmBuffers:
+        """Validates ``text_labels_mlm`` [B, L] (a label other than -100 outside [0, vocab_size) is a ValueError here, on the host - never
+        a device fault) and builds the compaction on the device.  Labels that arrive on the host (a DataLoader's batch) are checked and
+        counted there for free, and the count only sizes the launches; labels already on the device cost one read-back of two scalars.
+        N: token rows per sample of the xn the rows will be gathered from.  all_rows: list every position (the dense-logits pass)."""
+        V = self.mlm.V
+        if tuple(labels.shape) != (mb.B, mb.L):
+            raise ValueError(f"text_labels_mlm must be [B, max_text_len] = {(mb.B, mb.L)} (got {tuple(labels.shape)})")
+        lab = labels.to(torch.int64)
+        on = lab != -100
+        bad = on & ((lab < 0) | (lab >= V))
+        n_bad, n = (int(v) for v in torch.stack([bad.sum(), on.sum()]).tolist())
+        if n_bad:
+            raise ValueError(f"text_labels_mlm: {n_bad} label(s) outside [0, {V}) (vocab_size) other than the ignore index -100")
+        mb.labels = lab.to(self.device).contiguous()
+        mb.rows = mb.cap if all_rows else min(mb.cap, max(128, (n + 127) // 128 * 128))
+        check(lib.rmcl_mlm_compact(P(mb.labels), mb.M, mb.L, int(N), V, int(all_rows), P(mb.idx), P(mb.lab), P(mb.count), stream_ptr()),
+              "mlm_compact")
+        return mb
+
+    def mlm_forward(self, mb: MlmBuffers, xn: torch.Tensor, stats: torch.Tensor = None) -> torch.Tensor:
+        """stats = (mlm_loss, rows with argmax == label, n) of the bound batch; per compacted row mb.lse / .rowloss / .argmax."""
+        if self.lp_stale:
+            self.refresh_shadows()
+        stats = torch.empty(3, dtype=torch.float32, device=self.device) if stats is None else stats
+        check(lib.rmcl_mlm_forward(C.byref(self.mlm), P(self.q32), P(self.q_lp), self.dtype, P(xn), P(mb.idx), P(mb.lab), P(mb.count), mb.rows,
+                                   P(mb.ws), P(mb.lse), P(mb.rowloss), P(mb.argmax), P(stats), stream_ptr()), "mlm_forward")
+        return stats
+
+    def mlm_backward(self, mb: MlmBuffers, grad_scale: float, scale_dev: torch.Tensor, dxn: torch.Tensor, with_grads: bool = True):
+        """CE gradient (recomputed) -> decoder -> transform -> stored into the zero-filled dxn [B N, D]; head gradients into the arena."""
+        wT = self.mlm_weights_T()
+        check(lib.rmcl_mlm_backward(C.byref(self.mlm), P(self.q32), P(self.q_lp), P(wT), self.dtype, P(mb.idx), P(mb.lab), P(mb.count), mb.rows,
+                                    P(mb.ws), P(mb.lse), F(grad_scale), P(scale_dev), P(self.g32 if with_grads else None), P(dxn),
+                                    stream_ptr()), "mlm_backward")
+
+    def mlm_logits(self, mb: MlmBuffers, rows_out: int) -> torch.Tensor:
+        """dense logits [rows_out, vocab] of the first rows_out compacted rows of the last mlm_forward on `mb`"""
+        out = torch.empty(rows_out, self.mlm.V, dtype=torch.float32, device=self.device)
+        check(lib.rmcl_mlm_logits(C.byref(self.mlm), P(self.q32), P(self.q_lp), self.dtype, P(mb.ws), mb.rows, rows_out, P(out), I64(self.mlm.V),
+                                  stream_ptr()), "mlm_logits")
+        return out
 
     # ---- IRTR: rank head, visual_embed, the cached rank pass (include/rmcl.h "Image-text retrieval") ------------------------------------
     def rank_params(self, arena: torch.Tensor = None):

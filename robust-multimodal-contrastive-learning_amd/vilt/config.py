@@ -167,3 +167,24 @@ def task_finetune_irtr_f30k_randaug(**over):
     )
     cfg.update(over)
     return cfg
+
+
+def task_mlm_itm(**over):
+    """reference config.py:202-209: ViLT pre-training, masked language modelling + image-text matching (the objective that produced
+    vilt_200k_mlm_itm.ckpt).  The reference's own `datasets` line keeps COCO only (the four-dataset list is commented out there)."""
+    cfg = default_config(
+        exp_name="mlm_itm", datasets=["coco"], loss_names=_loss_names({"itm": 1, "mlm": 1}), batch_size=4096, max_epoch=10,
+        max_image_len=200,
+    )
+    cfg.update(over)
+    return cfg
+
+
+def task_mlm_itm_randaug(**over):
+    """reference config.py:212-220 (the RandAugment train transform itself is the caller's)."""
+    cfg = default_config(
+        exp_name="mlm_itm_randaug", datasets=["coco", "vg", "sbu", "gcc"], train_transform_keys=["pixelbert_randaug"],
+        loss_names=_loss_names({"itm": 1, "mlm": 1}), batch_size=4096, max_epoch=10, max_image_len=200,
+    )
+    cfg.update(over)
+    return cfg

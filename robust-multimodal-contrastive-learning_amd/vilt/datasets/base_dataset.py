@@ -33,6 +33,39 @@ def default_collator(max_text_len: int = 40, pad_id: int = 0) -> Callable:
     return pad
 
 
+def masking_collator(mask_id: int, vocab_size: int, special_ids=(), mlm_prob: float = 0.15, max_text_len: int = 40, pad_id: int = 0,
+                     generator: Optional[torch.Generator] = None, whole_word_masking: bool = False) -> Callable:
+    """The masked-LM collator of the reference's datamodule (datamodule_base.py:57-65: HF ``DataCollatorForLanguageModeling``, BERT
+    rule): every token that is neither special (``special_ids``: [CLS], [SEP], ...) nor padding is chosen with probability
+    ``mlm_prob``; of the chosen, 80 % become ``mask_id``, 10 % a uniformly random id of [0, vocab_size), 10 % stay; ``labels`` hold the
+    original id on the chosen positions and -100 everywhere else.  ``generator`` makes the draw reproducible (the random stream is
+    this function's own, not HF's).  Whole-word masking is not built."""
+    if whole_word_masking:
+        raise NotImplementedError("whole_word_masking=True (DataCollatorForWholeWordMask) is not built")
+    if not 0.0 <= mlm_prob <= 1.0:
+        raise ValueError(f"mlm_prob must lie in [0, 1] (got {mlm_prob})")
+    special = torch.tensor(sorted({int(pad_id), *[int(i) for i in special_ids]}), dtype=torch.int64)
+    pad = default_collator(max_text_len, pad_id)
+
+    def mask(encodings: List[dict]) -> Dict[str, torch.Tensor]:
+        ids = pad(encodings)["input_ids"]
+        valid = torch.zeros_like(ids, dtype=torch.bool)
+        for row, enc in zip(valid, encodings):
+            row[: min(len(enc["input_ids"]), max_text_len)] = True
+        free = valid & ~torch.isin(ids, special)
+        u = torch.rand(ids.shape, generator=generator)
+        chosen = free & (u < mlm_prob)
+        kind = torch.rand(ids.shape, generator=generator)
+        rand_ids = torch.randint(0, vocab_size, ids.shape, generator=generator, dtype=torch.int64)
+        labels = torch.where(chosen, ids, torch.full_like(ids, -100))
+        out = ids.clone()
+        out[chosen & (kind < 0.8)] = mask_id
+        swap = chosen & (kind >= 0.8) & (kind < 0.9)
+        out[swap] = rand_ids[swap]
+        return {"input_ids": out, "labels": labels}
+    return mask
+
+
 def _stack_views(per_sample: List[List[torch.Tensor]], hmax: int, wmax: int) -> List[torch.Tensor]:
     """[sample][view] tensors [3, h, w]  ->  [view] tensors [B, 3, hmax, wmax], zero padded bottom / right."""
     n_views = len(per_sample[0])

@@ -198,6 +198,53 @@ def compute_itm_wpa(pl_module, batch):
     return ret
 
 
+def compute_mlm(pl_module, batch):
+    """objectives.compute_mlm (:604-630): one FULL-mode encoder pass on the masked ids (no cls-only tail: the loss reads text rows), then
+    mlm_score and the cross-entropy over the positions whose label is not -100 - on those rows only, compacted, with the decoder and
+    the softmax fused (csrc/mlm.hip): no [B, L, vocab] logits tensor exists on the training path.  ``mlm_logits`` is the dense tensor
+    when config["mlm_return_logits"] is true or the call runs under no_grad in eval mode, else None (INTEGRATION.md "MLM")."""
+    eng = pl_module.engine
+    cfg = pl_module.hparams.config
+    if eng.mlm is None:
+        raise ValueError("compute_mlm needs a model built with loss_names['mlm'] > 0 (the mlm_score head)")
+    need_grad = torch.is_grad_enabled() and pl_module.training
+    ids, labels = batch["text_ids_mlm"], batch["text_labels_mlm"]
+    pb = eng.bind_batch(ids, batch["text_masks"], batch["image"][0], tag="mlm")
+    d = pb.d
+    N = d.L + 1 + d.P
+    mb = eng.mlm_bind(eng.mlm_bufs(pb.B, "mlm"), labels, N)                 # (validates the labels before anything is launched on them)
+    op = eng.make_operand(pb, out=pb.patchesT_full)
+    eng.encoder_forward(pb, key=False, mode=L.MODE_FULL if need_grad else L.MODE_INFER, patchesT=op)
+    stats = eng.mlm_forward(mb, pb.xn)                                      # (loss, correct rows, rows with a label), all on the device
+    value = _scalar(stats[0:1].clone())
+    if need_grad:
+        def backward(grad_out, pb=pb, mb=mb, op=op, N=N):
+            g = grad_out.to(torch.float32).reshape(1).contiguous()
+            dxn = torch.zeros(pb.B * N, pb.d.D, dtype=torch.float32, device=eng.device)
+            eng.mlm_backward(mb, 1.0, g, dxn, with_grads=True)
+            eng.encoder_backward(pb, L.MODE_FULL, op, dxn, cls_only=False, dpatches=None)
+            pl_module.after_backward()
+
+        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+    logits = None
+    if cfg.get("mlm_return_logits", False) or not (torch.is_grad_enabled() or pl_module.training):
+        ma = eng.mlm_bind(eng.mlm_bufs(pb.B, "mlm_dense"), labels, N, all_rows=True)
+        eng.mlm_forward(ma, pb.xn)
+        logits = eng.mlm_logits(ma, ma.M).view(pb.B, d.L, eng.mlm.V)
+    ret = {"mlm_loss": value, "mlm_logits": logits, "mlm_labels": labels, "mlm_ids": ids}
+    phase = "train" if pl_module.training else "val"
+    # Accuracy (gadgets/my_metrics.py:5-28): correct / total over the rows with a label, per step and accumulated over the epoch
+    acc = getattr(pl_module, "mlm_epoch_counts", None)
+    if acc is None:
+        acc = pl_module.mlm_epoch_counts = {}
+    if phase not in acc:
+        acc[phase] = torch.zeros(2, dtype=torch.float32, device=eng.device)
+    acc[phase] += stats[1:3]
+    pl_module.log(f"mlm/{phase}/loss", value.detach())
+    pl_module.log(f"mlm/{phase}/accuracy", stats[1] / stats[2])
+    return ret
+
+
 def compute_moco_contrastive(pl_module, batch):
     """objectives.py:217-447 (image view).  Returns {"moco_loss", pos_/neg_{dist,cosine,dot}_attacked_img}."""
     eng = pl_module.engine

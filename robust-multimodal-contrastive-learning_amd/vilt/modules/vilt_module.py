@@ -198,6 +198,16 @@ class ViLTransformerSS(nn.Module):
         # weights_only=True: executes nothing from the file (the reference uses a full unpickle, vilt_module.py:138)
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
         state_dict = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
+        if self.hparams.config["loss_names"].get("mlm", 0) > 0 and not self.hparams.config.get("test_only", False):
+            # MLM head from the 200k checkpoint when that file exists (:140-150; the reference fails without it, here the head of the
+            # loaded file - or the initialisation - stays)
+            for cand in ("models_weight/vilt_200k_mlm_itm.ckpt", "../models_weight/vilt_200k_mlm_itm.ckpt"):
+                if os.path.isfile(cand):
+                    c2 = torch.load(cand, map_location="cpu", weights_only=True)["state_dict"]
+                    for k in ("mlm_score.bias", "mlm_score.transform.dense.weight", "mlm_score.transform.dense.bias",
+                              "mlm_score.transform.LayerNorm.weight", "mlm_score.transform.LayerNorm.bias", "mlm_score.decoder.weight"):
+                        state_dict[k] = c2[k]
+                    break
         if self.hparams.config["loss_names"].get("itm", 0) > 0:          # ITM head from the 200k checkpoint (:152-159)
             for cand in ("models_weight/vilt_200k_mlm_itm.ckpt", "../models_weight/vilt_200k_mlm_itm.ckpt"):
                 if os.path.isfile(cand):
@@ -360,9 +370,11 @@ class ViLTransformerSS(nn.Module):
 
     # ---- inference API ---------------------------------------------------------------------
     def _infer(self, batch, key, mask_text, mask_image, image_token_type_idx, image_embeds, image_masks):
-        if mask_text or mask_image:
-            raise NotImplementedError("MLM/MPP masking is outside the RMCL hot path")
+        if mask_image:
+            raise NotImplementedError("MPP masking (mask_image=True) is outside the RMCL hot path")
         if image_embeds is not None or image_masks is not None:
+            if mask_text:
+                raise NotImplementedError("infer(mask_text=True, image_embeds=...) is not built (the reference never calls it)")
             return self._infer_embeds(batch, key, image_token_type_idx, image_embeds, image_masks)
         if image_token_type_idx not in (1, 2):
             raise NotImplementedError(f"image_token_type_idx={image_token_type_idx}: only 1 and 2 (NLVR2) exist")
@@ -372,7 +384,8 @@ class ViLTransformerSS(nn.Module):
             raise ValueError("image_token_type_idx=2 needs an NLVR2 model (loss_names nlvr2 / nlvr2_attacked: 3-row token_type_embeddings)")
         imgkey = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"   # vilt_module.py:284-287
         eng.dropout_on = self.training and eng.drop_p > 0
-        text_ids, text_masks = batch["text_ids"], batch["text_masks"]
+        do_mlm = "_mlm" if mask_text else ""                     # vilt_module.py:289-291: the masked ids and their labels
+        text_ids, text_masks = batch[f"text_ids{do_mlm}"], batch["text_masks"]
         # the reference's infer is an ordinary differentiable forward (vilt_module.py:275-351): with autograd on, the query pass keeps
         # the FULL stash and the returned features carry a backward into the gradient arena (the momentum pass never does: k_* get no
         # gradients, vilt_module.py:270-273)
@@ -431,7 +444,7 @@ class ViLTransformerSS(nn.Module):
         }
         if not key:
             ret["image_labels"] = None
-            ret["text_labels"] = batch.get("text_labels")
+            ret["text_labels"] = batch.get(f"text_labels{do_mlm}")
         return ret
 
     def _infer_embeds(self, batch, key, image_token_type_idx, image_embeds, image_masks):
@@ -509,6 +522,8 @@ class ViLTransformerSS(nn.Module):
         if len(self.current_tasks) == 0:
             ret.update(self.infer(batch))
             return ret
+        if "mlm" in self.current_tasks:                                   # first, like the reference (vilt_module.py:426-436)
+            ret.update(objectives.compute_mlm(self, batch))
         if "itm" in self.current_tasks:
             ret.update(objectives.compute_itm_wpa(self, batch))
         if "moco" in self.current_tasks:
@@ -525,7 +540,7 @@ class ViLTransformerSS(nn.Module):
             ret.update(objectives.compute_nlvr2_attack(self, batch))
         if "irtr" in self.current_tasks:
             ret.update(objectives.compute_irtr(self, batch))
-        unsupported = [t for t in self.current_tasks if t not in ("itm", "moco", "barlowtwins", "vqa", "vqa_attacked", "nlvr2", "nlvr2_attacked", "irtr")]
+        unsupported = [t for t in self.current_tasks if t not in ("mlm", "itm", "moco", "barlowtwins", "vqa", "vqa_attacked", "nlvr2", "nlvr2_attacked", "irtr")]
         if unsupported:
             raise NotImplementedError(f"tasks {unsupported} are outside the RMCL hot path (SURVEY 8)")
         return ret

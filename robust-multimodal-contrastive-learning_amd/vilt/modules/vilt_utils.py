@@ -31,6 +31,11 @@ def epoch_wrapup(pl_module):
     phase = "train" if pl_module.training else "val"
     out = {k: (float(v) if torch.is_tensor(v) and v.numel() == 1 else v) for k, v in pl_module.logged.items()}
     pl_module.logged = {}
+    counts = getattr(pl_module, "mlm_epoch_counts", {}).pop(phase, None)
+    if counts is not None:
+        # the epoch value of the reference's Accuracy metric: correct / total over every labelled row seen this epoch, then reset
+        correct, total = counts.tolist()
+        out[f"mlm/{phase}/accuracy_epoch"] = correct / total if total else float("nan")
     if pl_module.hparams.config.get("get_recall_metric", False) and not pl_module.training:
         # vilt_utils.py:90-97: image-text retrieval recalls at the end of a validation / test epoch; ir_r1 + tr_r1 joins the_metric.
         # The datasets come from pl_module.irtr_eval_dsets = (text_dset, image_dset) when set, else from the trainer's datamodule
@@ -99,6 +104,7 @@ class FusedAdamW:
               "adamw")
         e.fold_stale["q"] = True
         e.lpT_stale = True
+        e.mlm_wt_stale = True
 
 
 class PolySchedule:

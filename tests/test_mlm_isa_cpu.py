@@ -1,0 +1,52 @@
+"""CPU (hipcc cross-compiles gfx950 without a GPU): every kernel of csrc/mlm.hip is present and uses no scratch memory, the bf16
+decoder kernels run on the bf16 matrix-core instructions, and the file's assembly holds no float atomic and no compare-and-swap loop
+(every output of the MLM head has one owner and a fixed summation order) - the same reading of the compiler's own assembly as
+tests/test_vqa_isa_cpu.py."""
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "robust-multimodal-contrastive-learning_amd", "csrc", "mlm.hip")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-x", "hip", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include")]
+KERNELS = ("mlm_compact_kernel", "mlm_gather_kernel", "mlm_scatter_kernel", "mlm_gelu_ln_fwd_kernel", "mlm_gelu_ln_bwd_kernel",
+           "mlm_param_grad_kernel", "mlm_transpose_kernel", "mlm_dec_fwd_kernel", "mlm_dec_finish_kernel", "mlm_stats_kernel",
+           "mlm_dec_bwd_w_kernel", "mlm_dec_bwd_h_kernel", "mlm_dh_reduce_kernel", "mlm_logits_kernel")
+# the bf16 instantiations (operand type unsigned short: "It" in the mangled name) of the kernels that multiply by decoder.weight
+DECODER_BF16 = ("mlm_dec_fwd_kernelItLi6E", "mlm_dec_bwd_w_kernelItLi6E", "mlm_dec_bwd_h_kernelItLi6E", "mlm_logits_kernelItLi6E")
+
+
+@pytest.fixture(scope="module")
+def isa():
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not on PATH")
+    with tempfile.TemporaryDirectory() as tmp:
+        dst = os.path.join(tmp, "mlm.s")
+        r = subprocess.run(["hipcc", *FLAGS, SRC, "-o", dst], capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return open(dst).read()
+
+
+def test_mlm_kernels_are_present_and_use_no_scratch(isa):
+    sizes = re.findall(r"\.set (_Z\S+)\.private_seg_size, (\d+)", isa)
+    names = " ".join(n for n, _ in sizes)
+    for k in KERNELS:
+        assert k in names, k
+    spilled = [(n[:80], int(s)) for n, s in sizes if int(s) != 0]
+    assert not spilled, spilled
+
+
+def test_decoder_kernels_run_on_the_bf16_matrix_cores(isa):
+    for k in DECODER_BF16:
+        m = re.search(r"^_Z\S*" + re.escape(k) + r"\S*:[^\n]*\n(.*?)^\.Lfunc_end", isa, re.S | re.M)
+        assert m, k
+        assert re.search(r"v_mfma_f32_\d+x\d+x\d+_bf16", m.group(1)), k
+
+
+def test_no_float_atomics_in_the_file(isa):
+    for word in ("global_atomic_add_f32", "global_atomic_pk_add", "cmpswap", "flat_atomic_add_f32", "ds_add_f32", "ds_add_rtn_f32"):
+        assert word not in isa, word
