@@ -11,6 +11,33 @@ import torch
 from .. import _lib as L
 
 
+def device_image(eng, img) -> torch.Tensor:
+    """A batch image (``batch["image"][v]``) as the float tensor [B,3,H,W] on the device, for the callers that need pixels: the public
+    ``pgd_attack`` methods return / leave behind images, the ITM objective mixes two views."""
+    if hasattr(img, "tables"):                               # decoded bytes (collate_raw_uint8): MinMaxResize on the device first
+        img = eng.resize_raw(img)
+    if hasattr(img, "float_image"):                          # byte batch (collate_uint8)
+        img = img.to(eng.device).float_image()
+    return img.to(eng.device)
+
+
+def ascent_tail(eng, pb, step, K, lr, eps, keep_prev=False, full=None) -> torch.Tensor:
+    """The end of PGD step `step` of K on the buffers `pb` (a whole batch, a lane or a view), after its data gradient is in
+    ``pb.gpatch``: the L-inf-normalised ascent step with the eps projection (``Engine.pgd_step``, :162-173), which also writes the
+    operand of what runs next - cast(img + delta) into ``pb.patchesT`` for the next step's forward, after the last step the attacked
+    view cast(img + delta_{K-1} + delta_K) into ``full`` (default ``pb.patchesT_full``).  ``keep_prev``: delta_{K-1} is left in
+    ``pb.delta_prev``.  Returns the operand written."""
+    last = step == K - 1
+    if last and keep_prev:
+        if K > 1:
+            pb.delta_prev.copy_(pb.delta)
+        else:
+            pb.delta_prev.zero_()
+    op = (pb.patchesT_full if full is None else full) if last else pb.patchesT
+    eng.pgd_step(pb, lr, eps, first=step == 0, out=op, sum_prev=last)
+    return op
+
+
 class PGDAttack:
     def __init__(self, config, contrastive_framework):
         self.contrastive_framework = contrastive_framework
@@ -22,6 +49,23 @@ class PGDAttack:
     def pgd_attack(self, pl_module, batch, k_image):
         raise NotImplementedError(f"pgd_attack of {self.contrastive_framework} isn't implemented.")
 
+    def _attack_chain(self, eng, pb, cls_grad, clean_op=None, keep_prev=False, full=None):
+        """K steps as one chain on the current stream: encoder forward at img + delta, ``cls_grad(step)`` (the pooler / projection
+        heads, the objective's loss and its head backward: returns (dq, dcls_extra), the gradient at the projection and at the pooled
+        cls rows, for ``Engine.heads_backward``), data-gradient backward, ``ascent_tail``.  Every step's update kernel also writes
+        the next forward's operand, step 0 starts from the implicit delta_0 = 0: no zero fills, no separate add + cast passes, no
+        delta copy inside the loop.  ``clean_op``: the caller's cast of the clean image in pb.patchesT, if it has one; ``full``: where
+        the attacked view's operand goes (``ascent_tail``).  Returns ``pb.delta`` = delta_K."""
+        K = self.adv_steps_img
+        op = clean_op if clean_op is not None else eng.make_operand(pb)     # img_init + delta_0, delta_0 = 0 (:136,144)
+        for step in range(K):
+            eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
+            dq, dcls_extra = cls_grad(step)
+            eng.heads_backward(pb, dq, dcls_extra, with_grads=False)
+            eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=pb.gpatch)
+            op = ascent_tail(eng, pb, step, K, self.adv_lr_img, self.adv_max_norm_img, keep_prev, full)
+        return pb.delta
+
 
 class PGDAttack_moco(PGDAttack):
     def __init__(self, config):
@@ -31,9 +75,6 @@ class PGDAttack_moco(PGDAttack):
         """K-step attack in patch layout.  Leaves delta_K in ``pb.delta`` and the ATTACKED VIEW's operand
         cast(img + delta_{K-1} + delta_K) (see compute_pgd / objectives.py:176) in ``pb.patchesT_full``; with ``keep_prev``
         also delta_{K-1} in ``pb.delta_prev`` (the public ``pgd_attack`` needs it for the batch image it leaves behind).
-
-        Every step's update kernel also writes the next forward's operand (``Engine.pgd_step``), step 0 starts from the
-        implicit delta_0 = 0: no zero fills, no separate add + cast passes, no delta copy inside the loop.
 
         ``before_first_loss``: callback run once between the first encoder forward and the first InfoNCE (the
         caller joins the key-encoder stream there).  ``clean_out``: dict that receives the clean-query statistics:
@@ -48,11 +89,8 @@ class PGDAttack_moco(PGDAttack):
         lanes = eng.lanes(pb) if pb is pb0 else None
         if lanes is not None:
             return self._attack_lanes(eng, pb, lanes, K, before_first_loss, clean_out, keep_prev, clean_op, key_stream, key_event)
-        # img_init + delta_0, delta_0 = 0 (:136,144); ``clean_op``: the caller's cast of the clean image in pb.patchesT, if it has one
-        op = clean_op if (clean_op is not None and pb is pb0) else eng.make_operand(pb)
-        for step in range(K):
-            last = step == K - 1
-            eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
+
+        def cls_grad(step):
             eng.heads_forward(pb, key=False, wgrad=False)
             if step == 0 and before_first_loss is not None:
                 before_first_loss()
@@ -61,16 +99,9 @@ class PGDAttack_moco(PGDAttack):
             if step == 0 and clean_out is not None:
                 clean_out["prediction"] = pb.rows[:, 1].clone()
                 clean_out["q"] = pb.q.clone()
-            eng.heads_backward(pb, pb.dq, None, with_grads=False)
-            eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=pb.gpatch)
-            if last and keep_prev:
-                if K > 1:
-                    pb.delta_prev.copy_(pb.delta)
-                else:
-                    pb.delta_prev.zero_()
-            op = pb0.patchesT_full if last else pb.patchesT
-            eng.pgd_step(pb, self.adv_lr_img, self.adv_max_norm_img, first=step == 0, out=op, sum_prev=last)   # :162-173
-        return pb.delta
+            return pb.dq, None
+
+        return self._attack_chain(eng, pb, cls_grad, clean_op if pb is pb0 else None, keep_prev, pb0.patchesT_full)
 
     def _attack_lanes(self, eng, pb, lanes, K, before_first_loss, clean_out, keep_prev, clean_op, key_stream, key_event=None):
         """The same K steps as two independent half-batch chains (Engine.lanes): lane 0 on the current stream, lane 1 on
@@ -106,7 +137,6 @@ class PGDAttack_moco(PGDAttack):
         check(lib.rmcl_tune_set(10, len(lanes)), "tune_set")  # the GEMM routing sizes a launch against its share of the CUs
         try:
             for step in range(K):
-                last = step == K - 1
                 # the host alternates between the lanes call by call, so that neither queue runs dry while the other is being filled
                 for i, ln in enumerate(lanes):
                     with on(i):
@@ -131,13 +161,7 @@ class PGDAttack_moco(PGDAttack):
                         eng.encoder_backward(ln, L.MODE_DATA, ops[i], ln.dcls, cls_only=True, dpatches=ln.gpatch)
                 for i, ln in enumerate(lanes):
                     with on(i):
-                        if last and keep_prev:
-                            if K > 1:
-                                ln.delta_prev.copy_(ln.delta)
-                            else:
-                                ln.delta_prev.zero_()
-                        ops[i] = ln.patchesT_full if last else ln.patchesT
-                        eng.pgd_step(ln, self.adv_lr_img, self.adv_max_norm_img, first=step == 0, out=ops[i], sum_prev=last)
+                        ops[i] = ascent_tail(eng, ln, step, K, self.adv_lr_img, self.adv_max_norm_img, keep_prev)
         finally:
             # process-global routing state and the forked streams are put back on EVERY path: an exception inside the loop must not
             # leave every later GEMM sized for half the chip or the side streams unjoined
@@ -148,16 +172,11 @@ class PGDAttack_moco(PGDAttack):
 
     def pgd_attack(self, pl_module, batch, k_modality=None):
         eng = pl_module.engine
-        img_init = batch["image"][0]
-        if hasattr(img_init, "tables"):                      # decoded bytes (collate_raw_uint8): MinMaxResize on the device first
-            img_init = eng.resize_raw(img_init)
-        if hasattr(img_init, "float_image"):                 # byte batch (collate_uint8): this public API returns / leaves behind images
-            img_init = img_init.to(eng.device).float_image()
+        img_init = device_image(eng, batch["image"][0])
         pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init)
         delta_p = self.attack_patches(pl_module, pb, k_modality, keep_prev=True)
-        B = img_init.shape[0]
         # the reference leaves batch['image'][0] = img_init + delta_{K-1} behind (:144)
-        batch["image"][0] = img_init.to(eng.device) + eng.patches_to_image(pb.delta_prev, pb)
+        batch["image"][0] = img_init + eng.patches_to_image(pb.delta_prev, pb)
         return eng.patches_to_image(delta_p, pb)
 
 
@@ -175,35 +194,21 @@ class PGDAttack_bartlowtwins(PGDAttack):
         K = self.adv_steps_img
         bb = eng.bt_bufs(pb.B, "pgd")
         mode = bool(pl_module.training)           # deepcopy(pl_module.barlowtwins_head) keeps the train / eval flag (:189)
-        op = clean_op if clean_op is not None else eng.make_operand(pb)                 # delta_0 = 0
-        for step in range(K):
-            last = step == K - 1
-            eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
+
+        def cls_grad(step):
             eng.heads_forward(pb, key=False, want_q=False, wgrad=False)
             eng.bt_forward(bb, pb.cls, training=mode, track=False)
             eng.bt_loss(bb, zk, float(pb.B), pl_module.adv_lr, 1.0 / K, want_dz=True)
-            dcls = eng.bt_backward(bb, bb.dz, training=mode, with_grads=False)
-            eng.heads_backward(pb, None, dcls, with_grads=False)
-            eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=pb.gpatch)
-            if last and keep_prev:
-                if K > 1:
-                    pb.delta_prev.copy_(pb.delta)
-                else:
-                    pb.delta_prev.zero_()
-            op = pb.patchesT_full if last else pb.patchesT
-            eng.pgd_step(pb, self.adv_lr_img, self.adv_max_norm_img, first=step == 0, out=op, sum_prev=last)
-        return pb.delta
+            return None, eng.bt_backward(bb, bb.dz, training=mode, with_grads=False)
+
+        return self._attack_chain(eng, pb, cls_grad, clean_op, keep_prev)
 
     def pgd_attack(self, pl_module, batch, k_modality=None):
         eng = pl_module.engine
-        img_init = batch["image"][0]
-        if hasattr(img_init, "tables"):
-            img_init = eng.resize_raw(img_init)
-        if hasattr(img_init, "float_image"):
-            img_init = img_init.to(eng.device).float_image()
+        img_init = device_image(eng, batch["image"][0])
         pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init, tag="bt")
         delta_p = self.attack_patches(pl_module, pb, k_modality.to(eng.device, torch.float32).contiguous(), keep_prev=True)
-        batch["image"][0] = img_init.to(eng.device) + eng.patches_to_image(pb.delta_prev, pb)
+        batch["image"][0] = img_init + eng.patches_to_image(pb.delta_prev, pb)
         return eng.patches_to_image(delta_p, pb)
 
 
@@ -222,40 +227,25 @@ class PGDAttack_vqa(PGDAttack):
         objectives.py:176) in ``pb.patchesT_full``.  ``vb_tables``: VqaBuffers holding this batch's label / score tables
         (Engine.vqa_targets); the loop's head passes run in them."""
         eng = pl_module.engine
-        K = self.adv_steps_img
         pb0 = pb
         pb = eng.pgd_bufs(pb)                                 # fp32 twin when the engine runs PGD in fp32
         vb = vb_tables
-        op = clean_op if (clean_op is not None and pb is pb0) else eng.make_operand(pb)      # delta_0 = 0
-        for step in range(K):
-            last = step == K - 1
-            eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
+
+        def cls_grad(step):
             eng.heads_forward(pb, key=False, want_q=False, wgrad=False)
             eng.vqa_forward(vb, pb.cls)
             eng.vqa_bce(vb, 1.0, want_dz=True)                                        # :444-460, d loss / d logits
-            dcls = eng.vqa_backward(vb, vb.dz, with_grads=False)
-            eng.heads_backward(pb, None, dcls, with_grads=False)
-            eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=pb.gpatch)
-            if last and keep_prev:
-                if K > 1:
-                    pb.delta_prev.copy_(pb.delta)
-                else:
-                    pb.delta_prev.zero_()
-            op = pb0.patchesT_full if last else pb.patchesT
-            eng.pgd_step(pb, self.adv_lr_img, self.adv_max_norm_img, first=step == 0, out=op, sum_prev=last)   # :464-481
-        return pb.delta
+            return None, eng.vqa_backward(vb, vb.dz, with_grads=False)
+
+        return self._attack_chain(eng, pb, cls_grad, clean_op if pb is pb0 else None, keep_prev, pb0.patchesT_full)   # :464-481
 
     def pgd_attack(self, pl_module, batch, k_modality=None):
         eng = pl_module.engine
-        img_init = batch["image"][0]
-        if hasattr(img_init, "tables"):
-            img_init = eng.resize_raw(img_init)
-        if hasattr(img_init, "float_image"):
-            img_init = img_init.to(eng.device).float_image()
+        img_init = device_image(eng, batch["image"][0])
         pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init, tag="vqa_att")
         vb = eng.vqa_targets(eng.vqa_bufs(pb.B, "pgd"), batch["vqa_labels"], batch["vqa_scores"])
         delta_p = self.attack_patches(pl_module, pb, vb, keep_prev=True)
-        batch["image"][0] = img_init.to(eng.device) + eng.patches_to_image(pb.delta_prev, pb)
+        batch["image"][0] = img_init + eng.patches_to_image(pb.delta_prev, pb)
         return eng.patches_to_image(delta_p, pb)
 
 
@@ -290,7 +280,6 @@ class PGDAttack_nlvr2(PGDAttack):
                 pv.delta_prev.zero_()
                 eng.make_operand(pv, out=pv.patchesT_full)
         for step in range(K):
-            last = step == K - 1
             cls2 = npass.forward(L.MODE_DATA, wgrad=False)
             eng.nlvr2_forward(nb, cls2)
             eng.nlvr2_ce(nb, 1.0 / K, want_dz=True)                          # CE / adv_steps_img (:296)
@@ -301,13 +290,7 @@ class PGDAttack_nlvr2(PGDAttack):
                     continue
                 if npass.pair and not (a0 and a1):                          # the image that is not attacked: zero gradient rows -> step 0
                     pv.gpatch.view(npass.B, 2, -1)[:, 1 if a0 else 0].zero_()
-                if last and keep_prev:
-                    if K > 1:
-                        pv.delta_prev.copy_(pv.delta)
-                    else:
-                        pv.delta_prev.zero_()
-                npass.ops[i] = pv.patchesT_full if last else pv.patchesT
-                eng.pgd_step(pv, self.adv_lr_img, self.adv_max_norm_img, first=step == 0, out=npass.ops[i], sum_prev=last)   # :302-331
+                npass.ops[i] = ascent_tail(eng, pv, step, K, self.adv_lr_img, self.adv_max_norm_img, keep_prev)   # :302-331
 
     def _image_of(self, eng, npass, pat_attr, shapes):
         """(image_0 part, image_1 part) of a per-view patch buffer, in the batch's image layouts"""
@@ -340,12 +323,7 @@ class PGDAttack_nlvr2(PGDAttack):
         eng = pl_module.engine
         imgs = []
         for key in ("image_0", "image_1"):
-            im = batch[key][0]
-            if hasattr(im, "tables"):
-                im = eng.resize_raw(im)
-            if hasattr(im, "float_image"):
-                im = im.to(eng.device).float_image()
-            imgs.append(im.to(eng.device, torch.float32))
+            imgs.append(device_image(eng, batch[key][0]).to(torch.float32))
         b2 = dict(batch, image_0=[imgs[0]], image_1=[imgs[1]])
         npass = Nlvr2Pass.bind(pl_module, b2, "nlvr2_att_0").twin("nlvr2_att")
         nb = eng.nlvr2_bufs(npass.B, "pgd")

@@ -101,25 +101,32 @@ def param_specs(cfg: dict, lay: L.Layout) -> List[Tuple[str, int, Tuple[int, ...
 EMA_GROUPS = ("text_embeddings", "token_type_embeddings", "transformer", "moco_head")
 
 
+def _pack(base: int, table):
+    """The one arena packer of the optional heads: `table` = [(struct key, state-dict name, shape, element count or None = the
+    shape's product)], placed one after the other from element offset `base`, every slot rounded up to 64 elements.  Returns
+    (offs {key: element offset}, specs [(name, offset, shape)], elements used)."""
+    off, offs, specs = base, {}, []
+    for key, name, shape, cnt in table:
+        offs[key] = off
+        specs.append((name, off, shape))
+        if cnt is None:
+            cnt = 1
+            for v in shape:
+                cnt *= v
+        off += (cnt + 63) // 64 * 64
+    return offs, specs, off - base
+
+
 def bt_layout(cfg: dict, base: int):
     """BarlowTwinsHead (heads.py:88-107; widths [8192, 8192], 8192 at vilt_module.py:115, config key "barlowtwins_dims")
     appended to the parameter arena at element offset `base`: returns (rmcl_bt_head struct, specs, elements used)."""
     D = cfg["hidden_size"]
     H1, H2, H3 = cfg.get("barlowtwins_dims", (8192, 8192, 8192))
-    off = base
-    offs = {}
     n = "barlowtwins_head.projector."
-    shapes = [("w1", n + "0.weight", (H1, D)), ("g1", n + "1.weight", (H1,)), ("b1", n + "1.bias", (H1,)),
-              ("w2", n + "3.weight", (H2, H1)), ("g2", n + "4.weight", (H2,)), ("b2", n + "4.bias", (H2,)), ("w3", n + "6.weight", (H3, H2))]
-    specs = []
-    for key, name, shape in shapes:
-        offs[key] = off
-        specs.append((name, off, shape))
-        cnt = 1
-        for v in shape:
-            cnt *= v
-        off += (cnt + 63) // 64 * 64
-    return L.BtHead(D=D, H1=H1, H2=H2, H3=H3, **offs), specs, off - base
+    offs, specs, used = _pack(base, [("w1", n + "0.weight", (H1, D), None), ("g1", n + "1.weight", (H1,), None), ("b1", n + "1.bias", (H1,), None),
+                                     ("w2", n + "3.weight", (H2, H1), None), ("g2", n + "4.weight", (H2,), None), ("b2", n + "4.bias", (H2,), None),
+                                     ("w3", n + "6.weight", (H3, H2), None)])
+    return L.BtHead(D=D, H1=H1, H2=H2, H3=H3, **offs), specs, used
 
 
 class BtBuffers:
@@ -136,45 +143,23 @@ class BtBuffers:
         self.loss2 = f32(2)
 
 
+def _classifier_layout(prefix: str, D: int, H: int, N: int, ldl: int, base: int):
+    """Linear(D, H) - LayerNorm(H) - GELU - Linear(H, N) under the state-dict prefix `prefix` (the shape of vqa_classifier and
+    nlvr2_classifier) at element offset `base`: (rmcl_vqa_head struct, specs, elements used).  The last weight keeps ldl rows in
+    the arena (ldl = the logits pitch, a multiple of 64): rows N..ldl-1 stay zero (no gradient reaches them, AdamW leaves a zero
+    parameter with a zero gradient at zero), so the data gradient dz W3 runs on the padded width."""
+    n = prefix
+    offs, specs, used = _pack(base, [("w0", n + "0.weight", (H, D), H * D), ("b0", n + "0.bias", (H,), H), ("g1", n + "1.weight", (H,), H),
+                                     ("b1", n + "1.bias", (H,), H), ("w3", n + "3.weight", (N, H), ldl * H), ("b3", n + "3.bias", (N,), N)])
+    return L.VqaHead(D=D, H=H, N=N, ldl=ldl, **offs), specs, used
+
+
 def vqa_layout(cfg: dict, base: int):
     """vqa_classifier (vilt_module.py:164-172: Linear(D, 2D) - LayerNorm(2D) - GELU - Linear(2D, vqav2_label_size)) appended to the
-    parameter arena at element offset `base`: returns (rmcl_vqa_head struct, specs, elements used).  The last weight keeps ldl rows
-    in the arena (ldl = the logits pitch, a multiple of 64): rows N..ldl-1 stay zero (no gradient reaches them, AdamW leaves a zero
-    parameter with a zero gradient at zero), so the data gradient dz W3 runs on the padded width."""
-    D = cfg["hidden_size"]
-    H, N = 2 * D, int(cfg["vqav2_label_size"])
-    ldl = (N + 63) // 64 * 64
-    n = "vqa_classifier."
-    shapes = [("w0", n + "0.weight", (H, D), H * D), ("b0", n + "0.bias", (H,), H), ("g1", n + "1.weight", (H,), H),
-              ("b1", n + "1.bias", (H,), H), ("w3", n + "3.weight", (N, H), ldl * H), ("b3", n + "3.bias", (N,), N)]
-    off, offs, specs = base, {}, []
-    for key, name, shape, cnt in shapes:
-        offs[key] = off
-        specs.append((name, off, shape))
-        off += (cnt + 63) // 64 * 64
-    return L.VqaHead(D=D, H=H, N=N, ldl=ldl, **offs), specs, off - base
-
-
-class VqaBuffers:
-    """Per-pass buffers of the VQA head: its stash, the pitched logits and dz, the row outputs, and the label / score tables of the
-    batch (one pinned host buffer, one asynchronous copy: ``Engine.vqa_targets``)."""
-
-    def __init__(self, eng: "Engine", B: int):
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=eng.device)
-        h = eng.vqa
-        self.B = B
-        self.stash = f32(int(lib.rmcl_vqa_stash_floats(C.byref(h), B)))
-        self.logits_p = f32(B, h.ldl)
-        self.logits = self.logits_p[:, : h.N]                  # the public [B, N] view
-        self.dz = f32(B, h.ldl)
-        self.dcls = f32(B, h.D)
-        self.rows = f32(B, 2)
-        self.argmax = torch.empty(B, dtype=torch.int32, device=eng.device)
-        self.loss2 = f32(2)
-        self.A = 0
-        self.tab = None                                         # device [2, B, A] int32: labels, then the scores' bits
-        self.labels = self.scores = None
-        self._host = None
+    parameter arena at element offset `base`: returns (rmcl_vqa_head struct, specs, elements used); the logits pitch is
+    vqav2_label_size rounded up to 64 (_classifier_layout)."""
+    D, N = cfg["hidden_size"], int(cfg["vqav2_label_size"])
+    return _classifier_layout("vqa_classifier.", D, 2 * D, N, (N + 63) // 64 * 64, base)
 
 
 def nlvr2_layout(cfg: dict, base: int):
@@ -182,33 +167,44 @@ def nlvr2_layout(cfg: dict, base: int):
     at element offset `base`: the VQA head struct with D = H = 2 hidden, N = 2 and a logits pitch of 64 (include/rmcl.h).  Returns
     (rmcl_vqa_head struct, specs, elements used).  As for vqa_layout, the last weight keeps ldl rows (rows 2..63 stay zero)."""
     D2 = 2 * cfg["hidden_size"]
-    N, ldl = 2, 64
-    n = "nlvr2_classifier."
-    shapes = [("w0", n + "0.weight", (D2, D2), D2 * D2), ("b0", n + "0.bias", (D2,), D2), ("g1", n + "1.weight", (D2,), D2),
-              ("b1", n + "1.bias", (D2,), D2), ("w3", n + "3.weight", (N, D2), ldl * D2), ("b3", n + "3.bias", (N,), N)]
-    off, offs, specs = base, {}, []
-    for key, name, shape, cnt in shapes:
-        offs[key] = off
-        specs.append((name, off, shape))
-        off += (cnt + 63) // 64 * 64
-    return L.VqaHead(D=D2, H=D2, N=N, ldl=ldl, **offs), specs, off - base
+    return _classifier_layout("nlvr2_classifier.", D2, D2, 2, 64, base)
 
 
-class Nlvr2Buffers:
-    """Per-pass buffers of the NLVR2 head (B = pairs): its stash, the pitched logits and dz, the CE row outputs and the labels."""
+class ClassifierBuffers:
+    """What the per-pass buffers of the VQA and the NLVR2 head share (both run the rmcl_vqa_head kernels on the struct `h`): the
+    stash, the pitched logits and dz, the cls gradient, the row outputs of the loss (`rows_shape`) and the per-row argmax."""
 
-    def __init__(self, eng: "Engine", B: int):
+    def __init__(self, eng: "Engine", h, B: int, rows_shape):
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=eng.device)
-        h = eng.nlvr2
         self.B = B
         self.stash = f32(int(lib.rmcl_vqa_stash_floats(C.byref(h), B)))
         self.logits_p = f32(B, h.ldl)
-        self.logits = self.logits_p[:, : h.N]                  # the public [B, 2] view
+        self.logits = self.logits_p[:, : h.N]                  # the public [B, N] view
         self.dz = f32(B, h.ldl)
-        self.dcls = f32(B, h.D)                                # [B, 2 hidden] = the pair pass's [2B, hidden] cls gradient
-        self.rows = f32(B)
+        self.dcls = f32(B, h.D)                                # (NLVR2: [B, 2 hidden] = the pair pass's [2B, hidden] cls gradient)
+        self.rows = f32(*rows_shape)
         self.argmax = torch.empty(B, dtype=torch.int32, device=eng.device)
-        self.stats = f32(3)
+
+
+class VqaBuffers(ClassifierBuffers):
+    """Per-pass buffers of the VQA head: its stash, the pitched logits and dz, the row outputs, and the label / score tables of the
+    batch (one pinned host buffer, one asynchronous copy: ``Engine.vqa_targets``)."""
+
+    def __init__(self, eng: "Engine", B: int):
+        super().__init__(eng, eng.vqa, B, (B, 2))
+        self.loss2 = torch.empty(2, dtype=torch.float32, device=eng.device)
+        self.A = 0
+        self.tab = None                                         # device [2, B, A] int32: labels, then the scores' bits
+        self.labels = self.scores = None
+        self._host = None
+
+
+class Nlvr2Buffers(ClassifierBuffers):
+    """Per-pass buffers of the NLVR2 head (B = pairs): its stash, the pitched logits and dz, the CE row outputs and the labels."""
+
+    def __init__(self, eng: "Engine", B: int):
+        super().__init__(eng, eng.nlvr2, B, (B,))
+        self.stats = torch.empty(3, dtype=torch.float32, device=eng.device)
         self.labels = torch.empty(B, dtype=torch.int32, device=eng.device)
 
 
@@ -217,18 +213,10 @@ def mlm_layout(cfg: dict, base: int):
     own) appended to the parameter arena at element offset `base`: returns (rmcl_mlm_head struct, specs, elements used)."""
     D, V = int(cfg["hidden_size"]), int(cfg["vocab_size"])
     n = "mlm_score."
-    shapes = [("tw", n + "transform.dense.weight", (D, D)), ("tb", n + "transform.dense.bias", (D,)),
-              ("lg", n + "transform.LayerNorm.weight", (D,)), ("lb", n + "transform.LayerNorm.bias", (D,)),
-              ("dw", n + "decoder.weight", (V, D)), ("db", n + "bias", (V,))]
-    off, offs, specs = base, {}, []
-    for key, name, shape in shapes:
-        offs[key] = off
-        specs.append((name, off, shape))
-        cnt = 1
-        for v in shape:
-            cnt *= v
-        off += (cnt + 63) // 64 * 64
-    return L.MlmHead(D=D, V=V, **offs), specs, off - base
+    offs, specs, used = _pack(base, [("tw", n + "transform.dense.weight", (D, D), None), ("tb", n + "transform.dense.bias", (D,), None),
+                                     ("lg", n + "transform.LayerNorm.weight", (D,), None), ("lb", n + "transform.LayerNorm.bias", (D,), None),
+                                     ("dw", n + "decoder.weight", (V, D), None), ("db", n + "bias", (V,), None)])
+    return L.MlmHead(D=D, V=V, **offs), specs, used
 
 
 class MlmBuffers:
@@ -269,13 +257,8 @@ class PassBuffers:
         self.d = d
         N = d.L + 1 + d.P
         M = B * N
-        u8 = lambda n: torch.empty(int(n), dtype=torch.uint8, device=dev)
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        self.workspace = u8(lib.rmcl_workspace_bytes(C.byref(d)))
-        self.stash_full = u8(lib.rmcl_stash_bytes(C.byref(d), L.MODE_FULL))
-        self.stash_data = u8(lib.rmcl_stash_bytes(C.byref(d), L.MODE_DATA))
-        self.hstash_q = u8(lib.rmcl_heads_stash_bytes(C.byref(d)))
-        self.hstash_k = u8(lib.rmcl_heads_stash_bytes(C.byref(d)))
+        self._init_scratch(eng, d, full_stash=True)
         self.co_mask = torch.empty(B, N, dtype=torch.int32, device=dev)
         self.xn = f32(M, d.D)
         self.patches32 = f32(B * d.P, d.patch_k)
@@ -292,43 +275,40 @@ class PassBuffers:
         self.dq = f32(B, d.proj)
         self.dcls = f32(B, d.D)
         self.rows = f32(B, 10)
+
+    def _init_scratch(self, eng: "Engine", d, full_stash: bool):
+        """The scratch of one pass, owned by whole-batch buffers and lanes alike: workspace, stashes, loss ring, InfoNCE workspace, and
+        the per-step defaults (text tensors, position rows, dropout seeds, tail flags)."""
+        dev = eng.device
+        u8 = lambda n: torch.empty(int(n), dtype=torch.uint8, device=dev)
+        self.workspace = u8(lib.rmcl_workspace_bytes(C.byref(d)))
+        self.stash_full = u8(lib.rmcl_stash_bytes(C.byref(d), L.MODE_FULL)) if full_stash else None   # lanes run the data-gradient passes only
+        self.stash_data = u8(lib.rmcl_stash_bytes(C.byref(d), L.MODE_DATA))
+        self.hstash_q = u8(lib.rmcl_heads_stash_bytes(C.byref(d)))
+        self.hstash_k = u8(lib.rmcl_heads_stash_bytes(C.byref(d)))
         self.loss_ring = torch.zeros(32, dtype=torch.float32, device=dev)    # zeroed scalars for the kernels that ACCUMULATE a loss / norm:
         self.loss_i = 0                                                      # one fill per 32 uses instead of one per use (zero_scalar)
         self.loss_sum = self.loss_ring[0:1]
-        self.nce_ws = u8(lib.rmcl_infonce_ws_bytes(B, I64(eng.num_negative)))
+        self.nce_ws = u8(lib.rmcl_infonce_ws_bytes(d.B, I64(eng.num_negative)))
         self.text_ids = None
         self.text_mask = None
         self.pos_tok = self.dpos_tok = None      # per-sample position rows of a zero-padded batch and their gradient (lazy)
         self.drop = {L.MODE_INFER: (0, 0.0), L.MODE_DATA: (0, 0.0), L.MODE_FULL: (0, 0.0)}
         self.tail = {}                           # mode -> the last forward in that mode used the cls-only tail
 
-
     def _init_lane(self, eng: "Engine", d, par: "PassBuffers", lane: int):
-        dev, B = eng.device, d.B
+        B = d.B
         N = d.L + 1 + d.P
-        u8 = lambda n: torch.empty(int(n), dtype=torch.uint8, device=dev)
         rows = lambda t, per: t[lane * B * per:(lane + 1) * B * per]
         self.geom = self.ragged = None
         self.B, self.d, self.lane, self.parent = B, d, lane, par
-        self.workspace = u8(lib.rmcl_workspace_bytes(C.byref(d)))
-        self.stash_full = None                                   # lanes run the data-gradient passes only
-        self.stash_data = u8(lib.rmcl_stash_bytes(C.byref(d), L.MODE_DATA))
-        self.hstash_q = u8(lib.rmcl_heads_stash_bytes(C.byref(d)))
-        self.hstash_k = u8(lib.rmcl_heads_stash_bytes(C.byref(d)))
+        self._init_scratch(eng, d, full_stash=False)
         self.co_mask = rows(par.co_mask, 1)
         self.xn = rows(par.xn, N)
         self.patches32, self.patchesT, self.patchesT_full = rows(par.patches32, d.P), rows(par.patchesT, d.P), rows(par.patchesT_full, d.P)
         self.gpatch, self.delta, self.delta_prev = rows(par.gpatch, d.P), rows(par.delta, d.P), rows(par.delta_prev, d.P)
         self.amax = rows(par.amax, 64)
         self.cls, self.q, self.k, self.dq, self.dcls, self.rows = (rows(t, 1) for t in (par.cls, par.q, par.k, par.dq, par.dcls, par.rows))
-        self.loss_ring = torch.zeros(32, dtype=torch.float32, device=dev)
-        self.loss_i = 0
-        self.loss_sum = self.loss_ring[0:1]
-        self.nce_ws = u8(lib.rmcl_infonce_ws_bytes(B, I64(eng.num_negative)))
-        self.text_ids = self.text_mask = None
-        self.pos_tok = self.dpos_tok = None
-        self.drop = {L.MODE_INFER: (0, 0.0), L.MODE_DATA: (0, 0.0), L.MODE_FULL: (0, 0.0)}
-        self.tail = {}
 
 
 class RankPass:
@@ -393,38 +373,31 @@ class Engine:
         lib.rmcl_param_layout(C.byref(d0), C.byref(self.layout))
         lay = self.layout
         z = lambda n, dt=torch.float32: torch.zeros(int(n), dtype=dt, device=self.device)
-        # optional Barlow-Twins head (loss_names["barlowtwins"] > 0): appended behind the C layout's tensors, so the optimizer,
-        # the gradient reduction and the state dict see it as part of the same arena
-        self.bt, self.bt_specs, extra = None, [], 0
-        if cfg.get("loss_names", {}).get("barlowtwins", 0) > 0:
-            self.bt, self.bt_specs, extra = bt_layout(cfg, int(lay.total))
+        # optional heads, appended behind the C layout's tensors in this fixed order, so the optimizer, the gradient reduction and the
+        # state dict see them as part of the same arena; a model without a head keeps its arena size and specs:
+        #   bt    Barlow-Twins head (loss_names["barlowtwins"] > 0)
+        #   vqa   VQA classifier (loss_names["vqa"] / ["vqa_attacked"] > 0)
+        #   nlvr2 NLVR2 classifier (loss_names["nlvr2"] / ["nlvr2_attacked"] > 0); the 3-row token-type table of these models is part
+        #         of the C layout (rmcl_dims.n_types = 3, make_dims)
+        #   mlm   MLM head (loss_names["mlm"] > 0)
+        ln = cfg.get("loss_names", {})
+        extra = 0
+        for attr, present, layout_of in (("bt", ln.get("barlowtwins", 0) > 0, bt_layout),
+                                         ("vqa", ln.get("vqa", 0) > 0 or ln.get("vqa_attacked", 0) > 0, vqa_layout),
+                                         ("nlvr2", is_nlvr2(cfg), nlvr2_layout), ("mlm", ln.get("mlm", 0) > 0, mlm_layout)):
+            head, specs, used = layout_of(cfg, int(lay.total) + extra) if present else (None, [], 0)
+            setattr(self, attr, head)
+            setattr(self, attr + "_specs", specs)
+            extra += used
+        self._head_bufs = {}                                    # (buffer class, B, tag) -> per-pass buffers of a head (_head_buffers)
+        if self.bt is not None:
             H = self.bt
             self.bt_running = torch.cat([torch.zeros(H.H1), torch.ones(H.H1), torch.zeros(H.H2), torch.ones(H.H2), torch.zeros(H.H3),
                                          torch.ones(H.H3)]).to(self.device)      # [mean1, var1, mean2, var2, mean3, var3]
             self.bt_tracked = torch.zeros(3, dtype=torch.int64, device=self.device)
             self.bt_corr = torch.empty(H.H3, H.H3, dtype=torch.float32, device=self.device)
             self.bt_ws = torch.empty(int(lib.rmcl_bt_loss_ws_floats(H.H3)), dtype=torch.float32, device=self.device)
-            self._bt_bufs = {}
-        # optional VQA classifier (loss_names["vqa"] / ["vqa_attacked"] > 0): appended behind the same arena, like the Barlow-Twins head
-        self.vqa, self.vqa_specs = None, []
-        ln = cfg.get("loss_names", {})
-        if ln.get("vqa", 0) > 0 or ln.get("vqa_attacked", 0) > 0:
-            self.vqa, self.vqa_specs, n_vqa = vqa_layout(cfg, int(lay.total) + extra)
-            extra += n_vqa
-            self._vqa_bufs = {}
-        # optional NLVR2 classifier (loss_names["nlvr2"] / ["nlvr2_attacked"] > 0): behind the other heads; the 3-row token-type table
-        # of these models is part of the C layout (rmcl_dims.n_types = 3, make_dims)
-        self.nlvr2, self.nlvr2_specs = None, []
-        if is_nlvr2(cfg):
-            self.nlvr2, self.nlvr2_specs, n_nl = nlvr2_layout(cfg, int(lay.total) + extra)
-            extra += n_nl
-            self._nlvr2_bufs = {}
-        # optional MLM head (loss_names["mlm"] > 0): behind the other heads; a model without it keeps its arena size and specs
-        self.mlm, self.mlm_specs = None, []
-        if ln.get("mlm", 0) > 0:
-            self.mlm, self.mlm_specs, n_mlm = mlm_layout(cfg, int(lay.total) + extra)
-            extra += n_mlm
-            self._mlm_bufs = {}
+        if self.mlm is not None:
             self.mlm_wT = None                                  # decoder.weight^T in the operand type (rmcl_mlm_weight_transpose)
             self.mlm_wt_stale = True
         # IRTR (loss_names["irtr"] > 0): rank_output.weight / .bias ARE row 1 of the ITM head's slots (vilt_module.py:233-239 makes them
@@ -618,25 +591,54 @@ class Engine:
         cnt = counts.cpu()
         if Hh == S and Ww == S and select is None and bool((cnt == gh * gw).all()):
             return None
+        sel, counts, n = self._cap_selection(sel, counts, cnt, select, max_image_len, check_tokens)
+        return RaggedGeometry(sel, counts, hw, n, gh, gw, (B, 3, Hh, Ww))
+
+    def _cap_selection(self, sel: torch.Tensor, counts: torch.Tensor, cnt: torch.Tensor, select, max_image_len=None, check_tokens: bool = True):
+        """The image length n of a zero-padded batch and its selection cut to it.  sel [B, G] / counts [B]: the valid-patch lists, both
+        on the device or both on the host; cnt: the counts on the HOST.  n = the largest count, capped at max_image_len (default: the
+        config's).  `select`: the caller's draw [B, n] replaces sel (parity tests: the reference's); else every sample with more than n
+        valid patches keeps a random subset, drawn on the host's generator in sample order.  Returns (sel, counts clamped to n, n)."""
+        B = cnt.shape[0]
         n = int(cnt.max())
         mil = self.cfg.get("max_image_len", -1) if max_image_len is None else max_image_len
         if isinstance(mil, int) and mil > 0:
             n = min(n, mil)                                                # vision_transformer.py:602-616
         if check_tokens and n + 1 + self.cfg["max_text_len"] > 256 and self.dtype == L.BF16:
             raise NotImplementedError(f"{n} image patches + text exceed the 256-token limit of the fused attention kernels")
-        if select is not None:                                             # the caller's draw (parity tests: the reference's)
-            sel = select.to(self.device, torch.int32).contiguous()
+        over = []
+        if select is not None:
+            sel = select.to(sel.device, torch.int32).contiguous()
             assert sel.shape == (B, n), (tuple(sel.shape), (B, n))
-            counts = torch.minimum(counts, torch.full_like(counts, n))
         else:
             over = (cnt > n).nonzero().flatten().tolist()
             for b in over:                                                 # more valid patches than max_image_len: the reference
                 v = int(cnt[b])                                            # keeps a random subset (multinomial w/o replacement, :633-636)
-                keep = torch.multinomial(torch.ones(v).float(), n).to(self.device)
+                keep = torch.multinomial(torch.ones(v).float(), n).to(sel.device)
                 sel[b, :n] = sel[b, :v].index_select(0, keep)
-            if over:
-                counts = torch.minimum(counts, torch.full_like(counts, n))
-        return RaggedGeometry(sel, counts, hw, n, gh, gw, (B, 3, Hh, Ww))
+        if select is not None or over:                                     # (otherwise no count exceeds n: nothing to clamp, no launch)
+            counts = torch.minimum(counts, torch.full_like(counts, n))
+        return sel, counts, n
+
+    def _bind(self, text_ids: torch.Tensor, text_mask: torch.Tensor, geom, B: int, tag: str, img_type: int = 0) -> PassBuffers:
+        """What every bind ends in: the buffers of (B, tag, image length) with the batch's geometry, token-type row and text.
+        img_type 0: token-type row 1 (callers that need another row set it after); -1: the NLVR2 pair pass."""
+        pb = self.bufs(B, tag, None, None if geom is None else geom.n)
+        self._set_geometry(pb, geom)
+        pb.d.img_type = img_type
+        pb.text_ids = text_ids.to(self.device, torch.int64).contiguous()
+        pb.text_mask = text_mask.to(self.device, torch.int64).contiguous()
+        return pb
+
+    def _im2patch(self, img: torch.Tensor, pat: torch.Tensor, geom, B: int, Hh: int, Ww: int, inverse: bool = False):
+        """image [B,3,Hh,Ww] -> patch rows `pat` (inverse: patch rows -> image, zero outside the selected patches): every patch of the
+        grid (geom None) or the selected ones."""
+        ps, name = self.cfg["patch_size"], "patch2im" if inverse else "im2patch"
+        if geom is None:
+            check(lib.rmcl_im2patch_f32(P(img), P(pat), B, 3, Hh, Ww, ps, int(inverse), stream_ptr()), name)
+        else:
+            check(lib.rmcl_im2patch_sel(P(img), P(pat), P(geom.sel), P(geom.counts), geom.sel.shape[1], B, geom.n, 3, Hh, Ww, ps,
+                                        int(inverse), stream_ptr()), name + "_sel")
 
     def bind_batch(self, text_ids: torch.Tensor, text_mask: torch.Tensor, image, tag: str = "moco",
                    select: torch.Tensor = None) -> PassBuffers:
@@ -649,18 +651,9 @@ class Engine:
             return self._bind_uint8(text_ids, text_mask, image, tag, select)
         img = image.to(self.device, torch.float32).contiguous()
         B, Cc, Hh, Ww = img.shape
-        ps = self.cfg["patch_size"]
         geom = self.patch_geometry(img, select)
-        pb = self.bufs(B, tag, None, None if geom is None else geom.n)
-        self._set_geometry(pb, geom)
-        pb.d.img_type = 0                                                  # token-type row 1; callers that need another row set it after
-        pb.text_ids = text_ids.to(self.device, torch.int64).contiguous()
-        pb.text_mask = text_mask.to(self.device, torch.int64).contiguous()
-        if geom is None:
-            check(lib.rmcl_im2patch_f32(P(img), P(pb.patches32), B, 3, Hh, Ww, ps, 0, stream_ptr()), "im2patch")
-        else:
-            check(lib.rmcl_im2patch_sel(P(img), P(pb.patches32), P(geom.sel), P(geom.counts), geom.sel.shape[1], B, geom.n, 3, Hh, Ww,
-                                        ps, 0, stream_ptr()), "im2patch_sel")
+        pb = self._bind(text_ids, text_mask, geom, B, tag)
+        self._im2patch(img, pb.patches32, geom, B, Hh, Ww)
         return pb
 
     @staticmethod
@@ -701,16 +694,9 @@ class Engine:
             geom = RaggedGeometry(il(g0.sel, g1.sel), il(g0.counts, g1.counts), il(g0.hw, g1.hw), max(g0.n, g1.n), gh, gw,
                                   (2 * B, 3, Hm, Wm))
         img = torch.stack([img0, img1], dim=1).reshape(2 * B, 3, Hm, Wm)
-        pb = self.bufs(2 * B, tag, None, None if geom is None else geom.n)
-        self._set_geometry(pb, geom)
-        pb.d.img_type = -1
-        pb.text_ids = text_ids.to(self.device, torch.int64).repeat_interleave(2, dim=0).contiguous()
-        pb.text_mask = text_mask.to(self.device, torch.int64).repeat_interleave(2, dim=0).contiguous()
-        if geom is None:
-            check(lib.rmcl_im2patch_f32(P(img), P(pb.patches32), 2 * B, 3, Hm, Wm, ps, 0, stream_ptr()), "im2patch")
-        else:
-            check(lib.rmcl_im2patch_sel(P(img), P(pb.patches32), P(geom.sel), P(geom.counts), geom.sel.shape[1], 2 * B, geom.n, 3, Hm, Wm,
-                                        ps, 0, stream_ptr()), "im2patch_sel")
+        pb = self._bind(text_ids.to(self.device, torch.int64).repeat_interleave(2, dim=0),
+                        text_mask.to(self.device, torch.int64).repeat_interleave(2, dim=0), geom, 2 * B, tag, img_type=-1)
+        self._im2patch(img, pb.patches32, geom, 2 * B, Hm, Wm)
         pb.keep_alive = (img,)
         return pb
 
@@ -763,28 +749,9 @@ class Engine:
         geom = None
         if not full:
             sel, counts, hw = select_from_sizes(u8.sizes, gh, gw, ps)
-            n = int(counts.max())
-            mil = self.cfg.get("max_image_len", -1)
-            if isinstance(mil, int) and mil > 0:
-                n = min(n, mil)                                            # vision_transformer.py:602-616
-            if n + 1 + self.cfg["max_text_len"] > 256 and self.dtype == L.BF16:
-                raise NotImplementedError(f"{n} image patches + text exceed the 256-token limit of the fused attention kernels")
-            if select is not None:
-                sel = select.to(torch.int32).contiguous()
-                assert sel.shape == (B, n), (tuple(sel.shape), (B, n))
-                counts = torch.minimum(counts, torch.full_like(counts, n))
-            else:
-                for b in (counts > n).nonzero().flatten().tolist():        # random subset like the reference (:633-636)
-                    v = int(counts[b])
-                    keep = torch.multinomial(torch.ones(v).float(), n)
-                    sel[b, :n] = sel[b, :v].index_select(0, keep)
-                counts = torch.minimum(counts, torch.full_like(counts, n))
+            sel, counts, n = self._cap_selection(sel, counts, counts, select)   # on the host; to the device only afterwards
             geom = RaggedGeometry(sel.to(self.device), counts.to(self.device), hw.to(self.device), n, gh, gw, (B, 3, Hh, Ww))
-        pb = self.bufs(B, tag, None, None if geom is None else geom.n)
-        self._set_geometry(pb, geom)
-        pb.d.img_type = 0                                                  # token-type row 1; callers that need another row set it after
-        pb.text_ids = text_ids.to(self.device, torch.int64).contiguous()
-        pb.text_mask = text_mask.to(self.device, torch.int64).contiguous()
+        pb = self._bind(text_ids, text_mask, geom, B, tag)
         sizes = self._h2d(u8.sizes)
         check(lib.rmcl_image_u8_to_patches(P(data), P(sizes), P(geom.sel) if geom else None, P(geom.counts) if geom else None,
                                            geom.sel.shape[1] if geom else 0, B, geom.n if geom else gh * gw, Hh, Ww, ps, P(self._lut),
@@ -802,16 +769,10 @@ class Engine:
 
     def patches_to_image(self, pat: torch.Tensor, pb: PassBuffers) -> torch.Tensor:
         """patch rows (delta, gradients) of `pb`'s batch back to image layout [B,3,H,W] (zero outside the selected patches)."""
-        ps = self.cfg["patch_size"]
-        if pb.geom is None:
-            S = self.cfg["image_size"]
-            out = torch.empty(pb.B, 3, S, S, dtype=torch.float32, device=self.device)
-            check(lib.rmcl_im2patch_f32(P(out), P(pat), pb.B, 3, S, S, ps, 1, stream_ptr()), "patch2im")
-            return out
-        g = pb.geom
-        out = torch.empty(g.shape, dtype=torch.float32, device=self.device)
-        check(lib.rmcl_im2patch_sel(P(out), P(pat), P(g.sel), P(g.counts), g.sel.shape[1], pb.B, g.n, 3, g.shape[2], g.shape[3], ps, 1,
-                                    stream_ptr()), "patch2im_sel")
+        S = self.cfg["image_size"]
+        shape = (pb.B, 3, S, S) if pb.geom is None else tuple(pb.geom.shape)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self._im2patch(out, pat, pb.geom, pb.B, shape[2], shape[3], inverse=True)
         return out
 
     def make_operand(self, pb: PassBuffers, d1=None, d2=None, out=None) -> torch.Tensor:
@@ -899,10 +860,15 @@ class Engine:
                                         P(self.weights_T() if pb.dtype == L.BF16 else None), stream_ptr()), "encoder_backward")
 
     # ---- Barlow-Twins head (include/rmcl.h rmcl_bt_*) --------------------------------------------------------------
+    def _head_buffers(self, cls, B: int, tag: str):
+        """the per-(batch size, tag) buffers of a head, allocated on first use: cls = BtBuffers / VqaBuffers / Nlvr2Buffers / MlmBuffers"""
+        key = (cls, B, tag)
+        if key not in self._head_bufs:
+            self._head_bufs[key] = cls(self, B)
+        return self._head_bufs[key]
+
     def bt_bufs(self, B: int, tag: str) -> BtBuffers:
-        if (B, tag) not in self._bt_bufs:
-            self._bt_bufs[(B, tag)] = BtBuffers(self, B)
-        return self._bt_bufs[(B, tag)]
+        return self._head_buffers(BtBuffers, B, tag)
 
     def bt_forward(self, bb: BtBuffers, cls: torch.Tensor, training: bool, track: bool):
         """z = barlowtwins_head(cls_feats).  training: batch statistics; track: also update the module's running estimates (the
@@ -943,9 +909,7 @@ class Engine:
 
     # ---- VQA head (include/rmcl.h rmcl_vqa_*) ------------------------------------------------------------------------
     def vqa_bufs(self, B: int, tag: str) -> VqaBuffers:
-        if (B, tag) not in self._vqa_bufs:
-            self._vqa_bufs[(B, tag)] = VqaBuffers(self, B)
-        return self._vqa_bufs[(B, tag)]
+        return self._head_buffers(VqaBuffers, B, tag)
 
     def vqa_targets(self, vb: VqaBuffers, labels, scores):
         """Packs the per-sample label / score lists (``batch["vqa_labels"]`` / ``["vqa_scores"]``, rows may be empty) into ONE pinned
@@ -1017,9 +981,7 @@ class Engine:
 
     # ---- NLVR2 head (the VQA head kernels on the nlvr2_classifier struct) + hard-label CE (include/rmcl.h rmcl_nlvr2_ce) ----------
     def nlvr2_bufs(self, B: int, tag: str) -> Nlvr2Buffers:
-        if (B, tag) not in self._nlvr2_bufs:
-            self._nlvr2_bufs[(B, tag)] = Nlvr2Buffers(self, B)
-        return self._nlvr2_bufs[(B, tag)]
+        return self._head_buffers(Nlvr2Buffers, B, tag)
 
     def nlvr2_labels(self, nb: Nlvr2Buffers, answers):
         """batch["answers"] (bools, or 0 / 1; objectives.py:1012-1013 casts them to long) -> nb.labels.  Anything else is a ValueError
@@ -1056,9 +1018,7 @@ class Engine:
 
     # ---- MLM head (include/rmcl.h rmcl_mlm_*) ------------------------------------------------------------------------
     def mlm_bufs(self, B: int, tag: str) -> MlmBuffers:
-        if (B, tag) not in self._mlm_bufs:
-            self._mlm_bufs[(B, tag)] = MlmBuffers(self, B)
-        return self._mlm_bufs[(B, tag)]
+        return self._head_buffers(MlmBuffers, B, tag)
 
     def mlm_weights_T(self) -> torch.Tensor:
         """decoder.weight^T [D, vocab rounded up to 128] in the engine's operand type, re-derived when the masters changed"""
@@ -1165,13 +1125,11 @@ class Engine:
         pat32 = torch.empty(B * n, d.patch_k, dtype=torch.float32, device=self.device)
         op = pat32 if self.dtype == L.F32 else torch.empty(B * n, d.patch_k, dtype=torch.bfloat16, device=self.device)
         rg = None
+        self._im2patch(img, pat32, geom, B, Hh, Ww)
         if geom is None:
-            check(lib.rmcl_im2patch_f32(P(img), P(pat32), B, 3, Hh, Ww, ps, 0, stream_ptr()), "im2patch")
             ii, jj = torch.meshgrid(torch.arange(g), torch.arange(g), indexing="ij")
             patch_index = torch.stack([ii, jj], dim=-1).reshape(1, g * g, 2).expand(B, -1, -1)
         else:
-            check(lib.rmcl_im2patch_sel(P(img), P(pat32), P(geom.sel), P(geom.counts), geom.sel.shape[1], B, n, 3, Hh, Ww, ps, 0,
-                                        stream_ptr()), "im2patch_sel")
             pos_tok = torch.empty(B, n + 1, d.D, dtype=torch.float32, device=self.device)
             rg = L.Ragged(sel=geom.sel.data_ptr(), counts=geom.counts.data_ptr(), hw=geom.hw.data_ptr(), sel_ld=geom.sel.shape[1],
                           gw=geom.gw, G0=g, pos_tok=pos_tok.data_ptr(), dpos_tok=0)

@@ -11,6 +11,7 @@ import torch
 from ... import _lib as L
 from ..._lib import lib, check, P, I64
 from ...runtime import stream_ptr
+from ...attack.pgd_attack_vilt import device_image
 from . import dist_utils
 
 
@@ -112,11 +113,7 @@ def compute_itm_wpa(pl_module, batch):
     itm_labels = torch.cat([torch.ones(pos_len), torch.zeros(Bn - pos_len)]).to(dev)
     forced = getattr(pl_module, "itm_labels_override", None)            # test hook: fix the 50/50 draw
     itm_labels = forced.to(dev).float() if forced is not None else itm_labels[torch.randperm(Bn, device=dev)]
-    img, fimg = batch["image"][0].to(dev), batch["false_image_0"][0].to(dev)
-    if hasattr(img, "tables"):                                          # decoded bytes (collate_raw_uint8): MinMaxResize on the device first
-        img, fimg = eng.resize_raw(img), eng.resize_raw(fimg)
-    if hasattr(img, "float_image"):                                     # byte batches (collate_uint8): the mix of the two views needs pixels
-        img, fimg = img.float_image(), fimg.float_image()
+    img, fimg = device_image(eng, batch["image"][0]), device_image(eng, batch["false_image_0"][0])   # the mix of the two views needs pixels
     images = torch.where(itm_labels.view(-1, 1, 1, 1) == 1, img, fimg)                 # :722-730
 
     pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], images, tag="itm")
