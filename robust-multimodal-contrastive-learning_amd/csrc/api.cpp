@@ -354,6 +354,7 @@ int rmcl_pgd_step_fused(const void* grad, int dtype, float* delta, uint32_t* ama
   return rmcl_pgd_update_fused(grad, dtype, delta, amax_scratch, B, per_sample, lr, eps, base, operand, operand_dtype, flags, (hipStream_t)stream);
 }
 int rmcl_delta_channel_norm(const float* delta, float* out, int64_t rows, int C, int pp, void* stream) {
+  RMCL_REQUIRE(delta && out, "delta_channel_norm: NULL argument");
   return rmcl_delta_chan_norm(delta, out, rows, C, pp, (hipStream_t)stream);
 }
 int rmcl_ema_f32(float* k, const float* q, void* k_lp, float m, int64_t n, void* stream) {
@@ -365,6 +366,7 @@ int rmcl_enqueue_f32(float* queue, const float* keys, int n, int proj, int64_t K
   return rmcl_enqueue(queue, keys, n, proj, Kq, ptr, (hipStream_t)stream);
 }
 int rmcl_cast_f32(const float* in, void* out, int dtype, int64_t n, void* stream) {
+  RMCL_REQUIRE(in && out, "cast: NULL argument");
   return rmcl_cast(in, out, dtype, n, (hipStream_t)stream);
 }
 int rmcl_adamw_f32(float* p, const float* g, float* m, float* v, void* p_lp, const int64_t* seg_end, const float* seg_lr_mult,
@@ -404,6 +406,7 @@ int rmcl_wpa_cost_finish(float* cost, const int32_t* txt_valid, const int32_t* i
 int rmcl_wpa_distance(const float* cost, const float* T, const float* w, float* dist, float* dsim, int B, int Lt, int Li, int ld,
                       void* stream) {
   RMCL_REQUIRE(cost && T && dist, "wpa_distance: NULL argument");
+  RMCL_REQUIRE(w || !dsim, "wpa_distance: NULL argument (dsim needs w)");
   return rmcl_wpa_dist(cost, T, w, dist, dsim, B, Lt, Li, ld, (hipStream_t)stream);
 }
 int rmcl_itm_fwd(const float* cls, const float* W, const float* bias, const int32_t* labels, float* logits, float* dlogits,

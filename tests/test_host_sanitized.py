@@ -62,6 +62,11 @@ expect_error(lib.rmcl_infonce_split_bf16(None, None, None, 4, 128, C.c_int64(102
 expect_error(lib.rmcl_image_u8_to_patches(None, None, None, None, 0, 4, 144, 384, 384, 32, None, None, None), "u8 NULL")
 expect_error(lib.rmcl_grad_ready_wait(-1, None), "grad_ready_wait")
 expect_error(lib.rmcl_pgd_step(None, 0, None, None, 4, C.c_int64(16), C.c_float(0.1), C.c_float(0.1), None), "pgd NULL")
+expect_error(lib.rmcl_cast_f32(None, None, 1, C.c_int64(4), None), "cast NULL")
+expect_error(lib.rmcl_cast_f32(one, None, 0, C.c_int64(4), None), "cast NULL out")
+expect_error(lib.rmcl_delta_channel_norm(None, None, C.c_int64(1), 3, 4, None), "delta_channel_norm NULL")
+expect_error(lib.rmcl_delta_channel_norm(one, None, C.c_int64(1), 3, 4, None), "delta_channel_norm NULL out")
+expect_error(lib.rmcl_wpa_distance(one, one, None, one, one, 1, 1, 1, 4, None), "wpa_distance: dsim without w")
 assert lib.rmcl_infonce_ws_bytes(64, C.c_int64(65536)) > 0 and lib.rmcl_attention_scratch_elems(64, 12, 185) > 0
 print("SANITIZED_HOST_OK", n_err)
 '''
