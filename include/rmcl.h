@@ -432,7 +432,11 @@ int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, c
 int rmcl_heads_forward(const rmcl_dims* d, const float* pool32, const float* head32, const float* xn,
                        void* hstash, float* cls_feats, float* q, void* stream);
 /* The same with flags.  RMCL_HEADS_NO_WGRAD: the matching rmcl_heads_backward will be called with grads32 = NULL (key pass, PGD
- * and text-attack passes: data gradients only) - the pooler input is then not stashed and one launch less is issued.         */
+ * and text-attack passes: data gradients only) - the pooler input is then not stashed and one launch less is issued.  The library
+ * remembers (on the host) which stash buffers last saw such a forward: rmcl_heads_backward on one of them with grads32 != NULL
+ * returns -1 instead of forming the pooler weight gradient from a stale input.  The record is per stash address, is updated when
+ * the call is made (not when the enqueued work executes) and is never dropped: only a later forward without the flag on the same
+ * address clears it.                                                                                                         */
 #define RMCL_HEADS_NO_WGRAD 1
 int rmcl_heads_forward2(const rmcl_dims* d, const float* pool32, const float* head32, const float* xn,
                         void* hstash, float* cls_feats, float* q, int flags, void* stream);

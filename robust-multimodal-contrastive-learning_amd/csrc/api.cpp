@@ -3,7 +3,9 @@
 #include "rmcl_common.h"
 #include "kernels.h"
 #include "../../include/rmcl.h"
+#include <mutex>
 #include <string>
+#include <unordered_set>
 
 static thread_local std::string g_err;
 extern "C" void rmcl_set_error(const char* msg) { g_err = msg ? msg : ""; }
@@ -57,6 +59,13 @@ size_t carve_heads(const rmcl_dims& d, void* base, HeadStash* hs) {
   if (hs) *hs = h;
   return off;
 }
+// Stashes whose most recent rmcl_heads_forward2 ran with RMCL_HEADS_NO_WGRAD: their cls_in was not written, so a backward that forms
+// the pooler weight gradient from it is refused.  Host bookkeeping only (no device read, no synchronise).  The record is keyed by the
+// stash ADDRESS, is updated when the host call is made (not when the enqueued work runs: a backward captured into a graph apart from
+// its forward is judged by the calls made at capture time) and is never dropped - an address leaves the set only through a later
+// plain forward on it, so a freed and re-used buffer keeps its entry until its next forward, which every legal backward follows.
+std::mutex g_nowgrad_mu;
+std::unordered_set<const void*> g_nowgrad_stash;
 GemmArgs ga(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc) {
   GemmArgs g{};
   g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -158,6 +167,10 @@ int rmcl_heads_forward2(const rmcl_dims* d, const float* pool32, const float* he
   // hidden_states[:, 0] (heads.py:17): a compact copy for the pooler's weight gradient - or, when the matching backward forms none
   // (key pass, PGD passes), the pooler GEMM reads the rows in place (row stride N * D) and the gather launch is not issued
   const bool stash_in = !(flags & RMCL_HEADS_NO_WGRAD);
+  {
+    std::lock_guard<std::mutex> lk(g_nowgrad_mu);
+    if (stash_in) g_nowgrad_stash.erase(hstash); else g_nowgrad_stash.insert(hstash);
+  }
   if (stash_in) RMCL_TRY(rmcl_gather_rows(xn, h.cls_in, B, D, 1, N, 0, s));
   {
     GemmArgs g = stash_in ? ga(h.cls_in, pool32 + y.pool_w, h.pooled, B, D, D, D, D, D)
@@ -190,6 +203,10 @@ int rmcl_heads_forward2(const rmcl_dims* d, const float* pool32, const float* he
 int rmcl_heads_backward(const rmcl_dims* d, const float* pool32, const float* head32, void* hstash, const float* dq,
                         const float* dcls_extra, float* dcls, float* G, void* workspace, void* stream) {
   RMCL_REQUIRE(d && pool32 && hstash && dcls && workspace, "heads_backward: NULL argument");
+  if (G) {
+    std::lock_guard<std::mutex> lk(g_nowgrad_mu);
+    RMCL_REQUIRE(!g_nowgrad_stash.count(hstash), "heads_backward: grads32 given, but this stash's forward ran with RMCL_HEADS_NO_WGRAD (no pooler input kept)");
+  }
   rmcl_layout y;
   rmcl_param_layout(d, &y);
   HeadStash h;

@@ -19,8 +19,6 @@ EXEMPT = {
     "rmcl_prof_begin": "hipEvent timing of GEMM launches for bench.py's roofline object; no numerical result to pin",
     "rmcl_prof_end": "second half of rmcl_prof_begin",
     "rmcl_set_prefetch_stream": "stream of the stash-prefetch experiment (tune key 12, off by default)",
-    "rmcl_heads_forward2": "driven by Engine.heads_forward in the path tests (tests/test_path_gpu.py), never by name",
-    "rmcl_heads_backward": "driven by Engine.heads_backward in the path tests (tests/test_path_gpu.py), never by name",
 }
 
 
@@ -75,3 +73,28 @@ def test_null_operands_are_rejected_before_any_launch():
     _rejected(lib.rmcl_itm_bwd(buf, buf, buf, None, None, None, 1, 4, f(1.0), None), "itm_bwd")
     _rejected(lib.rmcl_ln_fold(None, buf, buf, buf, None), "ln_fold")
     _rejected(lib.rmcl_weight_transpose_bf16(None, buf, buf, None), "weight_transpose")
+
+
+def test_heads_arguments_are_rejected_before_any_launch():
+    """rmcl_heads_forward2 / rmcl_heads_backward: every required operand as NULL, an unknown flag bit, and a backward with neither dq nor
+    dcls_extra.  Host buffers throughout, as above."""
+    lib = _lib.lib
+    buf = (C.c_float * 16)()
+    d = _lib.Dims(B=1, L=4, P=3, D=64, H=1, layers=1, mlp=64, patch_k=64, proj=64, vocab=64, dtype=_lib.F32, exact=1, Pp=3)
+    dp = C.byref(d)
+    fwd = [dp, buf, buf, buf, buf, buf, buf]                                     # d, pool32, head32, xn, hstash, cls_feats, q
+    for i in (0, 1, 3, 4, 5):
+        a = list(fwd)
+        a[i] = None
+        _rejected(lib.rmcl_heads_forward2(*a, 0, None), "heads_forward")
+    assert lib.rmcl_heads_forward2(*fwd, 2, None) == -1
+    assert b"heads_forward" in lib.rmcl_last_error() and b"unknown flag" in lib.rmcl_last_error()
+    bwd = [dp, buf, buf, buf, buf, buf, buf, None, buf]                          # d, pool32, head32, hstash, dq, dcls_extra, dcls, grads32, workspace
+    for i in (0, 1, 3, 6, 8):
+        a = list(bwd)
+        a[i] = None
+        _rejected(lib.rmcl_heads_backward(*a, None), "heads_backward")
+    a = list(bwd)
+    a[4] = a[5] = None
+    assert lib.rmcl_heads_backward(*a, None) == -1
+    assert b"heads_backward" in lib.rmcl_last_error() and b"neither dq nor dcls_extra" in lib.rmcl_last_error()
