@@ -358,6 +358,18 @@ int rmcl_mlm_backward(const rmcl_mlm_head* h, const float* params, const void* p
 int rmcl_mlm_logits(const rmcl_mlm_head* h, const float* params, const void* params_lp, int dtype, float* ws, int rows, int rows_out,
                     float* logits, int64_t ldl, void* stream);
 
+/* ---- Text attack on the fine-tuning tasks (GreedyAttack_vqa / GreedyAttack_nlvr2) ------------------------------------------
+ * get_important_scores (attack/greedy_attack_vilt.py:221-228) on the device: the L1 norm over the hidden columns of the MEAN saliency
+ * gradient over a word's sub-word tokens,
+ *   out[b, w] = sum_d | (1 / len) * sum_{t = start .. start + len - 1} g[row0 + b * row_step, t, d] |
+ * g [R, L, D] f32: the `dtext` buffer rmcl_encoder_backward fills, R >= row0 + (B - 1) * row_step + 1 sequences (row0 = 1, row_step = 2:
+ * the image_1 sequences of an NLVR2 pair pass).  spans [B, W, 2] int32 = (first token position, token count) per word; positions count
+ * [CLS] as 0.  A count <= 0 marks a padding entry: it writes 0.  A span that leaves [0, L) is cut to the tokens inside (nothing is read
+ * out of bounds; the divisor stays the stated count).  out [B, W] f32.  fp32 accumulation, tokens summed in ascending order, one wave
+ * per output, no float atomics, no scratch: two identical calls give identical bits.
+ * 1 <= B <= 65536, 1 <= W <= 4096, 1 <= L <= 4096, 4 <= D <= 8192 with D % 4 == 0, row0 >= 0, row_step >= 1.                      */
+int rmcl_word_saliency(const float* g, const int32_t* spans, float* out, int B, int W, int L, int D, int row0, int row_step, void* stream);
+
 /* One joint text+image encoder forward up to transformer.norm: replaces ViLTransformerSS.infer /
  * infer_k (vilt_module.py:275-418) minus the pooler.  params32: fp32 arena; params_lp: bf16
  * shadow arena (NULL when dtype is F32).  text_ids/text_mask [B,L] int64; patches [B*P,patch_k]

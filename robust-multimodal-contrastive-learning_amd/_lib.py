@@ -105,6 +105,7 @@ EXPORTS = (
     "rmcl_nlvr2_ce",
     "rmcl_visual_embed", "rmcl_encoder_forward_rank", "rmcl_irtr_score", "rmcl_irtr_ce", "rmcl_irtr_bwd",
     "rmcl_mlm_ws_floats", "rmcl_mlm_compact", "rmcl_mlm_weight_transpose", "rmcl_mlm_forward", "rmcl_mlm_backward", "rmcl_mlm_logits",
+    "rmcl_word_saliency",
 )
 
 

@@ -88,17 +88,19 @@ class GreedyAttack:
     def calc_words_to_sub_words(self, words, batch_size):
         self.words_to_sub_words = [WS.words_to_sub_words(self.tokenizer, words[i], self.max_length) for i in range(batch_size)]
 
-    def compute_word_importance(self, words, input_ids, grads, batch_size):
+    def compute_word_importance(self, words, input_ids, grads, batch_size, scores=None):
         """compute_word_importance (:266-310) behind get_grad: per sentence the attackable word with the largest importance
         (None when every word is filtered, already replaced, or the 20 % / max_loops budget is spent).
-        grads [B, L, D] host array of the saliency gradients, input_ids [B, L] host tensor."""
+        grads [B, L, D] host array of the saliency gradients, input_ids [B, L] host tensor.  scores: the per-sentence importance
+        lists when `word_scores` already produced them (grads is then not read)."""
         sep_id = self.tokenizer.convert_tokens_to_ids("[SEP]")
         sep_idx = (input_ids == sep_id).nonzero()
         assert len(sep_idx) == batch_size
         known = self.synonyms if hasattr(self.synonyms, "__contains__") else None
         replace_idx = []
         for i in range(batch_size):
-            norms = self.get_important_scores(grads[i][1:], self.words_to_sub_words[i])     # [1:]: the map skips [CLS]
+            norms = scores[i] if scores is not None else \
+                self.get_important_scores(grads[i][1:], self.words_to_sub_words[i])        # [1:]: the map skips [CLS]
             order = torch.topk(torch.tensor(norms), k=len(norms)).indices
             budget = min(int(sep_idx[i][1] * 0.2), self.max_loops)                            # at most 20 % of the words
             pick = None
@@ -152,6 +154,35 @@ class GreedyAttack:
         """split_forward: [(candidate losses, index of the best candidate or -1)] per sample"""
         raise NotImplementedError(f"split_forward of {self.contrastive_framework} isn't implemented.")
 
+    def word_scores(self, pl_module, pb, grads, Bn):
+        """Per-sentence word importance lists computed from the device gradient, or None: the host path (the whole gradient is
+        copied and `get_important_scores` runs per sentence) - the default, what the MoCo and Barlow-Twins attacks run."""
+        return None
+
+    def accept(self, losses, best_j):
+        """Is the best candidate of a changed sample taken?  (:568: only an index > 0.)"""
+        return best_j > 0
+
+    def bind_batch(self, pl_module, batch, ids, masks):
+        """(pass buffers of the batch with the clean image, its operand shared by every loop)"""
+        eng = pl_module.engine
+        pb = eng.bind_batch(ids, masks, batch["image"][0], tag="txtatk")
+        return pb, eng.make_operand(pb)
+
+    def saliency_rows(self, pb):
+        """sequences whose word-embedding gradient get_grad writes (rows of the `de` buffer / Lt)"""
+        return pb.B
+
+    def set_text(self, pb, ids, masks):
+        pb.text_ids, pb.text_mask = ids, masks
+
+    def bind_candidates(self, pl_module, pb, op, own, cids, cmasks):
+        """the candidate pass: sentence r with the image of sample own[r]"""
+        pc = pl_module.engine.twin(pb, "txtatk_cand", owner=own)
+        pc.text_ids, pc.text_mask = cids, cmasks
+        torch.index_select(op.view(pb.B, -1), 0, own, out=pc.patchesT.view(int(own.numel()), -1))
+        return pc
+
     def adv_attack_samples(self, pl_module, batch, k_modality):
         if self.tokenizer is not None:
             return self._attack_words(pl_module, batch, k_modality)
@@ -174,19 +205,20 @@ class GreedyAttack:
         self.calc_words_to_sub_words(cur_words, Bn)
         self.replace_history = [set() for _ in range(Bn)]
         self.changes_verification = [0] * Bn
-        pb = eng.bind_batch(ids_host.to(dev), masks_host.to(dev), batch["image"][0], tag="txtatk")
-        op = eng.make_operand(pb)                                   # clean image, shared by every loop
-        de = torch.empty(Bn * Lt, pb.d.D, device=dev)
-        k = k_modality.to(dev, torch.float32).contiguous()
+        pb, op = self.bind_batch(pl_module, batch, ids_host.to(dev), masks_host.to(dev))     # clean image, shared by every loop
+        de = torch.empty(self.saliency_rows(pb) * Lt, eng.cfg["hidden_size"], device=dev)
+        k = None if k_modality is None else k_modality.to(dev, torch.float32).contiguous()
         self.bind_keys(pl_module, pb, k)
         text = [" ".join(w) for w in cur_words]
         self.trace = []                                             # per loop: (replace_idx, all_new_text, all_num, picks) for tests
+        self.loss_trace = []                                        # per loop: the candidate losses, flat in candidate order
 
         for loop in range(self.max_loops):
-            pb.text_ids = ids_host.to(dev)
-            pb.text_mask = masks_host.to(dev)
+            self.set_text(pb, ids_host.to(dev), masks_host.to(dev))
             ctx, grads, _ = self.get_grad(pl_module, pb, op, de)
-            replace_idx = self.compute_word_importance(cur_words, ids_host, grads.cpu().numpy(), Bn)
+            scores = self.word_scores(pl_module, pb, grads, Bn)
+            replace_idx = self.compute_word_importance(cur_words, ids_host, grads.cpu().numpy() if scores is None else None, Bn,
+                                                       scores=scores)
             all_new_text, all_num, changed = self.construct_new_samples(replace_idx, cur_words, Bn)
             n_real = len(all_new_text)
             if n_real > Bc:
@@ -195,15 +227,14 @@ class GreedyAttack:
             owner = [b for b in range(Bn) for _ in range(all_num[b])]
             pad = Bc - n_real
             own = torch.tensor(owner + [0] * pad, device=dev)
-            pc = eng.twin(pb, "txtatk_cand", owner=own)
-            pc.text_ids = torch.cat([cids, ids_host[:1].expand(pad, Lt)]).to(dev).contiguous()
-            pc.text_mask = torch.cat([cmasks, masks_host[:1].expand(pad, Lt)]).to(dev).contiguous()
-            torch.index_select(op.view(Bn, -1), 0, own, out=pc.patchesT.view(Bc, -1))
+            pc = self.bind_candidates(pl_module, pb, op, own, torch.cat([cids, ids_host[:1].expand(pad, Lt)]).to(dev).contiguous(),
+                                      torch.cat([cmasks, masks_host[:1].expand(pad, Lt)]).to(dev).contiguous())
             self.bind_candidate_keys(pc, k, own)
             picks = self.score(pl_module, pc, ctx, owner, n_real, Bn)
+            self.loss_trace.append([x for losses, _ in picks for x in losses])
             count = 0
             for b, (losses, best_j) in enumerate(picks):
-                if changed[b] and best_j > 0:
+                if changed[b] and self.accept(losses, best_j):
                     self.changes_verification[b] += 1
                     cur_words[b] = all_new_text[best_j + count].split(" ")
                     self.words_to_sub_words[b] = WS.words_to_sub_words(tok, cur_words[b], self.max_length)
@@ -411,3 +442,234 @@ class GreedyAttack_barlowtwins(GreedyAttack):
                 j += 1
             out.append((losses, best_j))
         return out
+
+
+# ---- the fine-tuning tasks (greedy_attack_vilt.py:835-1043 NLVR2, :1263-1478 VQA) ------------------------------------------------------
+HEAD_ROWS = 256                       # include/rmcl.h: the classifier launchers take at most 256 rows
+
+
+def _chunks(n: int, size: int = HEAD_ROWS):
+    return [(s, min(n, s + size)) for s in range(0, n, size)]
+
+
+def vqa_candidate_rows(eng, cls: torch.Tensor, labels: torch.Tensor, scores: torch.Tensor, A: int, out: torch.Tensor = None,
+                       tag: str = "txtatk_cand") -> torch.Tensor:
+    """Per-row BCE sums (rmcl_vqa_bce rows[:, 0]) of vqa_classifier(cls [R, D]) against the label / score tables [R, A] (device, one
+    row per cls row), R of any size: the head launcher takes at most 256 rows, so the rows go through it in chunks.  Every row of
+    the head and of the loss is independent of the others, so the chunking changes no value.  Returns `out` [R] on the device."""
+    R = int(cls.shape[0])
+    out = torch.empty(R, dtype=torch.float32, device=eng.device) if out is None else out
+    for s, e in _chunks(R):
+        vb = eng.vqa_bufs(e - s, tag)
+        vb.labels, vb.scores, vb.A = labels[s:e].contiguous(), scores[s:e].contiguous(), A
+        eng.vqa_forward(vb, cls[s:e])
+        eng.vqa_bce(vb, 1.0, want_dz=False)
+        out[s:e].copy_(vb.rows[:, 0])
+    return out
+
+
+def nlvr2_candidate_rows(eng, cls2: torch.Tensor, labels: torch.Tensor, out: torch.Tensor = None, tag: str = "txtatk_cand") -> torch.Tensor:
+    """Per-row CE (rmcl_nlvr2_ce rows) of nlvr2_classifier(cls2 [R, 2 hidden]) against labels [R] (int32, device), in chunks of 256."""
+    R = int(cls2.shape[0])
+    out = torch.empty(R, dtype=torch.float32, device=eng.device) if out is None else out
+    for s, e in _chunks(R):
+        nb = eng.nlvr2_bufs(e - s, tag)
+        nb.labels.copy_(labels[s:e])
+        eng.nlvr2_forward(nb, cls2[s:e])
+        eng.nlvr2_ce(nb, 1.0, want_dz=False)
+        out[s:e].copy_(nb.rows)
+    return out
+
+
+def word_spans(mappings, W: int) -> torch.Tensor:
+    """words_to_sub_words maps -> spans [B, W, 2] int32 (first token position counting [CLS] as 0, token count); a word's tokens
+    are consecutive (calc_words_to_sub_words :346-360).  Entries behind a sentence's words: (0, 0)."""
+    sp = np.zeros((len(mappings), W, 2), dtype=np.int32)
+    for b, m in enumerate(mappings):
+        for w in range(len(m)):
+            if len(m[w]):
+                sp[b, w] = (int(m[w][0]) + 1, len(m[w]))                      # + 1: the reference reads grads[i][1:] (:276)
+    return torch.from_numpy(sp)
+
+
+class _TaskAttack(GreedyAttack):
+    """What GreedyAttack_vqa and GreedyAttack_nlvr2 share.  WORD level only (a tokenizer is required).  The loss of a batch is the
+    mean of per-row terms (VQA: the row sums of the BCE; NLVR2: the row CE), so with s_b the clean rows and c_ij the candidates'
+    the reference's batch loss for candidate j of sample i is (sum_b s_b + drift_i + c_ij - s_i) / B, where drift_i =
+    sum_{r < i} (c_{r,last} - s_r): `t_save = ori_z[i]` (:912, :1343) is a view, so the restore (:929, :1367) is a no-op and row r keeps
+    its LAST candidate while later samples are scored.  The running maximum starts at -1 (:911, :1342; MoCo's starts at the clean
+    loss), the first strict maximum wins, and a changed sample takes it when its loss is > 0 (:1010, :1445) - index 0 included."""
+
+    device_scores = True               # word importance from rmcl_word_saliency (False: the base class's host path)
+
+    def __init__(self, config, framework, tokenizer=None, stopwords=None, synonyms=None):
+        super().__init__(config, framework, None, tokenizer, stopwords, synonyms)
+        self._de = None                # the whole dtext buffer of the last get_grad (what rmcl_word_saliency reads)
+        if self.tokenizer is None:
+            raise NotImplementedError(
+                f"{framework}_attacked with text_view=True runs the word-level attack only: config['tokenizer'] must be a tokenizer "
+                f"object or the path of a local vocabulary file (got {config.get('tokenizer')!r}; a hub name cannot be fetched) and "
+                "config['embedding_path'] the local counter-fitted vector file")
+
+    def bind_keys(self, pl_module, pb, k):
+        pass
+
+    def saliency_of(self, pb):
+        """(sequence of sentence 0, sequence step) of the saliency rows inside get_grad's gradient buffer"""
+        return 0, 1
+
+    def word_scores(self, pl_module, pb, grads, Bn):
+        if not self.device_scores:
+            return None
+        W = max(1, max(len(m) for m in self.words_to_sub_words))
+        eng = pl_module.engine
+        spans = word_spans(self.words_to_sub_words, W).to(eng.device)
+        row0, step = self.saliency_of(pb)
+        sal = eng.word_saliency(self._de, spans, self.max_length, row0, step).cpu().numpy()    # the loop's one read-back: [B, W]
+        return [[float(x) for x in sal[b, :len(self.words_to_sub_words[b])]] for b in range(Bn)]
+
+    def accept(self, losses, best_j):
+        return best_j >= 0 and losses[best_j] > 0
+
+    @staticmethod
+    def select(s, c, owner, n_real, Bn):
+        """[(losses, first strict maximum starting from -1)] per sample from the clean rows s [B] and the candidate rows c [n_real]"""
+        tot = float(sum(s))
+        out, drift, start = [], 0.0, 0
+        for b in range(Bn):
+            idx = [i for i in range(start, n_real) if owner[i] == b]
+            start = idx[-1] + 1
+            best, best_j, losses = -1.0, -1, []
+            for j, r in enumerate(idx):
+                lj = (tot + drift + (c[r] - s[b])) / Bn
+                losses.append(lj)
+                if lj > best:
+                    best, best_j = lj, j
+            drift += c[idx[-1]] - s[b]
+            out.append((losses, best_j))
+        return out
+
+
+class GreedyAttack_vqa(_TaskAttack):
+    """attack/greedy_attack_vilt.py:1263-1478: the greedy attack maximising compute_vqa's loss (BCE-with-logits mean x vqav2_label_size)
+    of the clean image with the attacked question.  The reference attacks a deep copy of the model: no weight gradient is formed."""
+
+    def __init__(self, config, tokenizer=None, stopwords=None, synonyms=None):
+        super().__init__(config, "vqa", tokenizer, stopwords, synonyms)
+        self._tab = None
+
+    def bind_batch(self, pl_module, batch, ids, masks):
+        eng = pl_module.engine
+        pb, op = super().bind_batch(pl_module, batch, ids, masks)
+        self._tab = eng.vqa_targets(eng.vqa_bufs(pb.B, "txtatk"), batch["vqa_labels"], batch["vqa_scores"])
+        return pb, op
+
+    def get_grad(self, pl_module, pb, op, de):
+        """get_grad (:1284-1331): forward, BCE mean x N (incoming gradient 1), backward to the OUTPUT of word_embeddings.
+        Returns (per-row BCE sums [B], grads view [B,L,D] = `de`, the cls rows)."""
+        eng = pl_module.engine
+        vb = self._tab
+        eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
+        eng.heads_forward(pb, key=False, want_q=False, wgrad=False)
+        eng.vqa_forward(vb, pb.cls)
+        eng.vqa_bce(vb, 1.0, want_dz=True)
+        s = vb.rows[:, 0].clone()
+        dcls = eng.vqa_backward(vb, vb.dz, with_grads=False)
+        eng.heads_backward(pb, None, dcls, with_grads=False)
+        eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=None, dtext=de)
+        self._de = de
+        return s, de.view(pb.B, pb.d.L, -1), pb.cls
+
+    def score(self, pl_module, pc, ctx, owner, n_real, Bn):
+        """split_forward (:1333-1369): candidates through the encoder and vqa_classifier, each against its OWNER's label / score
+        tables (gathered on the device); the per-row BCE sums of batch and candidates come back in one transfer."""
+        eng = pl_module.engine
+        eng.encoder_forward(pc, key=False, mode=L.MODE_INFER, patchesT=pc.patchesT, cls_tail=True)
+        eng.heads_forward(pc, key=False, want_q=False, wgrad=False)
+        own = torch.tensor(owner[:n_real], device=eng.device)
+        vb = self._tab
+        rows = torch.empty(Bn + n_real, dtype=torch.float32, device=eng.device)
+        rows[:Bn].copy_(ctx)
+        vqa_candidate_rows(eng, pc.cls[:n_real], vb.labels.index_select(0, own), vb.scores.index_select(0, own), vb.A, out=rows[Bn:])
+        host = rows.cpu().tolist()
+        return self.select(host[:Bn], host[Bn:], owner, n_real, Bn)
+
+
+class GreedyAttack_nlvr2(_TaskAttack):
+    """attack/greedy_attack_vilt.py:835-1043: the same attack on CE(nlvr2_classifier([cls(image_0, type 1) | cls(image_1, type 2)]),
+    answers).  Runs on the pair pass (2B sequences for the batch, 2 n_candidates B for the candidates) where config["nlvr2_pair_pass"]
+    is on, else on the two-pass form.  Saliency: the reference's hook on word_embeddings fires once per infer call and only
+    emb_grads[0] is read (:894) - the call whose backward runs FIRST, which is the SECOND forward call (infer2: image_1 with token
+    type 2; autograd runs the later-built branch first).  The saliency is therefore the text gradient of the image_1 pass alone, not
+    the sum of both: the odd sequences of the pair pass (tests/golden/txtatk_nlvr2_*.npz records both per-pass gradients)."""
+
+    def __init__(self, config, tokenizer=None, stopwords=None, synonyms=None):
+        super().__init__(config, "nlvr2", tokenizer, stopwords, synonyms)
+        self._nb = None
+
+    def bind_batch(self, pl_module, batch, ids, masks):
+        from ..vilt.modules.objectives import Nlvr2Pass
+        eng = pl_module.engine
+        npass = Nlvr2Pass.bind(pl_module, dict(batch, text_ids=ids, text_masks=masks), "txtatk")
+        npass.clean_operands(full_buffer=False)
+        self._nb = eng.nlvr2_bufs(npass.B, "txtatk")
+        eng.nlvr2_labels(self._nb, batch["answers"])
+        return npass, npass.ops
+
+    def saliency_rows(self, npass):
+        return npass.views[-1].B
+
+    def saliency_of(self, npass):
+        return (1, 2) if npass.pair else (0, 1)
+
+    def set_text(self, npass, ids, masks):
+        for pv in npass.views:
+            pv.text_ids = ids.repeat_interleave(2, dim=0) if npass.pair else ids
+            pv.text_mask = masks.repeat_interleave(2, dim=0) if npass.pair else masks
+
+    def get_grad(self, pl_module, npass, ops, de):
+        """get_grad (:856-898).  Returns (per-row CE [B], grads view [B,L,D]: the image_1 sequences of `de`, the cls rows)."""
+        eng = pl_module.engine
+        nb = self._nb
+        cls2 = npass.forward(L.MODE_DATA, wgrad=False)
+        eng.nlvr2_forward(nb, cls2)
+        eng.nlvr2_ce(nb, 1.0, want_dz=True)
+        s = nb.rows.clone()
+        dcls2 = eng.nlvr2_backward(nb, nb.dz, with_grads=False)
+        D = npass.views[0].d.D
+        for i, (pv, op) in enumerate(zip(npass.views, npass.ops)):
+            if not npass.pair and i == 0:
+                continue                                  # the image_0 pass's text gradient is never read (emb_grads[0] is infer2's)
+            dc = dcls2.view(2 * npass.B, D) if npass.pair else dcls2[:, i * D:(i + 1) * D].contiguous()
+            eng.heads_backward(pv, None, dc, with_grads=False)
+            eng.encoder_backward(pv, L.MODE_DATA, op, pv.dcls, cls_only=True, dpatches=None, dtext=de)
+        self._de = de
+        row0, step = self.saliency_of(npass)
+        return s, de.view(-1, npass.views[0].d.L, D)[row0::step], cls2
+
+    def bind_candidates(self, pl_module, npass, ops, own, cids, cmasks):
+        from ..vilt.modules.objectives import Nlvr2Pass
+        eng = pl_module.engine
+        Bc = int(own.numel())
+        views = []
+        for i, (pv, op) in enumerate(zip(npass.views, ops)):
+            o = torch.stack([2 * own, 2 * own + 1], dim=1).reshape(-1) if npass.pair else own
+            pc = eng.twin(pv, f"txtatk_cand_{i}", owner=o)
+            pc.text_ids = cids.repeat_interleave(2, dim=0) if npass.pair else cids
+            pc.text_mask = cmasks.repeat_interleave(2, dim=0) if npass.pair else cmasks
+            torch.index_select(op.view(pv.B, -1), 0, o, out=pc.patchesT.view(int(o.numel()), -1))
+            views.append(pc)
+        cpass = Nlvr2Pass(eng, views, Bc, npass.pair)
+        cpass.ops = [pc.patchesT for pc in views]
+        return cpass
+
+    def score(self, pl_module, cpass, ctx, owner, n_real, Bn):
+        """split_forward (:900-931): candidates carry their owner's image pair and label; per-row CE from rmcl_nlvr2_ce."""
+        eng = pl_module.engine
+        cls2 = cpass.forward(L.MODE_INFER, wgrad=False)
+        own = torch.tensor(owner[:n_real], device=eng.device)
+        rows = torch.empty(Bn + n_real, dtype=torch.float32, device=eng.device)
+        rows[:Bn].copy_(ctx)
+        nlvr2_candidate_rows(eng, cls2[:n_real].contiguous(), self._nb.labels.index_select(0, own), out=rows[Bn:])
+        host = rows.cpu().tolist()
+        return self.select(host[:Bn], host[Bn:], owner, n_real, Bn)

@@ -502,4 +502,11 @@ int rmcl_attention_bwd(const void* qkv, const int32_t* mask, const void* probs, 
   return rmcl_attention_bwd_impl(qkv, mask, probs, dout, out, dqkv, scores, dscores, B, N, H, dtype, exact, (hipStream_t)stream);
 }
 
+int rmcl_word_saliency(const float* g, const int32_t* spans, float* out, int B, int W, int L, int D, int row0, int row_step, void* stream) {
+  RMCL_REQUIRE(g && spans && out, "word_saliency: NULL argument");
+  RMCL_REQUIRE(B >= 1 && B <= 65536 && W >= 1 && W <= 4096 && L >= 1 && L <= 4096 && D >= 4 && D <= 8192 && D % 4 == 0 && row0 >= 0 && row_step >= 1,
+               "word_saliency: bad shape (1 <= B <= 65536, 1 <= W, L <= 4096, 4 <= D <= 8192, D % 4 == 0, row0 >= 0, row_step >= 1)");
+  return rmcl_word_saliency_launch(g, spans, out, B, W, L, D, row0, row_step, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -145,3 +145,5 @@ int rmcl_itm_head_bwd(const float* dl, const float* cls, const float* W, float* 
 int rmcl_visual_assemble(const float* pe, const float* cls, const float* pos, int pos_per_sample, float* out, int B, int P, int D, hipStream_t s);
 int rmcl_rank_assemble(const float* embeds, const int* masks, const int* img_of, int n_img, int ld_tok, const long* text_mask,
                        const float* vtype1, float* x, int* co, int B, int P, int L, int N, int D, hipStream_t s);
+// txtatk.hip: word saliency of the text attack on the fine-tuning tasks (one wave per (sentence, word))
+int rmcl_word_saliency_launch(const float* g, const int* spans, float* out, int B, int W, int L, int D, int row0, int row_step, hipStream_t s);

@@ -1016,6 +1016,22 @@ class Engine:
                                          P(nb.dcls), stream_ptr()), "nlvr2_head_backward")
         return nb.dcls
 
+    # ---- text attack on the fine-tuning tasks (include/rmcl.h rmcl_word_saliency) -------------------------------------------
+    def word_saliency(self, g: torch.Tensor, spans: torch.Tensor, L_: int, row0: int = 0, row_step: int = 1, out: torch.Tensor = None):
+        """out [B, W] = L1 norm of the mean saliency gradient over each word's sub-word tokens.  g: the fp32 `dtext` buffer of
+        encoder_backward, [R * L_, D] (or [R, L_, D]); spans [B, W, 2] int32 on the device (first token position counting [CLS] as 0,
+        token count; count 0 = padding entry -> 0); sentence b reads sequence row0 + b * row_step of g."""
+        B, W = int(spans.shape[0]), int(spans.shape[1])
+        D = int(g.shape[-1])
+        R = g.numel() // (L_ * D)
+        if g.dtype != torch.float32 or spans.dtype != torch.int32 or not g.is_contiguous() or not spans.is_contiguous() or spans.shape[2] != 2:
+            raise L.RmclError("word_saliency: g must be contiguous fp32 and spans contiguous int32 [B, W, 2]")
+        if row0 < 0 or row_step < 1 or row0 + (B - 1) * row_step >= R:
+            raise L.RmclError(f"word_saliency: sequence {row0} + {B - 1} * {row_step} is outside the {R} sequences of the gradient buffer")
+        out = torch.empty(B, W, dtype=torch.float32, device=self.device) if out is None else out
+        check(lib.rmcl_word_saliency(P(g), P(spans), P(out), B, W, L_, D, row0, row_step, stream_ptr()), "word_saliency")
+        return out
+
     # ---- MLM head (include/rmcl.h rmcl_mlm_*) ------------------------------------------------------------------------
     def mlm_bufs(self, B: int, tag: str) -> MlmBuffers:
         return self._head_buffers(MlmBuffers, B, tag)

@@ -78,7 +78,8 @@ def task_finetune_vqa_randaug(**over):
 
 def task_finetune_vqa_randaug_attacked(**over):
     """reference config.py:319-348: adversarial VQAv2 fine-tuning.  Both views default to False as in the reference, which then fails
-    in compute_vqa_attack; here the module refuses that at construction (ValueError): pass image_view=True (PGD on the image)."""
+    in compute_vqa_attack; here the module refuses that at construction (ValueError): pass image_view=True (PGD on the image) and / or
+    text_view=True (GreedyAttack_vqa, word level: `tokenizer` must then be a local vocabulary path and `embedding_path` a local file)."""
     cfg = default_config(
         exp_name="finetune_vqa_randaug_attacked", datasets=["vqa"], train_transform_keys=["pixelbert_randaug"],
         loss_names=_loss_names({"vqa_attacked": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,
@@ -113,7 +114,8 @@ def task_finetune_nlvr2_randaug(**over):
 def task_finetune_nlvr2_randaug_attacked(**over):
     """reference config.py:258-288: adversarial NLVR2 fine-tuning.  Both views default to False as in the reference, which then fails
     (no nlvr2_attacked_loss); here the module refuses that at construction (ValueError): pass image_view=True (PGD on the images
-    selected by attack_idx)."""
+    selected by attack_idx) and / or text_view=True (GreedyAttack_nlvr2, word level: `tokenizer` must then be a local vocabulary path and
+    `embedding_path` a local file)."""
     cfg = default_config(
         exp_name="finetune_nlvr2_randaug_attacked", datasets=["nlvr2"], train_transform_keys=["pixelbert_randaug"],
         loss_names=_loss_names({"nlvr2_attacked": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,

@@ -577,21 +577,29 @@ def compute_vqa(pl_module, batch):
 
 
 def compute_vqa_attack(pl_module, batch):
-    """objectives.py:813-859 (image view): PGD on the VQA loss (PGDAttack_vqa, through compute_pgd's img + delta_{K-1} + delta_K),
-    then the head and the loss on the attacked view.  The batch itself is not modified (the reference attacks a deepcopy)."""
+    """objectives.py:813-859.  Image view: PGD on the VQA loss (PGDAttack_vqa, through compute_pgd's img + delta_{K-1} + delta_K).
+    Text view: GreedyAttack_vqa on the CLEAN image (compute_geometric on a deepcopy of the batch, :820).  The head and the loss then run
+    on (attacked or clean image, attacked or clean text); with both views the attacked sentence is paired with the attacked image
+    (:821-823).  The batch itself is not modified (the reference attacks deep copies)."""
     eng = pl_module.engine
-    if pl_module.text_view:
-        raise NotImplementedError("vqa_attacked with text_view (GreedyAttack_vqa) is outside the RMCL hot path")
     phase = "train" if pl_module.training else "val"
     pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], batch["image"][0], tag="vqa_att")
-    op = eng.make_operand(pb)                                                 # img + delta_0, delta_0 = 0
     vp = eng.vqa_targets(eng.vqa_bufs(pb.B, "pgd"), batch["vqa_labels"], batch["vqa_scores"])
-    pl_module.pgd_attacker.attack_patches(pl_module, pb, vp, clean_op=op)    # compute_pgd (:816)
-    check(lib.rmcl_delta_channel_norm(P(pb.delta), P(eng.zero_scalar(pb)), I64(pb.delta.shape[0]), 3, pb.d.patch_k // 3,
-                                      stream_ptr()), "delta_norm")
-    n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
-    pl_module.log(f"vqa_attacked_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
-    return _vqa_head_loss(pl_module, pb, pb.patchesT_full, batch, "vqa_attacked", "vqa_att", tables=vp)
+    if pl_module.image_view:
+        op = eng.make_operand(pb)                                             # img + delta_0, delta_0 = 0
+        pl_module.pgd_attacker.attack_patches(pl_module, pb, vp, clean_op=op)    # compute_pgd (:816)
+        check(lib.rmcl_delta_channel_norm(P(pb.delta), P(eng.zero_scalar(pb)), I64(pb.delta.shape[0]), 3, pb.d.patch_k // 3,
+                                          stream_ptr()), "delta_norm")
+        n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
+        pl_module.log(f"vqa_attacked_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
+        op = pb.patchesT_full
+    else:
+        op = eng.make_operand(pb, out=pb.patchesT_full)                       # the clean image, built once
+    if pl_module.text_view:
+        aug = compute_geometric(pl_module, copy(batch), "vqa_attacked")       # (:820) on the clean image
+        pb.text_ids = aug["text_ids"].to(eng.device, torch.int64).contiguous()
+        pb.text_mask = aug["text_masks"].to(eng.device, torch.int64).contiguous()
+    return _vqa_head_loss(pl_module, pb, op, batch, "vqa_attacked", "vqa_att", tables=vp)
 
 
 # ---- NLVR2 (objectives.py:898-1060) ------------------------------------------------------------------------------------------------
@@ -712,13 +720,14 @@ def compute_nlvr2(pl_module, batch):
 
 
 def compute_nlvr2_attack(pl_module, batch):
-    """objectives.py:898-1000 (image view): the clean pair (nlvr2_original_*), PGDAttack_nlvr2 on the CE (compute_pgd's
-    img + delta_{K-1} + delta_K per image), the attacked pair (nlvr2_attacked_*).  Both losses carry a backward (training_step sums every
-    key with "loss").  The reference's train branch reads the never-set ret["nlvr2_attacked_labels"] (defect (a)): the
-    labels are ret["nlvr2_labels"] here.  The batch itself is not modified (the reference attacks a deepcopy)."""
+    """objectives.py:898-1000: the clean pair (nlvr2_original_*); image view: PGDAttack_nlvr2 on the CE (compute_pgd's
+    img + delta_{K-1} + delta_K per image); text view: GreedyAttack_nlvr2 on the CLEAN pair (:927); the attacked pass
+    (nlvr2_attacked_*) runs on (attacked or clean images, attacked or clean text) - with both views the attacked sentence with the
+    attacked images (:928-930; the image-only pass of :915-923 is overwritten there and carries no gradient, it is not run).  Both
+    losses carry a backward (training_step sums every key with "loss").  The reference's train branch reads the never-set
+    ret["nlvr2_attacked_labels"] (defect (a)): the labels are ret["nlvr2_labels"] here.  The batch itself is not
+    modified (the reference attacks deep copies)."""
     eng = pl_module.engine
-    if pl_module.text_view:
-        raise NotImplementedError("nlvr2_attacked with text_view (GreedyAttack_nlvr2) is outside the RMCL hot path")
     phase = "train" if pl_module.training else "val"
     npass = Nlvr2Pass.bind(pl_module, batch, "nlvr2_clean")
     npass.clean_operands()
@@ -727,9 +736,19 @@ def compute_nlvr2_attack(pl_module, batch):
     apass = npass.twin("nlvr2_att")
     npg = eng.nlvr2_bufs(npass.B, "pgd")
     npg.labels.copy_(nb_c.labels)
-    pl_module.pgd_attacker.attack_pairs(pl_module, apass, npg)                # compute_pgd (:914)
-    pl_module.log(f"nlvr2_attacked_attack/{phase}/delta", pl_module.pgd_attacker.delta_log(pl_module, apass, batch))
-    apass.ops = [pv.patchesT_full for pv in apass.views]                      # img + delta_{K-1} + delta_K, left by the last step
+    if pl_module.image_view:
+        pl_module.pgd_attacker.attack_pairs(pl_module, apass, npg)            # compute_pgd (:914)
+        pl_module.log(f"nlvr2_attacked_attack/{phase}/delta", pl_module.pgd_attacker.delta_log(pl_module, apass, batch))
+        apass.ops = [pv.patchesT_full for pv in apass.views]                  # img + delta_{K-1} + delta_K, left by the last step
+    else:
+        apass.clean_operands()
+    if pl_module.text_view:
+        aug = compute_geometric(pl_module, copy(batch), "nlvr2_attacked")     # (:927) on the clean pair
+        ids = aug["text_ids"].to(eng.device, torch.int64)
+        masks = aug["text_masks"].to(eng.device, torch.int64)
+        for pv in apass.views:
+            pv.text_ids = (ids.repeat_interleave(2, dim=0) if apass.pair else ids).contiguous()
+            pv.text_mask = (masks.repeat_interleave(2, dim=0) if apass.pair else masks).contiguous()
     v_att, lg_att, nb_a, st_a = _nlvr2_loss(pl_module, apass, batch, "att", labels_from=nb_c, ref=nb_c)
     ret["nlvr2_attacked_logits"] = lg_att
     ret["nlvr2_attacked_loss"] = v_att

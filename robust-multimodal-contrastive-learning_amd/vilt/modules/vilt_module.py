@@ -17,7 +17,7 @@ from ... import _lib as L
 from ..._lib import lib, check
 from ...runtime import Engine, EMA_GROUPS
 from ...attack.pgd_attack_vilt import PGDAttack_moco, PGDAttack_bartlowtwins, PGDAttack_vqa, PGDAttack_nlvr2
-from ...attack.greedy_attack_vilt import GreedyAttack_moco, GreedyAttack_barlowtwins
+from ...attack.greedy_attack_vilt import GreedyAttack_moco, GreedyAttack_barlowtwins, GreedyAttack_vqa, GreedyAttack_nlvr2
 from . import objectives, vilt_utils, dist_utils
 
 
@@ -167,23 +167,27 @@ class ViLTransformerSS(nn.Module):
             if not (self.image_view or self.text_view):
                 # the reference reaches compute_vqa_attack with `infer` unbound (NameError, objectives.py:825) - this default of
                 # task_finetune_vqa_randaug_attacked is refused here, at construction
-                raise ValueError("loss_names['vqa_attacked'] > 0 needs image_view=True (text_view / GreedyAttack_vqa is not built)")
+                raise ValueError("loss_names['vqa_attacked'] > 0 needs image_view=True and / or text_view=True")
             if self.text_view:
-                raise NotImplementedError("vqa_attacked with text_view=True (GreedyAttack_vqa) is outside the RMCL hot path")
-            self.pgd_attacker = PGDAttack_vqa(config)
+                # word level only: NotImplementedError unless config["tokenizer"] is a tokenizer object / a local vocabulary
+                self.greedy_attacker = GreedyAttack_vqa(config)
+            if self.image_view:
+                self.pgd_attacker = PGDAttack_vqa(config)
         if ln.get("nlvr2_attacked", 0) > 0:                                # vilt_module.py:211-231
             self.image_view = config.get("image_view", False)
             self.text_view = config.get("text_view", False)
             if not (self.image_view or self.text_view):
                 # the reference returns no nlvr2_attacked_loss then and its logging raises a KeyError (defect (b))
-                raise ValueError("loss_names['nlvr2_attacked'] > 0 needs image_view=True (text_view / GreedyAttack_nlvr2 is not built)")
+                raise ValueError("loss_names['nlvr2_attacked'] > 0 needs image_view=True and / or text_view=True")
             if self.text_view:
-                raise NotImplementedError("nlvr2_attacked with text_view=True (GreedyAttack_nlvr2) is outside the RMCL hot path")
+                # word level only: NotImplementedError unless config["tokenizer"] is a tokenizer object / a local vocabulary
+                self.greedy_attacker = GreedyAttack_nlvr2(config)
             self.attack_idx = [bool(a) for a in config.get("attack_idx", [False, False])]   # (reference default: config.py:92)
-            if len(self.attack_idx) != 2 or not any(self.attack_idx):
-                # compute_pgd divides the delta log by sum(attack_idx) (objectives.py:183): [False, False] is a division by zero (defect (c))
-                raise ValueError(f"nlvr2_attacked with image_view needs attack_idx with at least one True of two (got {config.get('attack_idx')})")
-            self.pgd_attacker = PGDAttack_nlvr2(config)
+            if self.image_view:
+                if len(self.attack_idx) != 2 or not any(self.attack_idx):
+                    # compute_pgd divides the delta log by sum(attack_idx) (objectives.py:183): [False, False] is a division by zero (defect (c))
+                    raise ValueError(f"nlvr2_attacked with image_view needs attack_idx with at least one True of two (got {config.get('attack_idx')})")
+                self.pgd_attacker = PGDAttack_nlvr2(config)
         self.id2answer = None                      # answer strings of the label ids (test_step); the reference reads them from its datamodule
         self.grad_anchor = torch.zeros((), device=eng.device, requires_grad=True)
         self.sync_grads = True                     # False on the early micro-steps of gradient accumulation (DDP no_sync)
