@@ -11,6 +11,7 @@
 #include <algorithm>
 #include "rmcl_common.h"
 #include "kernels.h"
+#include "head_rows.h"
 #include "../../include/rmcl.h"
 
 namespace {
@@ -185,27 +186,19 @@ __global__ __launch_bounds__(256) void pair_metrics_kernel(const float* __restri
   }
 }
 
-GemmArgs mk(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = 1.f; g.splitk = 1; g.nb1 = 1; g.nb2 = 1;
-  return g;
-}
-
 struct BtStash {                     // per pass, all fp32 (rmcl_bt_stash_floats)
   float *x0, *h1, *a1, *h2, *a2, *h3, *stat, *t0, *t1;     // stat: mean1 rstd1 mean2 rstd2 mean3 rstd3
 };
 long carve(const rmcl_bt_head& h, int B, float* base, BtStash* s) {
-  long o = 0;
-  auto take = [&](long n) { float* p = base ? base + o : nullptr; o += (n + 63) / 64 * 64; return p; };
+  StashCarver c{base};
   const int Hm = std::max(std::max(h.H1, h.H2), std::max(h.H3, h.D));
-  s->x0 = take((long)B * h.D);
-  s->h1 = take((long)B * h.H1); s->a1 = take((long)B * h.H1);
-  s->h2 = take((long)B * h.H2); s->a2 = take((long)B * h.H2);
-  s->h3 = take((long)B * h.H3);
-  s->stat = take(2L * (h.H1 + h.H2 + h.H3));
-  s->t0 = take((long)B * Hm); s->t1 = take((long)B * Hm);
-  return o;
+  s->x0 = c.take((long)B * h.D);
+  s->h1 = c.take((long)B * h.H1); s->a1 = c.take((long)B * h.H1);
+  s->h2 = c.take((long)B * h.H2); s->a2 = c.take((long)B * h.H2);
+  s->h3 = c.take((long)B * h.H3);
+  s->stat = c.take(2L * (h.H1 + h.H2 + h.H3));
+  s->t0 = c.take((long)B * Hm); s->t1 = c.take((long)B * Hm);
+  return c.used;
 }
 int bn_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, float* rm, float* rv, float mom, int B, int N,
            int relu, int training, hipStream_t s) {
@@ -246,11 +239,11 @@ int rmcl_bt_head_forward(const rmcl_bt_head* h, const float* params, const float
   float* mean1 = st.stat, *rstd1 = mean1 + h->H1, *mean2 = rstd1 + h->H1, *rstd2 = mean2 + h->H2, *mean3 = rstd2 + h->H2, *rstd3 = mean3 + h->H3;
   hipError_t e = hipMemcpyAsync(st.x0, cls_feats, (size_t)B * h->D * 4, hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
-  RMCL_TRY(rmcl_launch_gemm_exact(mk(st.x0, params + h->w1, st.h1, B, h->H1, h->D, h->D, h->D, h->H1), RMCL_F32, RMCL_F32, 1, 1, s));
+  RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.x0, params + h->w1, st.h1, B, h->H1, h->D, h->D, h->D, h->H1, 0), RMCL_F32, RMCL_F32, 1, 1, s));
   RMCL_TRY(bn_fwd(st.h1, params + h->g1, params + h->b1, st.a1, mean1, rstd1, rm[0], rv[0], momentum, B, h->H1, 1, training, s));
-  RMCL_TRY(rmcl_launch_gemm_exact(mk(st.a1, params + h->w2, st.h2, B, h->H2, h->H1, h->H1, h->H1, h->H2), RMCL_F32, RMCL_F32, 1, 1, s));
+  RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.a1, params + h->w2, st.h2, B, h->H2, h->H1, h->H1, h->H1, h->H2, 0), RMCL_F32, RMCL_F32, 1, 1, s));
   RMCL_TRY(bn_fwd(st.h2, params + h->g2, params + h->b2, st.a2, mean2, rstd2, rm[1], rv[1], momentum, B, h->H2, 1, training, s));
-  RMCL_TRY(rmcl_launch_gemm_exact(mk(st.a2, params + h->w3, st.h3, B, h->H3, h->H2, h->H2, h->H2, h->H3), RMCL_F32, RMCL_F32, 1, 1, s));
+  RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.a2, params + h->w3, st.h3, B, h->H3, h->H2, h->H2, h->H2, h->H3, 0), RMCL_F32, RMCL_F32, 1, 1, s));
   RMCL_TRY(bn_fwd(st.h3, nullptr, nullptr, z, mean3, rstd3, rm[2], rv[2], momentum, B, h->H3, 0, training, s));
   return 0;
 }
@@ -265,31 +258,31 @@ int rmcl_bt_head_backward(const rmcl_bt_head* h, const float* params, float* sta
   // norm (affine=False): dh3
   RMCL_TRY(bn_bwd(dz, st.h3, nullptr, mean3, rstd3, nullptr, st.t0, nullptr, nullptr, B, h->H3, training, s));
   if (G) {                                                                   // dW3 += dh3^T a2
-    GemmArgs g = mk(st.t0, st.a2, G + h->w3, h->H3, h->H2, B, h->H3, h->H2, h->H2);
+    GemmArgs g = head_gemm(st.t0, st.a2, G + h->w3, h->H3, h->H2, B, h->H3, h->H2, h->H2, 0);
     g.epi = EPI_ACCUM;
     RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
   }
-  RMCL_TRY(rmcl_launch_gemm_exact(mk(st.t0, params + h->w3, st.t1, B, h->H2, h->H3, h->H3, h->H2, h->H2), RMCL_F32, RMCL_F32, 1, 0, s));   // da2
+  RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.t0, params + h->w3, st.t1, B, h->H2, h->H3, h->H3, h->H2, h->H2, 0), RMCL_F32, RMCL_F32, 1, 0, s));   // da2
   RMCL_TRY(bn_bwd(st.t1, st.h2, st.a2, mean2, rstd2, params + h->g2, st.t0, G ? G + h->g2 : nullptr, G ? G + h->b2 : nullptr, B, h->H2, training, s));
   if (G) {
-    GemmArgs g = mk(st.t0, st.a1, G + h->w2, h->H2, h->H1, B, h->H2, h->H1, h->H1);
+    GemmArgs g = head_gemm(st.t0, st.a1, G + h->w2, h->H2, h->H1, B, h->H2, h->H1, h->H1, 0);
     g.epi = EPI_ACCUM;
     RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
   }
-  RMCL_TRY(rmcl_launch_gemm_exact(mk(st.t0, params + h->w2, st.t1, B, h->H1, h->H2, h->H2, h->H1, h->H1), RMCL_F32, RMCL_F32, 1, 0, s));   // da1
+  RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.t0, params + h->w2, st.t1, B, h->H1, h->H2, h->H2, h->H1, h->H1, 0), RMCL_F32, RMCL_F32, 1, 0, s));   // da1
   RMCL_TRY(bn_bwd(st.t1, st.h1, st.a1, mean1, rstd1, params + h->g1, st.t0, G ? G + h->g1 : nullptr, G ? G + h->b1 : nullptr, B, h->H1, training, s));
   if (G) {
-    GemmArgs g = mk(st.t0, st.x0, G + h->w1, h->H1, h->D, B, h->H1, h->D, h->D);
+    GemmArgs g = head_gemm(st.t0, st.x0, G + h->w1, h->H1, h->D, B, h->H1, h->D, h->D, 0);
     g.epi = EPI_ACCUM;
     RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
   }
-  RMCL_TRY(rmcl_launch_gemm_exact(mk(st.t0, params + h->w1, dcls, B, h->D, h->H1, h->H1, h->D, h->D), RMCL_F32, RMCL_F32, 1, 0, s));       // dcls
+  RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.t0, params + h->w1, dcls, B, h->D, h->H1, h->H1, h->D, h->D, 0), RMCL_F32, RMCL_F32, 1, 0, s));   // dcls
   return 0;
 }
 
 int rmcl_bt_corr(const float* zq, const float* zk, int B, int N, float inv_bs, float* c, void* stream) {
   RMCL_REQUIRE(zq && zk && c && N % 4 == 0, "bt_corr: NULL argument / N % 4");
-  GemmArgs g = mk(zq, zk, c, N, N, B, N, N, N);                               // c = zq^T zk (objectives.py:478)
+  GemmArgs g = head_gemm(zq, zk, c, N, N, B, N, N, N, 0);                               // c = zq^T zk (objectives.py:478)
   g.alpha = inv_bs;
   return rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, (hipStream_t)stream);
 }
@@ -309,7 +302,7 @@ int rmcl_bt_loss(float* c, int N, float lambda, float grad_scale, float* ws, flo
 
 int rmcl_bt_dz(const float* zk, const float* G, int B, int N, float inv_bs, float* dzq, void* stream) {
   RMCL_REQUIRE(zk && G && dzq, "bt_dz: NULL argument");
-  GemmArgs g = mk(zk, G, dzq, B, N, N, N, N, N);                              // dzq[b,i] = sum_j G[i,j] zk[b,j] / bs
+  GemmArgs g = head_gemm(zk, G, dzq, B, N, N, N, N, N, 0);                              // dzq[b,i] = sum_j G[i,j] zk[b,j] / bs
   g.alpha = inv_bs;
   return rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, (hipStream_t)stream);
 }

@@ -13,28 +13,13 @@
 // Every reduction has a fixed order and nothing uses float atomics: two identical calls give identical bits.
 #include "rmcl_common.h"
 #include "kernels.h"
+#include "head_rows.h"
 #include "../../include/rmcl.h"
 
 namespace {
 
 #define IRTR_WAVES 4
 #define IRTR_MAX_R 64
-
-__device__ __forceinline__ float irtr_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// first maximum of a group held one score per lane (lanes >= R hold -inf / index R): ties go to the smaller index
-__device__ __forceinline__ int irtr_wave_argmax(float v, int i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(v, o, 64);
-    const int i2 = __shfl_xor(i, o, 64);
-    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-  }
-  return i;
-}
 
 __global__ __launch_bounds__(256) void irtr_score_kernel(const float* __restrict__ cls, long ld_cls, const float* __restrict__ w,
                                                          const float* __restrict__ bias, int S, int D, float* __restrict__ scores,
@@ -57,33 +42,9 @@ __global__ __launch_bounds__(256) void irtr_score_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void irtr_ce_kernel(const float* __restrict__ scores, int B, int R, float gscale,
                                                       const float* __restrict__ gscale_dev, float* __restrict__ dscore,
                                                       float* __restrict__ rows, float* __restrict__ stats) {
-  __shared__ float s_loss[IRTR_WAVES];
-  __shared__ int s_hit[IRTR_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float scale = (gscale_dev ? gscale * gscale_dev[0] : gscale) / (float)B;
-  float loss_acc = 0.f;                 // lane 0's running sum over this wave's groups, in group order
-  int hit = 0;
-  for (int b = wave; b < B; b += IRTR_WAVES) {
-    const float z = lane < R ? scores[(long)b * R + lane] : -INFINITY;
-    const float m = irtr_wave_max(z);
-    const float e = lane < R ? expf(z - m) : 0.f;
-    const float s = wave_sum(e);
-    const float z0 = __shfl(z, 0, 64);
-    const int am = irtr_wave_argmax(z, lane < R ? lane : R);
-    const float row = (logf(s) + m) - z0;
-    if (dscore && lane < R) dscore[(long)b * R + lane] = scale * (e / s - (lane == 0 ? 1.f : 0.f));
-    if (lane == 0) {
-      if (rows) rows[b] = row;
-      loss_acc += row;
-      hit += am == 0;
-    }
-  }
-  if (lane == 0) { s_loss[wave] = loss_acc; s_hit[wave] = hit; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    stats[0] = ((s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3])) / (float)B;
-    stats[1] = (float)(s_hit[0] + s_hit[1] + s_hit[2] + s_hit[3]);
-  }
+  __builtin_assume(R >= 1 && R <= IRTR_MAX_R);             // (the launcher requires it: the dscore loop runs at most once per lane)
+  // answer 0 in every group, pitch R, two stats (runtime.py allocates two floats)
+  softmax_ce_rows(scores, R, nullptr, B, R, gscale, gscale_dev, dscore, R, rows, nullptr, nullptr, 0, stats, 2);
 }
 
 // blocks [0, nbw): one thread per column c of w (dw, and db in block 0's first wave); blocks [nbw, ...): dcls, one float4 per thread

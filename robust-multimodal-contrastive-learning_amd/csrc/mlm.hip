@@ -22,6 +22,7 @@
 #include <algorithm>
 #include "rmcl_common.h"
 #include "kernels.h"
+#include "head_rows.h"
 #include "../../include/rmcl.h"
 
 namespace {
@@ -46,20 +47,6 @@ template <> struct Mma<float> {
   static __device__ __forceinline__ Frag load(const float* p, int lane) { return p[lane >> 5]; }
   static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 };
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float mq_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float mq_wave_sum(float v) {       // (vqa.hip vq_wave_sum)
-  v += mq_dpp<0xB1, 0xf>(v);
-  v += mq_dpp<0x4E, 0xf>(v);
-  v += mq_dpp<0x141, 0xf>(v);
-  v += mq_dpp<0x140, 0xf>(v);
-  v += mq_dpp<0x142, 0xa>(v);
-  v += mq_dpp<0x143, 0xc>(v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 // z tile [32 x 32] = A rows x B rows over K = D (both K-contiguous); arow / brow: this lane's row (lane & 31) of either operand
 template <typename T>
@@ -151,21 +138,14 @@ __global__ __launch_bounds__(256) void mlm_gelu_ln_fwd_kernel(const float* __res
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   float4 v[NV];
-  float s = 0.f;
+  float s = 0.f, mu, rs;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const float4 x = *reinterpret_cast<const float4*>(a + (long)row * D + (lane + 64 * i) * 4);
     v[i] = make_float4(gelu_erf(x.x), gelu_erf(x.y), gelu_erf(x.z), gelu_erf(x.w));
-    s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    s += sum4_pairwise(v[i]);
   }
-  const float mu = mq_wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float e = v[i].x - mu, f = v[i].y - mu, g = v[i].z - mu, k = v[i].w - mu;
-    q += (e * e + f * f) + (g * g + k * k);
-  }
-  const float rs = 1.0f / sqrtf(mq_wave_sum(q) / (float)D + 1e-12f);
+  ln_row_stats<NV>(v, s, 1e-12f, mu, rs);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (lane + 64 * i) * 4;
@@ -212,26 +192,23 @@ __global__ __launch_bounds__(256) void mlm_gelu_ln_bwd_kernel(const float* __res
       const float4 dy = *reinterpret_cast<const float4*>(dh + (long)r * D + c);
       xh[i] = make_float4((gelu_erf(av[i].x) - mu) * rs, (gelu_erf(av[i].y) - mu) * rs, (gelu_erf(av[i].z) - mu) * rs,
                           (gelu_erf(av[i].w) - mu) * rs);
-      pg[i].x = fmaf(dy.x, xh[i].x, pg[i].x); pg[i].y = fmaf(dy.y, xh[i].y, pg[i].y);
-      pg[i].z = fmaf(dy.z, xh[i].z, pg[i].z); pg[i].w = fmaf(dy.w, xh[i].w, pg[i].w);
-      pb[i].x += dy.x; pb[i].y += dy.y; pb[i].z += dy.z; pb[i].w += dy.w;
-      dx[i] = make_float4(dy.x * w[i].x, dy.y * w[i].y, dy.z * w[i].z, dy.w * w[i].w);
-      s1 += (dx[i].x + dx[i].y) + (dx[i].z + dx[i].w);
-      s2 += (dx[i].x * xh[i].x + dx[i].y * xh[i].y) + (dx[i].z * xh[i].z + dx[i].w * xh[i].w);
+      ln_bwd_acc(dy, xh[i], w[i], pg[i], pb[i], dx[i], s1, s2);
     }
-    const float m1 = mq_wave_sum(s1) / (float)D, m2 = mq_wave_sum(s2) / (float)D;
+    float m1, m2;
+    ln_bwd_means(s1, s2, D, m1, m2);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (lane + 64 * i) * 4;
       float4 o;
-      o.x = rs * (dx[i].x - m1 - xh[i].x * m2) * gelu_erf_grad(av[i].x);
-      o.y = rs * (dx[i].y - m1 - xh[i].y * m2) * gelu_erf_grad(av[i].y);
-      o.z = rs * (dx[i].z - m1 - xh[i].z * m2) * gelu_erf_grad(av[i].z);
-      o.w = rs * (dx[i].w - m1 - xh[i].w * m2) * gelu_erf_grad(av[i].w);
+      o.x = ln_bwd_dx(dx[i].x, xh[i].x, m1, m2, rs) * gelu_erf_grad(av[i].x);
+      o.y = ln_bwd_dx(dx[i].y, xh[i].y, m1, m2, rs) * gelu_erf_grad(av[i].y);
+      o.z = ln_bwd_dx(dx[i].z, xh[i].z, m1, m2, rs) * gelu_erf_grad(av[i].z);
+      o.w = ln_bwd_dx(dx[i].w, xh[i].w, m1, m2, rs) * gelu_erf_grad(av[i].w);
       pa[i].x += o.x; pa[i].y += o.y; pa[i].z += o.z; pa[i].w += o.w;
       *reinterpret_cast<float4*>(da + (long)r * D + c) = o;
     }
   }
+  // (this merge stays literal in the kernel - behind a shared helper the row loop above compiles to other bits: DESIGN "Head row primitives")
   for (int ph = 0; ph < 4; ++ph) {
     if (wave == ph) {
 #pragma unroll
@@ -381,13 +358,7 @@ __global__ __launch_bounds__(256) void mlm_stats_kernel(const float* __restrict_
   const int n = min(count[0], rows);
   float l = 0.f, c = 0.f;
   for (int r = threadIdx.x; r < n; r += 256) { l += rowloss[r]; c += argmax[r] == lab[r] ? 1.f : 0.f; }
-  red[0][threadIdx.x] = l;
-  red[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-    __syncthreads();
-  }
+  block_tree_sum2(red, l, c);
   if (threadIdx.x == 0) { stats[0] = red[0][0] / (float)n; stats[1] = red[1][0]; stats[2] = (float)n; }
 }
 
@@ -580,42 +551,33 @@ int fwd_chunks(int rows) {                                // vocabulary chunks o
   return std::max(1, std::min(64, 512 / std::max(rt, 1)));
 }
 long carve(const rmcl_mlm_head& hd, int rows, float* base, MlmWs* w) {
-  long o = 0;
-  auto take = [&](long n) { float* p = base ? base + o : nullptr; o += (n + 63) / 64 * 64; return p; };
+  StashCarver c{base};
   const long RD = (long)rows * hd.D;
   w->nchunk = 64;                                         // (capacity of the partial table; the launch uses fwd_chunks(rows) <= 64)
-  w->x = take(RD);
-  w->a = take(RD);
-  w->stat = take(2L * rows);
-  w->h = take(RD);                                        // (T <= 4 bytes)
-  w->hT = take(RD);
-  w->part = reinterpret_cast<float4*>(take(4L * 64 * rows));
-  w->parti = reinterpret_cast<int*>(take(64L * rows));
-  w->dh = take(RD);
-  w->da = take(RD);
-  w->dx = take(RD);
-  w->lnpart = take((long)cdiv(rows, MLM_ROWS_PER_BLK) * 3 * hd.D);
+  w->x = c.take(RD);
+  w->a = c.take(RD);
+  w->stat = c.take(2L * rows);
+  w->h = c.take(RD);                                        // (T <= 4 bytes)
+  w->hT = c.take(RD);
+  w->part = reinterpret_cast<float4*>(c.take(4L * 64 * rows));
+  w->parti = reinterpret_cast<int*>(c.take(64L * rows));
+  w->dh = c.take(RD);
+  w->da = c.take(RD);
+  w->dx = c.take(RD);
+  w->lnpart = c.take((long)cdiv(rows, MLM_ROWS_PER_BLK) * 3 * hd.D);
   // (monotone in rows and >= h_chunks(rows) x rows in each of its three regimes: buffers sized for a larger extent fit a smaller one)
-  w->dhp = take(std::max({32L * std::min(rows, 512), 16L * std::min(rows, 1024), 8L * rows}) * hd.D);
-  return o;
+  w->dhp = c.take(std::max({32L * std::min(rows, 512), 16L * std::min(rows, 1024), 8L * rows}) * hd.D);
+  return c.used;
 }
 bool head_ok(const rmcl_mlm_head* h) { return h && (h->D == 256 || h->D == 768) && h->V >= 1; }
 bool rows_ok(int rows) { return rows >= MLM_RG && rows % MLM_RG == 0 && rows <= (1 << 20); }
-
-GemmArgs mk(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = 1.f; g.splitk = 1; g.nb1 = 1; g.nb2 = 1;
-  g.tag = GEMM_TAG_HEAD;
-  return g;
-}
 
 template <typename T>
 int lds_bytes(int D, bool with_dz) { return (32 * (D + Mma<T>::PAD) + (with_dz ? 32 * (MLM_RG + Mma<T>::PAD) : 0)) * (int)sizeof(T); }
 
 template <typename T>
 int transform_fwd(const rmcl_mlm_head* h, const float* params, const MlmWs& w, int rows, hipStream_t s) {
-  GemmArgs g0 = mk(w.x, params + h->tw, w.a, rows, h->D, h->D, h->D, h->D, h->D);                    // a = x Wt^T + bt
+  GemmArgs g0 = head_gemm(w.x, params + h->tw, w.a, rows, h->D, h->D, h->D, h->D, h->D, GEMM_TAG_HEAD);                    // a = x Wt^T + bt
   g0.epi = EPI_BIAS;
   g0.bias = params + h->tb;
   RMCL_TRY(rmcl_launch_gemm(g0, RMCL_F32, RMCL_F32, 1, 1, 1, s));
@@ -672,11 +634,11 @@ int backward_t(const rmcl_mlm_head* h, const float* params, const T* W, const T*
   if (G) {
     RMCL_LAUNCH(mlm_param_grad_kernel, dim3(cdiv(D, 256)), dim3(256), 0, s, w.lnpart, nblk, D, G + h->lg, G + h->lb, G + h->tb);
     RMCL_CHECK_LAUNCH();
-    GemmArgs gw = mk(w.da, w.x, G + h->tw, D, D, rows, D, D, D);                                      // dWt += da^T x
+    GemmArgs gw = head_gemm(w.da, w.x, G + h->tw, D, D, rows, D, D, D, GEMM_TAG_HEAD);                                      // dWt += da^T x
     gw.epi = EPI_ACCUM;
     RMCL_TRY(rmcl_launch_gemm(gw, RMCL_F32, RMCL_F32, 0, 0, 1, s));
   }
-  RMCL_TRY(rmcl_launch_gemm(mk(w.da, params + h->tw, w.dx, rows, D, D, D, D, D), RMCL_F32, RMCL_F32, 1, 0, 1, s));   // dx = da Wt
+  RMCL_TRY(rmcl_launch_gemm(head_gemm(w.da, params + h->tw, w.dx, rows, D, D, D, D, D, GEMM_TAG_HEAD), RMCL_F32, RMCL_F32, 1, 0, 1, s));   // dx = da Wt
   if (dxn) {
     RMCL_LAUNCH(mlm_scatter_kernel, dim3(std::min(1024, cdiv((long)rows * D / 4, 256))), dim3(256), 0, s, w.dx, idx, count, dxn, rows, D);
     RMCL_CHECK_LAUNCH();

@@ -7,6 +7,7 @@
 // atomics: loss, counts and dz are bit-reproducible.
 #include "rmcl_common.h"
 #include "kernels.h"
+#include "head_rows.h"
 #include "../../include/rmcl.h"
 
 namespace {
@@ -14,71 +15,12 @@ namespace {
 #define CE_WAVES 4
 #define CE_MAX_N 64
 
-__device__ __forceinline__ float ce_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float ce_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// first maximum of a row held one column per lane (lanes >= N hold -inf / index N): ties go to the smaller column
-__device__ __forceinline__ int ce_wave_argmax(float v, int i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(v, o, 64);
-    const int i2 = __shfl_xor(i, o, 64);
-    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-  }
-  return i;
-}
-
 __global__ __launch_bounds__(256) void nlvr2_ce_kernel(const float* __restrict__ logits, int ldl, const int* __restrict__ labels, int B,
                                                        int N, float gscale, const float* __restrict__ gscale_dev, float* __restrict__ dz,
                                                        float* __restrict__ rows, int* __restrict__ argmax, const float* __restrict__ ref,
                                                        int ld_ref, float* __restrict__ stats) {
-  __shared__ float s_loss[CE_WAVES];
-  __shared__ int s_hit[CE_WAVES], s_chg[CE_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float scale = (gscale_dev ? gscale * gscale_dev[0] : gscale) / (float)B;
-  float loss_acc = 0.f;                 // lane 0's running sum over this wave's rows, in row order
-  int hit = 0, chg = 0;
-  for (int b = wave; b < B; b += CE_WAVES) {
-    const float z = lane < N ? logits[(long)b * ldl + lane] : -INFINITY;
-    const float m = ce_wave_max(z);
-    const float e = lane < N ? expf(z - m) : 0.f;
-    const float s = ce_wave_sum(e);
-    const int lbl = min(max(labels[b], 0), N - 1);
-    const float zl = __shfl(z, lbl, 64);
-    const int am = min(ce_wave_argmax(z, lane < N ? lane : N), N - 1);
-    const float row = (logf(s) + m) - zl;
-    if (dz) {
-      for (int c = lane; c < ldl; c += 64)
-        dz[(long)b * ldl + c] = c < N ? scale * (e / s - (c == lbl ? 1.f : 0.f)) : 0.f;
-    }
-    int changed = 0;
-    if (ref) {
-      const float zr = lane < N ? ref[(long)b * ld_ref + lane] : -INFINITY;
-      changed = min(ce_wave_argmax(zr, lane < N ? lane : N), N - 1) != am;
-    }
-    if (lane == 0) {
-      rows[b] = row;
-      argmax[b] = am;
-      loss_acc += row;
-      hit += am == lbl;
-      chg += changed;
-    }
-  }
-  if (lane == 0) { s_loss[wave] = loss_acc; s_hit[wave] = hit; s_chg[wave] = chg; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float l = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
-    stats[0] = l / (float)B;
-    stats[1] = (float)(s_hit[0] + s_hit[1] + s_hit[2] + s_hit[3]);
-    stats[2] = (float)(s_chg[0] + s_chg[1] + s_chg[2] + s_chg[3]);
-  }
+  __builtin_assume(labels && rows && argmax);           // (the launcher requires them)
+  softmax_ce_rows(logits, ldl, labels, B, N, gscale, gscale_dev, dz, ldl, rows, argmax, ref, ld_ref, stats, 3);
 }
 
 }  // namespace

@@ -5,21 +5,6 @@
 
 #define LN_MAXV 4  // float4 per lane -> D <= 1024
 
-// wave sum by DPP row operations (all 64 lanes must be active); every lane receives lane 63's total
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float ln_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  v += ln_dpp<0xB1, 0xf>(v);     // quad_perm [1, 0, 3, 2]
-  v += ln_dpp<0x4E, 0xf>(v);     // quad_perm [2, 3, 0, 1]
-  v += ln_dpp<0x141, 0xf>(v);    // row_half_mirror
-  v += ln_dpp<0x140, 0xf>(v);    // row_mirror: every lane of a 16-lane row holds the row's sum
-  v += ln_dpp<0x142, 0xa>(v);    // row_bcast15 into rows 1 and 3
-  v += ln_dpp<0x143, 0xc>(v);    // row_bcast31 into rows 2 and 3: lane 63 holds the wave's sum
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
 // ---------------------------------------------------------------------------------------------
 // LayerNorm forward: y = (x - mean) * rstd * w + b  (optionally ReLU), x f32 [M,D], y TO [M,D]
 // ---------------------------------------------------------------------------------------------

@@ -223,6 +223,31 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// wave sum by DPP row operations (all 64 lanes must be active); every lane receives lane 63's total.  The order of the additions
+// differs from wave_sum's butterfly: a kernel keeps the one it has, or its bits change.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float update_dpp(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
+}
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+  v += update_dpp<0xB1, 0xf>(v);     // quad_perm [1, 0, 3, 2]
+  v += update_dpp<0x4E, 0xf>(v);     // quad_perm [2, 3, 0, 1]
+  v += update_dpp<0x141, 0xf>(v);    // row_half_mirror
+  v += update_dpp<0x140, 0xf>(v);    // row_mirror: every lane of a 16-lane row holds the row's sum
+  v += update_dpp<0x142, 0xa>(v);    // row_bcast15 into rows 1 and 3
+  v += update_dpp<0x143, 0xc>(v);    // row_bcast31 into rows 2 and 3: lane 63 holds the wave's sum
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+// first maximum over a wave of (value, index) pairs: the largest value, ties to the smaller index; v and i are both updated
+// (lanes without an element pass -inf and an index behind the last one)
+__device__ __forceinline__ void wave_argmax_first(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(v, o, 64);
+    const int i2 = __shfl_xor(i, o, 64);
+    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+  }
+}
 
 // ds_read_b64_tr_b16 through inline asm.  The builtin (__builtin_amdgcn_ds_read_tr16_b64_v4i16) carries no alias information, so
 // hipcc (ROCm 7.2) orders it behind EVERY LDS-DMA still in flight with an s_waitcnt vmcnt(0) - in a k-loop that keeps the next

@@ -14,27 +14,13 @@
 #include <algorithm>
 #include "rmcl_common.h"
 #include "kernels.h"
+#include "head_rows.h"
 #include "../../include/rmcl.h"
 
 namespace {
 
 #define VQA_ROWS_PER_BLK 16     // rows of one LayerNorm-backward workgroup (one partial of dgamma / dbeta per workgroup)
 #define VQA_MAX_N 4096          // widest label set the BCE row kernel stages in LDS
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float vq_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
-// wave sum by DPP row operations (norm_softmax.hip wave_sum_dpp): every lane receives lane 63's total
-__device__ __forceinline__ float vq_wave_sum(float v) {
-  v += vq_dpp<0xB1, 0xf>(v);
-  v += vq_dpp<0x4E, 0xf>(v);
-  v += vq_dpp<0x141, 0xf>(v);
-  v += vq_dpp<0x140, 0xf>(v);
-  v += vq_dpp<0x142, 0xa>(v);
-  v += vq_dpp<0x143, 0xc>(v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 
 // g = GELU(LayerNorm(h)) per row, eps 1e-5, exact-erf GELU; stat[2 row] = (mean, rstd).  One wave per row, NV float4 per lane
 // (H = 256 NV: no column guards).
@@ -47,7 +33,6 @@ __global__ __launch_bounds__(256) void vqa_ln_gelu_fwd_kernel(const float* __res
   if (row >= B) return;
   const float* hr = h + (long)row * H;
   float4 v[NV], w[NV], bb[NV];
-  float s = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (lane + 64 * i) * 4;
@@ -55,16 +40,10 @@ __global__ __launch_bounds__(256) void vqa_ln_gelu_fwd_kernel(const float* __res
     w[i] = *reinterpret_cast<const float4*>(gamma + c);
     bb[i] = *reinterpret_cast<const float4*>(beta + c);
   }
+  float s = 0.f, mu, rs;
 #pragma unroll
-  for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  const float mu = vq_wave_sum(s) / (float)H;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float a = v[i].x - mu, b2 = v[i].y - mu, c2 = v[i].z - mu, d = v[i].w - mu;
-    q += (a * a + b2 * b2) + (c2 * c2 + d * d);
-  }
-  const float rs = 1.0f / sqrtf(vq_wave_sum(q) / (float)H + 1e-5f);
+  for (int i = 0; i < NV; ++i) s += sum4_pairwise(v[i]);
+  ln_row_stats<NV>(v, s, 1e-5f, mu, rs);
   float* gr = g + (long)row * H;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -115,26 +94,23 @@ __global__ __launch_bounds__(256) void vqa_ln_gelu_bwd_kernel(const float* __res
       xh[i] = make_float4((hv.x - mu) * rs, (hv.y - mu) * rs, (hv.z - mu) * rs, (hv.w - mu) * rs);
       const float4 dy = make_float4(gv.x * gelu_erf_grad(xh[i].x * w[i].x + bb[i].x), gv.y * gelu_erf_grad(xh[i].y * w[i].y + bb[i].y),
                                     gv.z * gelu_erf_grad(xh[i].z * w[i].z + bb[i].z), gv.w * gelu_erf_grad(xh[i].w * w[i].w + bb[i].w));
-      pg[i].x = fmaf(dy.x, xh[i].x, pg[i].x); pg[i].y = fmaf(dy.y, xh[i].y, pg[i].y);
-      pg[i].z = fmaf(dy.z, xh[i].z, pg[i].z); pg[i].w = fmaf(dy.w, xh[i].w, pg[i].w);
-      pb[i].x += dy.x; pb[i].y += dy.y; pb[i].z += dy.z; pb[i].w += dy.w;
-      dx[i] = make_float4(dy.x * w[i].x, dy.y * w[i].y, dy.z * w[i].z, dy.w * w[i].w);        // d xhat
-      s1 += (dx[i].x + dx[i].y) + (dx[i].z + dx[i].w);
-      s2 += (dx[i].x * xh[i].x + dx[i].y * xh[i].y) + (dx[i].z * xh[i].z + dx[i].w * xh[i].w);
+      ln_bwd_acc(dy, xh[i], w[i], pg[i], pb[i], dx[i], s1, s2);
     }
-    const float m1 = vq_wave_sum(s1) / (float)H, m2 = vq_wave_sum(s2) / (float)H;
+    float m1, m2;
+    ln_bwd_means(s1, s2, H, m1, m2);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (lane + 64 * i) * 4;
       float4 o;
-      o.x = rs * (dx[i].x - m1 - xh[i].x * m2);
-      o.y = rs * (dx[i].y - m1 - xh[i].y * m2);
-      o.z = rs * (dx[i].z - m1 - xh[i].z * m2);
-      o.w = rs * (dx[i].w - m1 - xh[i].w * m2);
+      o.x = ln_bwd_dx(dx[i].x, xh[i].x, m1, m2, rs);
+      o.y = ln_bwd_dx(dx[i].y, xh[i].y, m1, m2, rs);
+      o.z = ln_bwd_dx(dx[i].z, xh[i].z, m1, m2, rs);
+      o.w = ln_bwd_dx(dx[i].w, xh[i].w, m1, m2, rs);
       *reinterpret_cast<float4*>(dh + (long)r * H + c) = o;
     }
   }
   if (!part) return;                                       // (uniform over the workgroup: no barrier is skipped by some threads only)
+  // (this merge stays literal in the kernel - behind a shared helper the row loop above compiles to other bits: DESIGN "Head row primitives")
   for (int ph = 0; ph < 4; ++ph) {
     if (wave == ph) {
 #pragma unroll
@@ -208,13 +184,8 @@ __global__ __launch_bounds__(256) void vqa_bce_row_kernel(const float* __restric
   if (dz)
     for (int c = N + threadIdx.x; c < ldl; c += 256) dz[(long)b * ldl + c] = 0.f;
   // block reductions: the loss in a fixed order; argmax = largest value, ties to the smaller column
-  loss = vq_wave_sum(loss);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(best, o, 64);
-    const int i2 = __shfl_xor(bi, o, 64);
-    if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-  }
+  loss = wave_sum_dpp(loss);
+  wave_argmax_first(best, bi);
   if (lane == 0) { rl[wave] = loss; rv[wave] = best; ri[wave] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -234,13 +205,7 @@ __global__ __launch_bounds__(256) void vqa_bce_finish_kernel(const float* __rest
   __shared__ float red[2][256];
   float l = 0.f, s = 0.f;
   for (int b = threadIdx.x; b < B; b += 256) { l += rows[2 * b]; s += rows[2 * b + 1]; }
-  red[0][threadIdx.x] = l;
-  red[1][threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-    __syncthreads();
-  }
+  block_tree_sum2(red, l, s);
   if (threadIdx.x == 0) { loss2[0] = red[0][0] / (float)B; loss2[1] = red[1][0] / (float)B; }
 }
 
@@ -252,28 +217,19 @@ __global__ __launch_bounds__(256) void vqa_targets_dense_kernel(const int* __res
   for (int c = threadIdx.x; c < N; c += 256) out[(long)b * ldo + c] = T[c];
 }
 
-GemmArgs mk(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = 1.f; g.splitk = 1; g.nb1 = 1; g.nb2 = 1;
-  g.tag = GEMM_TAG_HEAD;
-  return g;
-}
-
 struct VqaStash {                    // per pass, all fp32 (rmcl_vqa_stash_floats)
   float *x0, *h, *g, *stat, *t0, *t1, *part;
 };
 long carve(const rmcl_vqa_head& hd, int B, float* base, VqaStash* s) {
-  long o = 0;
-  auto take = [&](long n) { float* p = base ? base + o : nullptr; o += (n + 63) / 64 * 64; return p; };
-  s->x0 = take((long)B * hd.D);
-  s->h = take((long)B * hd.H);
-  s->g = take((long)B * hd.H);
-  s->stat = take(2L * B);
-  s->t0 = take((long)B * hd.H);
-  s->t1 = take((long)B * hd.H);
-  s->part = take((long)cdiv(B, VQA_ROWS_PER_BLK) * 2 * hd.H);
-  return o;
+  StashCarver c{base};
+  s->x0 = c.take((long)B * hd.D);
+  s->h = c.take((long)B * hd.H);
+  s->g = c.take((long)B * hd.H);
+  s->stat = c.take(2L * B);
+  s->t0 = c.take((long)B * hd.H);
+  s->t1 = c.take((long)B * hd.H);
+  s->part = c.take((long)cdiv(B, VQA_ROWS_PER_BLK) * 2 * hd.H);
+  return c.used;
 }
 bool head_ok(const rmcl_vqa_head* h) {
   return h && h->D >= 64 && h->D % 16 == 0 && (h->H == 512 || h->H == 768 || h->H == 1024 || h->H == 1536 || h->H == 2048) &&
@@ -303,7 +259,7 @@ int rmcl_vqa_head_forward(const rmcl_vqa_head* h, const float* params, const flo
   carve(*h, B, stash, &st);
   hipError_t e = hipMemcpyAsync(st.x0, cls, (size_t)B * h->D * 4, hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
-  GemmArgs g0 = mk(st.x0, params + h->w0, st.h, B, h->H, h->D, h->D, h->D, h->H);              // h = cls W0^T + b0
+  GemmArgs g0 = head_gemm(st.x0, params + h->w0, st.h, B, h->H, h->D, h->D, h->D, h->H, GEMM_TAG_HEAD);              // h = cls W0^T + b0
   g0.epi = EPI_BIAS;
   g0.bias = params + h->b0;
   RMCL_TRY(rmcl_launch_gemm_exact(g0, RMCL_F32, RMCL_F32, 1, 1, s));
@@ -316,7 +272,7 @@ int rmcl_vqa_head_forward(const rmcl_vqa_head* h, const float* params, const flo
     default: RMCL_LAUNCH(vqa_ln_gelu_fwd_kernel<8>, grid, dim3(256), 0, s, st.h, params + h->g1, params + h->b1, st.g, st.stat, B); break;
   }
   RMCL_CHECK_LAUNCH();
-  GemmArgs g3 = mk(st.g, params + h->w3, logits, B, h->N, h->H, h->H, h->H, h->ldl);             // logits = g W3^T + b3
+  GemmArgs g3 = head_gemm(st.g, params + h->w3, logits, B, h->N, h->H, h->H, h->H, h->ldl, GEMM_TAG_HEAD);             // logits = g W3^T + b3
   g3.epi = EPI_BIAS;
   g3.bias = params + h->b3;
   return rmcl_launch_gemm_exact(g3, RMCL_F32, RMCL_F32, 1, 1, s);
@@ -350,8 +306,8 @@ int rmcl_vqa_head_backward(const rmcl_vqa_head* h, const float* params, float* s
   VqaStash st;
   carve(*h, B, stash, &st);
   // dg = dz W3 over the padded K = ldl (dz pad columns are 0, the arena's pad rows of W3 are 0)
-  RMCL_TRY(rmcl_launch_gemm_exact(mk(dz, params + h->w3, st.t0, B, h->H, h->ldl, h->ldl, h->H, h->H), RMCL_F32, RMCL_F32, 1, 0, s));
-  if (G) RMCL_TRY(wgrad(mk(dz, st.g, G + h->w3, h->N, h->H, B, h->ldl, h->H, h->H), G + h->b3, s));     // dW3 += dz^T g, db3 += sum dz
+  RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(dz, params + h->w3, st.t0, B, h->H, h->ldl, h->ldl, h->H, h->H, GEMM_TAG_HEAD), RMCL_F32, RMCL_F32, 1, 0, s));
+  if (G) RMCL_TRY(wgrad(head_gemm(dz, st.g, G + h->w3, h->N, h->H, B, h->ldl, h->H, h->H, GEMM_TAG_HEAD), G + h->b3, s));   // dW3 += dz^T g, db3 += sum dz
   const int nblk = cdiv(B, VQA_ROWS_PER_BLK);
   float* part = G ? st.part : nullptr;
   switch (h->H / 256) {
@@ -365,9 +321,9 @@ int rmcl_vqa_head_backward(const rmcl_vqa_head* h, const float* params, float* s
   if (G) {
     RMCL_LAUNCH(vqa_ln_param_grad_kernel, dim3(cdiv(h->H, 256)), dim3(256), 0, s, st.part, nblk, h->H, G + h->g1, G + h->b1);
     RMCL_CHECK_LAUNCH();
-    RMCL_TRY(wgrad(mk(st.t1, st.x0, G + h->w0, h->H, h->D, B, h->H, h->D, h->D), G + h->b0, s));       // dW0 += dh^T cls, db0 += sum dh
+    RMCL_TRY(wgrad(head_gemm(st.t1, st.x0, G + h->w0, h->H, h->D, B, h->H, h->D, h->D, GEMM_TAG_HEAD), G + h->b0, s));   // dW0 += dh^T cls, db0 += sum dh
   }
-  return rmcl_launch_gemm_exact(mk(st.t1, params + h->w0, dcls, B, h->D, h->H, h->H, h->D, h->D), RMCL_F32, RMCL_F32, 1, 0, s);   // dcls
+  return rmcl_launch_gemm_exact(head_gemm(st.t1, params + h->w0, dcls, B, h->D, h->H, h->H, h->D, h->D, GEMM_TAG_HEAD), RMCL_F32, RMCL_F32, 1, 0, s);   // dcls
 }
 
 }  // extern "C"

@@ -32,7 +32,7 @@ def bf16_round(t):
     return t.to(torch.bfloat16).to(t.dtype)
 
 
-def _kernel_case(n, V, seed, tie=False):
+def _kernel_case(n, V, seed, tie=False, D=D):
     """n labelled positions among B x 40 text positions of an xn with 46 token rows per sample; a head with peaked logits."""
     Lt, N = 40, 46
     B = max(2, -(-n // Lt))
@@ -127,9 +127,14 @@ KTOL = {"f32": dict(z=1e-4, loss=1e-5, grad=2e-4), "bf16": dict(z=5e-3, loss=2e-
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("n,V", [(1, 30522), (37, 30522), (384, 30522), (2560, 30522), (37, 1000), (384, 1000)])
-def test_mlm_kernels_match_torch_fp64(n, V, dtype):
-    h, specs, arena, w, xn, labels, N = _kernel_case(n, V, 1000 + n + V)
+# hidden 256 is the other width the launcher takes: one float4 per lane in the transform's row pass (768 has three), two k-tiles per z tile
+@pytest.mark.parametrize("n,V,Dh", [pytest.param(1, 30522, 768, id="1-30522"), pytest.param(37, 30522, 768, id="37-30522"),
+                                    pytest.param(384, 30522, 768, id="384-30522"), pytest.param(2560, 30522, 768, id="2560-30522"),
+                                    pytest.param(37, 1000, 768, id="37-1000"), pytest.param(384, 1000, 768, id="384-1000"),
+                                    pytest.param(1, 1000, 768, id="1-1000"), pytest.param(1, 1000, 256, id="1-1000-D256"),
+                                    pytest.param(37, 1000, 256, id="37-1000-D256")])
+def test_mlm_kernels_match_torch_fp64(n, V, Dh, dtype):
+    h, specs, arena, w, xn, labels, N = _kernel_case(n, V, 1000 + n + V + (0 if Dh == 768 else Dh), D=Dh)
     r = _run_kernels(h, arena, xn, labels, N, dtype, gscale=0.5)
     ref = _fp64_reference(h, specs, w, xn, labels, N, dtype, 0.5)
     tol = KTOL[dtype]

@@ -29,8 +29,8 @@ HEAD = ("vqa_classifier.0.weight", "vqa_classifier.0.bias", "vqa_classifier.1.we
 
 
 # ---- kernels ------------------------------------------------------------------------------------------------------------
-def _kernel_case(B, seed):
-    cfg = {"hidden_size": 768, "vqav2_label_size": V.N_LABELS}
+def _kernel_case(B, seed, hidden=768):
+    cfg = {"hidden_size": hidden, "vqav2_label_size": V.N_LABELS}
     h, specs, n = vqa_layout(cfg, 0)
     g = torch.Generator().manual_seed(seed)
     arena = torch.zeros(n)
@@ -44,7 +44,7 @@ def _kernel_case(B, seed):
             t = 0.3 * torch.randn(shape, generator=g) - (1.0 if name.endswith("3.bias") else 0.0)
         arena[off:off + t.numel()] = t.flatten()
         w[name] = t.double().requires_grad_(True)
-    cls = torch.randn(B, 768, generator=g)
+    cls = torch.randn(B, hidden, generator=g)
     # label tables: row 0 empty, row 1 a duplicate label, rows with up to 10 answers, -1 pads; the widest row sets A
     labels, scores = [], []
     for b in range(B):
@@ -70,7 +70,7 @@ def _run_kernels(h, arena, cls, lab, sco, A, B, grads, gscale=1.0):
     rows = torch.empty(B, 2, device=DEV)
     am = torch.empty(B, dtype=torch.int32, device=DEV)
     loss2 = torch.empty(2, device=DEV)
-    dcls = torch.empty(B, 768, device=DEV)
+    dcls = torch.empty(B, h.D, device=DEV)
     gs = torch.tensor([gscale], device=DEV)
     check(lib.rmcl_vqa_head_forward(C.byref(h), P(arena), P(cls), B, P(stash), P(logits), stream_ptr()))
     check(lib.rmcl_vqa_bce(P(logits), h.ldl, P(lab), P(sco), A, B, h.N, F(1.0), P(gs), P(dz), P(rows), P(am), P(loss2), stream_ptr()))
@@ -79,9 +79,11 @@ def _run_kernels(h, arena, cls, lab, sco, A, B, grads, gscale=1.0):
     return logits, dz, rows, am, loss2, dcls
 
 
-@pytest.mark.parametrize("B", [1, 7, 64, 256])
-def test_vqa_head_and_bce_match_torch_fp64(B):
-    h, specs, arena, w, cls, labels, scores, lab, sco, A = _kernel_case(B, 100 + B)
+# hidden 256 is H = 512: the narrowest LayerNorm row pass the launcher takes (two float4 per lane; hidden 768 has six)
+@pytest.mark.parametrize("B,hidden", [pytest.param(1, 768, id="1"), pytest.param(7, 768, id="7"), pytest.param(64, 768, id="64"),
+                                      pytest.param(256, 768, id="256"), pytest.param(1, 256, id="1-h256"), pytest.param(7, 256, id="7-h256")])
+def test_vqa_head_and_bce_match_torch_fp64(B, hidden):
+    h, specs, arena, w, cls, labels, scores, lab, sco, A = _kernel_case(B, 100 + B + (0 if hidden == 768 else hidden), hidden)
     grads = torch.zeros_like(arena)
     logits, dz, rows, am, loss2, dcls = _run_kernels(h, arena, cls.to(DEV), lab, sco, A, B, grads, gscale=0.5)
     N = h.N
