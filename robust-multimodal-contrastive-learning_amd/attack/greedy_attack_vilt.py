@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..task_loss import Nlvr2Pass, InfoNceLoss, BarlowLoss, VqaLoss, Nlvr2Loss, vqa_candidate_rows  # noqa: F401  (vqa_candidate_rows: public here)
 from . import word_substitution as WS
 
 SEP_ID = 102
@@ -54,6 +55,7 @@ class GreedyAttack:
         self.words_to_sub_words: List[dict] = []
         self.replace_history: List[set] = []
         self.changes_verification: List[int] = []
+        self._de = None                # the whole dtext buffer of the last get_grad (what the tasks' rmcl_word_saliency reads)
         if self.tokenizer is not None and self.synonyms is None:
             if self.synonym == "cos_sim" and config.get("cos_sim", True):
                 path = config.get("embedding_path")
@@ -147,12 +149,29 @@ class GreedyAttack:
     def bind_candidate_keys(self, pc, k, own):
         pass
 
-    def get_grad(self, pl_module, pb, op, de):
+    def loss_of(self, pl_module):
+        """the objective's loss object (task_loss.py) against what ``bind_keys`` / ``bind_batch`` bound"""
         raise NotImplementedError(f"get_grad of {self.contrastive_framework} isn't implemented.")
 
+    def get_grad(self, pl_module, pb, op, de):
+        """get_grad (:406-452 MoCo, :623-668 Barlow-Twins, :856-898 NLVR2, :1284-1331 VQA): forward, the objective's batch loss, backward to
+        the OUTPUT of word_embeddings (what the reference's backward hook captures).  Returns (context for score(): the per-row loss
+        terms / the projections, grads view [B,L,D] of `de` (``saliency_of``), q / the projections / the cls rows)."""
+        loss = self.loss_of(pl_module)
+        ctx = loss.forward(pb, op, L.MODE_DATA).clone()
+        loss.backward(pb, op, L.MODE_DATA, dtext=de)
+        self._de = de
+        row0, step = self.saliency_of(pb)
+        return ctx, de.view(self.saliency_rows(pb), -1, de.shape[-1])[row0::step], ctx if loss.feats is None else loss.feats
+
     def score(self, pl_module, pc, ctx, owner, n_real, Bn):
-        """split_forward: [(candidate losses, index of the best candidate or -1)] per sample"""
-        raise NotImplementedError(f"split_forward of {self.contrastive_framework} isn't implemented.")
+        """split_forward: [(candidate losses, index of the best candidate or -1)] per sample, each candidate against its OWNER's targets"""
+        s, c = self.loss_of(pl_module).candidate_rows(pc, ctx, owner, n_real)
+        return self.select(s, c, owner, n_real, Bn)
+
+    def saliency_of(self, pb):
+        """(sequence of sentence 0, sequence step) of the saliency rows inside get_grad's gradient buffer"""
+        return 0, 1
 
     def word_scores(self, pl_module, pb, grads, Bn):
         """Per-sentence word importance lists computed from the device gradient, or None: the host path (the whole gradient is
@@ -260,9 +279,7 @@ class GreedyAttack:
         Bn, Lt = ids_host.shape
         nc = self.n_candidates
         Bc = Bn * nc
-        pb = eng.bind_batch(ids_host.to(dev), masks, batch["image"][0], tag="txtatk")
-        pc = None                                                   # candidate buffers: same image geometry, one row per candidate
-        op = eng.make_operand(pb)                                   # clean image, shared by every loop
+        pb, op = self.bind_batch(pl_module, batch, ids_host.to(dev), masks)       # clean image, shared by every loop
         de = torch.empty(Bn * Lt, pb.d.D, device=dev)
         k = k_modality.to(dev, torch.float32).contiguous()
         self.bind_keys(pl_module, pb, k)
@@ -325,37 +342,18 @@ class GreedyAttack_moco(GreedyAttack):
     def __init__(self, config, candidate_fn: Optional[Callable] = None, tokenizer=None, stopwords=None, synonyms=None):
         super().__init__(config, "moco", candidate_fn, tokenizer, stopwords, synonyms)
 
-    # ---- tensor side, same method names as the reference ----------------------------------------------------------
-    def get_grad(self, pl_module, pb, op, de):
-        """get_grad (:406-452): forward, batch-mean InfoNCE, backward to the OUTPUT of word_embeddings (what the
-        reference's backward hook captures).  Returns (per-row CE [B], grads view [B,L,D] = `de`, q [B,128])."""
-        eng = pl_module.engine
-        Bn = pb.B
-        eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
-        eng.heads_forward(pb, key=False)
-        eng.infonce(pb, 1.0 / Bn, want_dq=True)
-        ce0 = pb.rows[:, 0].clone()
-        eng.heads_backward(pb, pb.dq, None, with_grads=False)
-        eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=None, dtext=de)
-        return ce0, de.view(Bn, pb.d.L, -1), pb.q
+    def loss_of(self, pl_module):
+        return InfoNceLoss(pl_module)
 
     def split_forward(self, pl_module, pc, n_real):
         """split_forward (:454-492), device part: candidates through the encoder, per-row CE against the same keys."""
-        eng = pl_module.engine
-        eng.encoder_forward(pc, key=False, mode=L.MODE_INFER, patchesT=pc.patchesT, cls_tail=True)
-        eng.heads_forward(pc, key=False)
-        eng.infonce(pc, 0.0, want_dq=False)
-        return pc.rows[:n_real, 0]
+        return self.loss_of(pl_module).forward(pc, pc.patchesT, L.MODE_INFER, want_grad=False, scale=0.0)[:n_real]
 
     def bind_keys(self, pl_module, pb, k):
         pb.k.copy_(k)
 
     def bind_candidate_keys(self, pc, k, own):
         pc.k.copy_(k.index_select(0, own))
-
-    def score(self, pl_module, pc, ctx, owner, n_real, Bn):
-        cec = self.split_forward(pl_module, pc, n_real).cpu().tolist()
-        return self.select(ctx.cpu().tolist(), cec, owner, n_real, Bn)
 
     @staticmethod
     def select(ce0, cec, owner, n_real, Bn):
@@ -393,94 +391,25 @@ class GreedyAttack_barlowtwins(GreedyAttack):
     def bind_keys(self, pl_module, pb, k):
         self._zk = k
 
-    def get_grad(self, pl_module, pb, op, de):
-        """get_grad (:623-668): loss = on_diag + adv_lr * off_diag, gradient at the output of word_embeddings.
-        Returns (context for score(): the projections [B, H3], grads view [B,L,D], the projections)."""
-        eng = pl_module.engine
-        bb = eng.bt_bufs(pb.B, "txtatk")
-        eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
-        eng.heads_forward(pb, key=False, want_q=False)
-        mode = bool(pl_module.training)           # the attacked head is a deep copy: it keeps the module's train / eval flag
-        eng.bt_forward(bb, pb.cls, training=mode, track=False)
-        eng.bt_loss(bb, self._zk, float(pb.B), pl_module.adv_lr, 1.0, want_dz=True)
-        dcls = eng.bt_backward(bb, bb.dz, training=mode, with_grads=False)
-        eng.heads_backward(pb, None, dcls, with_grads=False)
-        eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=None, dtext=de)
-        z = bb.z.clone()
-        return z, de.view(pb.B, pb.d.L, -1), z
+    def loss_of(self, pl_module):
+        return BarlowLoss(pl_module, "txtatk", self._zk)
 
-    def score(self, pl_module, pc, ctx, owner, n_real, Bn):
-        """split_forward (:670-707).  Candidates go through encoder + head as ONE batch of n_real rows (BatchNorm statistics
-        over exactly those rows); then, sample by sample and candidate by candidate, row i of the projection matrix is
-        replaced and the loss of the whole matrix re-evaluated.  `t_save = ori_z[i]` (:691) is a view, so row i keeps its LAST
-        candidate while later samples are scored (same reference behaviour as the MoCo attack); the comparison baseline is
-        the loss of the UNMODIFIED matrix for every sample (:684-688).  All n_real + 1 losses are produced on the device
-        and read back once."""
-        eng = pl_module.engine
-        eng.encoder_forward(pc, key=False, mode=L.MODE_INFER, patchesT=pc.patchesT, cls_tail=True)
-        eng.heads_forward(pc, key=False, want_q=False)
-        bc = eng.bt_bufs(n_real, "txtatk_cand")
-        zc = eng.bt_forward(bc, pc.cls[:n_real].contiguous(), training=bool(pl_module.training), track=False)
-        Z = ctx.clone()
-        vals = torch.empty(n_real + 1, 2, device=Z.device)
-        lam = pl_module.adv_lr
-        eng.bt_loss_of(Z, self._zk, Bn, float(Bn), lam, 1.0, vals[0])
-        for r in range(n_real):
-            Z[owner[r]].copy_(zc[r])
-            eng.bt_loss_of(Z, self._zk, Bn, float(Bn), lam, 1.0, vals[1 + r])
-        v = vals.cpu().double()
-        loss = (v[:, 0] + lam * v[:, 1]).tolist()
+    @staticmethod
+    def select(base, loss, owner, n_real, Bn):
+        """[(losses, first strict maximum above the loss of the UNMODIFIED matrix `base[0]`, or -1)] per sample (:684-688) from the
+        n_real losses of BarlowLoss.candidate_rows' sequential row replacement"""
         out, r = [], 0
         for b in range(Bn):
-            best, best_j, losses = loss[0], -1, []
-            j = 0
+            best, best_j, r0 = base[0], -1, r
             while r < n_real and owner[r] == b:
-                losses.append(loss[1 + r])
-                if loss[1 + r] > best:
-                    best, best_j = loss[1 + r], j
+                if loss[r] > best:
+                    best, best_j = loss[r], r - r0
                 r += 1
-                j += 1
-            out.append((losses, best_j))
+            out.append((loss[r0:r], best_j))
         return out
 
 
 # ---- the fine-tuning tasks (greedy_attack_vilt.py:835-1043 NLVR2, :1263-1478 VQA) ------------------------------------------------------
-HEAD_ROWS = 256                       # include/rmcl.h: the classifier launchers take at most 256 rows
-
-
-def _chunks(n: int, size: int = HEAD_ROWS):
-    return [(s, min(n, s + size)) for s in range(0, n, size)]
-
-
-def vqa_candidate_rows(eng, cls: torch.Tensor, labels: torch.Tensor, scores: torch.Tensor, A: int, out: torch.Tensor = None,
-                       tag: str = "txtatk_cand") -> torch.Tensor:
-    """Per-row BCE sums (rmcl_vqa_bce rows[:, 0]) of vqa_classifier(cls [R, D]) against the label / score tables [R, A] (device, one
-    row per cls row), R of any size: the head launcher takes at most 256 rows, so the rows go through it in chunks.  Every row of
-    the head and of the loss is independent of the others, so the chunking changes no value.  Returns `out` [R] on the device."""
-    R = int(cls.shape[0])
-    out = torch.empty(R, dtype=torch.float32, device=eng.device) if out is None else out
-    for s, e in _chunks(R):
-        vb = eng.vqa_bufs(e - s, tag)
-        vb.labels, vb.scores, vb.A = labels[s:e].contiguous(), scores[s:e].contiguous(), A
-        eng.vqa_forward(vb, cls[s:e])
-        eng.vqa_bce(vb, 1.0, want_dz=False)
-        out[s:e].copy_(vb.rows[:, 0])
-    return out
-
-
-def nlvr2_candidate_rows(eng, cls2: torch.Tensor, labels: torch.Tensor, out: torch.Tensor = None, tag: str = "txtatk_cand") -> torch.Tensor:
-    """Per-row CE (rmcl_nlvr2_ce rows) of nlvr2_classifier(cls2 [R, 2 hidden]) against labels [R] (int32, device), in chunks of 256."""
-    R = int(cls2.shape[0])
-    out = torch.empty(R, dtype=torch.float32, device=eng.device) if out is None else out
-    for s, e in _chunks(R):
-        nb = eng.nlvr2_bufs(e - s, tag)
-        nb.labels.copy_(labels[s:e])
-        eng.nlvr2_forward(nb, cls2[s:e])
-        eng.nlvr2_ce(nb, 1.0, want_dz=False)
-        out[s:e].copy_(nb.rows)
-    return out
-
-
 def word_spans(mappings, W: int) -> torch.Tensor:
     """words_to_sub_words maps -> spans [B, W, 2] int32 (first token position counting [CLS] as 0, token count); a word's tokens
     are consecutive (calc_words_to_sub_words :346-360).  Entries behind a sentence's words: (0, 0)."""
@@ -504,7 +433,6 @@ class _TaskAttack(GreedyAttack):
 
     def __init__(self, config, framework, tokenizer=None, stopwords=None, synonyms=None):
         super().__init__(config, framework, None, tokenizer, stopwords, synonyms)
-        self._de = None                # the whole dtext buffer of the last get_grad (what rmcl_word_saliency reads)
         if self.tokenizer is None:
             raise NotImplementedError(
                 f"{framework}_attacked with text_view=True runs the word-level attack only: config['tokenizer'] must be a tokenizer "
@@ -513,10 +441,6 @@ class _TaskAttack(GreedyAttack):
 
     def bind_keys(self, pl_module, pb, k):
         pass
-
-    def saliency_of(self, pb):
-        """(sequence of sentence 0, sequence step) of the saliency rows inside get_grad's gradient buffer"""
-        return 0, 1
 
     def word_scores(self, pl_module, pb, grads, Bn):
         if not self.device_scores:
@@ -564,35 +488,8 @@ class GreedyAttack_vqa(_TaskAttack):
         self._tab = eng.vqa_targets(eng.vqa_bufs(pb.B, "txtatk"), batch["vqa_labels"], batch["vqa_scores"])
         return pb, op
 
-    def get_grad(self, pl_module, pb, op, de):
-        """get_grad (:1284-1331): forward, BCE mean x N (incoming gradient 1), backward to the OUTPUT of word_embeddings.
-        Returns (per-row BCE sums [B], grads view [B,L,D] = `de`, the cls rows)."""
-        eng = pl_module.engine
-        vb = self._tab
-        eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
-        eng.heads_forward(pb, key=False, want_q=False, wgrad=False)
-        eng.vqa_forward(vb, pb.cls)
-        eng.vqa_bce(vb, 1.0, want_dz=True)
-        s = vb.rows[:, 0].clone()
-        dcls = eng.vqa_backward(vb, vb.dz, with_grads=False)
-        eng.heads_backward(pb, None, dcls, with_grads=False)
-        eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=None, dtext=de)
-        self._de = de
-        return s, de.view(pb.B, pb.d.L, -1), pb.cls
-
-    def score(self, pl_module, pc, ctx, owner, n_real, Bn):
-        """split_forward (:1333-1369): candidates through the encoder and vqa_classifier, each against its OWNER's label / score
-        tables (gathered on the device); the per-row BCE sums of batch and candidates come back in one transfer."""
-        eng = pl_module.engine
-        eng.encoder_forward(pc, key=False, mode=L.MODE_INFER, patchesT=pc.patchesT, cls_tail=True)
-        eng.heads_forward(pc, key=False, want_q=False, wgrad=False)
-        own = torch.tensor(owner[:n_real], device=eng.device)
-        vb = self._tab
-        rows = torch.empty(Bn + n_real, dtype=torch.float32, device=eng.device)
-        rows[:Bn].copy_(ctx)
-        vqa_candidate_rows(eng, pc.cls[:n_real], vb.labels.index_select(0, own), vb.scores.index_select(0, own), vb.A, out=rows[Bn:])
-        host = rows.cpu().tolist()
-        return self.select(host[:Bn], host[Bn:], owner, n_real, Bn)
+    def loss_of(self, pl_module):
+        return VqaLoss(pl_module, self._tab)                    # get_grad :1284-1331 (BCE mean x N), split_forward :1333-1369
 
 
 class GreedyAttack_nlvr2(_TaskAttack):
@@ -608,11 +505,10 @@ class GreedyAttack_nlvr2(_TaskAttack):
         self._nb = None
 
     def bind_batch(self, pl_module, batch, ids, masks):
-        from ..vilt.modules.objectives import Nlvr2Pass
         eng = pl_module.engine
         npass = Nlvr2Pass.bind(pl_module, dict(batch, text_ids=ids, text_masks=masks), "txtatk")
         npass.clean_operands(full_buffer=False)
-        self._nb = eng.nlvr2_bufs(npass.B, "txtatk")
+        self._nb, self._pair = eng.nlvr2_bufs(npass.B, "txtatk"), npass.pair
         eng.nlvr2_labels(self._nb, batch["answers"])
         return npass, npass.ops
 
@@ -623,53 +519,22 @@ class GreedyAttack_nlvr2(_TaskAttack):
         return (1, 2) if npass.pair else (0, 1)
 
     def set_text(self, npass, ids, masks):
-        for pv in npass.views:
-            pv.text_ids = ids.repeat_interleave(2, dim=0) if npass.pair else ids
-            pv.text_mask = masks.repeat_interleave(2, dim=0) if npass.pair else masks
+        npass.set_text(ids, masks)
 
-    def get_grad(self, pl_module, npass, ops, de):
-        """get_grad (:856-898).  Returns (per-row CE [B], grads view [B,L,D]: the image_1 sequences of `de`, the cls rows)."""
-        eng = pl_module.engine
-        nb = self._nb
-        cls2 = npass.forward(L.MODE_DATA, wgrad=False)
-        eng.nlvr2_forward(nb, cls2)
-        eng.nlvr2_ce(nb, 1.0, want_dz=True)
-        s = nb.rows.clone()
-        dcls2 = eng.nlvr2_backward(nb, nb.dz, with_grads=False)
-        D = npass.views[0].d.D
-        for i, (pv, op) in enumerate(zip(npass.views, npass.ops)):
-            if not npass.pair and i == 0:
-                continue                                  # the image_0 pass's text gradient is never read (emb_grads[0] is infer2's)
-            dc = dcls2.view(2 * npass.B, D) if npass.pair else dcls2[:, i * D:(i + 1) * D].contiguous()
-            eng.heads_backward(pv, None, dc, with_grads=False)
-            eng.encoder_backward(pv, L.MODE_DATA, op, pv.dcls, cls_only=True, dpatches=None, dtext=de)
-        self._de = de
-        row0, step = self.saliency_of(npass)
-        return s, de.view(-1, npass.views[0].d.L, D)[row0::step], cls2
+    def loss_of(self, pl_module):
+        # two-pass form: the image_0 pass's text gradient is never read (emb_grads[0] is infer2's), so its backward is not run
+        return Nlvr2Loss(pl_module, self._nb, skip=() if self._pair else (0,))     # get_grad :856-898, split_forward :900-931
 
     def bind_candidates(self, pl_module, npass, ops, own, cids, cmasks):
-        from ..vilt.modules.objectives import Nlvr2Pass
+        """candidates carry their owner's image pair (and, in ``score``, its label)"""
         eng = pl_module.engine
-        Bc = int(own.numel())
         views = []
         for i, (pv, op) in enumerate(zip(npass.views, ops)):
             o = torch.stack([2 * own, 2 * own + 1], dim=1).reshape(-1) if npass.pair else own
             pc = eng.twin(pv, f"txtatk_cand_{i}", owner=o)
-            pc.text_ids = cids.repeat_interleave(2, dim=0) if npass.pair else cids
-            pc.text_mask = cmasks.repeat_interleave(2, dim=0) if npass.pair else cmasks
+            pc.text_ids, pc.text_mask = npass.text_of(cids, cmasks)
             torch.index_select(op.view(pv.B, -1), 0, o, out=pc.patchesT.view(int(o.numel()), -1))
             views.append(pc)
-        cpass = Nlvr2Pass(eng, views, Bc, npass.pair)
+        cpass = Nlvr2Pass(eng, views, int(own.numel()), npass.pair)
         cpass.ops = [pc.patchesT for pc in views]
         return cpass
-
-    def score(self, pl_module, cpass, ctx, owner, n_real, Bn):
-        """split_forward (:900-931): candidates carry their owner's image pair and label; per-row CE from rmcl_nlvr2_ce."""
-        eng = pl_module.engine
-        cls2 = cpass.forward(L.MODE_INFER, wgrad=False)
-        own = torch.tensor(owner[:n_real], device=eng.device)
-        rows = torch.empty(Bn + n_real, dtype=torch.float32, device=eng.device)
-        rows[:Bn].copy_(ctx)
-        nlvr2_candidate_rows(eng, cls2[:n_real].contiguous(), self._nb.labels.index_select(0, own), out=rows[Bn:])
-        host = rows.cpu().tolist()
-        return self.select(host[:Bn], host[Bn:], owner, n_real, Bn)

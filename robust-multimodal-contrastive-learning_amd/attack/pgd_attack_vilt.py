@@ -6,9 +6,13 @@ eps-projection) as HIP kernels with no deepcopy of the encoder and no weight-gra
 (:418-483) on the VQA soft-target BCE."""
 from __future__ import annotations
 
+import os
+
 import torch
 
 from .. import _lib as L
+from .._lib import lib, check
+from ..task_loss import Nlvr2Pass, InfoNceLoss, BarlowLoss, VqaLoss, Nlvr2Loss
 
 
 def device_image(eng, img) -> torch.Tensor:
@@ -39,6 +43,11 @@ def ascent_tail(eng, pb, step, K, lr, eps, keep_prev=False, full=None) -> torch.
 
 
 class PGDAttack:
+    """The K-step loop on one image per sample: a subclass names its loss object (``loss_of``) and how ``pgd_attack`` binds a batch."""
+    bind_tag = "moco"
+    fp32_twin = True          # the loop runs in Engine.pgd_bufs: the fp32 twin when the engine runs PGD in fp32 (:141)
+    split_lanes = False       # two half-batch chains where Engine.lanes offers them (_attack_lanes)
+
     def __init__(self, config, contrastive_framework):
         self.contrastive_framework = contrastive_framework
         self.adv_steps_img = config["adv_steps_img"]
@@ -46,71 +55,74 @@ class PGDAttack:
         self.adv_max_norm_img = config["adv_max_norm_img"]
         self.max_image_len = config["max_image_len"]
 
-    def pgd_attack(self, pl_module, batch, k_image):
+    def loss_of(self, pl_module, pb, target):
+        """the objective's loss object (task_loss.py) against `target`: the keys, or the buffers holding the batch's labels"""
         raise NotImplementedError(f"pgd_attack of {self.contrastive_framework} isn't implemented.")
 
-    def _attack_chain(self, eng, pb, cls_grad, clean_op=None, keep_prev=False, full=None):
-        """K steps as one chain on the current stream: encoder forward at img + delta, ``cls_grad(step)`` (the pooler / projection
-        heads, the objective's loss and its head backward: returns (dq, dcls_extra), the gradient at the projection and at the pooled
-        cls rows, for ``Engine.heads_backward``), data-gradient backward, ``ascent_tail``.  Every step's update kernel also writes
-        the next forward's operand, step 0 starts from the implicit delta_0 = 0: no zero fills, no separate add + cast passes, no
-        delta copy inside the loop.  ``clean_op``: the caller's cast of the clean image in pb.patchesT, if it has one; ``full``: where
-        the attacked view's operand goes (``ascent_tail``).  Returns ``pb.delta`` = delta_K."""
-        K = self.adv_steps_img
-        op = clean_op if clean_op is not None else eng.make_operand(pb)     # img_init + delta_0, delta_0 = 0 (:136,144)
-        for step in range(K):
-            eng.encoder_forward(pb, key=False, mode=L.MODE_DATA, patchesT=op, cls_tail=True)
-            dq, dcls_extra = cls_grad(step)
-            eng.heads_backward(pb, dq, dcls_extra, with_grads=False)
-            eng.encoder_backward(pb, L.MODE_DATA, op, pb.dcls, cls_only=True, dpatches=pb.gpatch)
-            op = ascent_tail(eng, pb, step, K, self.adv_lr_img, self.adv_max_norm_img, keep_prev, full)
-        return pb.delta
+    def bind(self, pl_module, batch, img_init, k_modality):          # -> (pass buffers, target) for the public ``pgd_attack``
+        return pl_module.engine.bind_batch(batch["text_ids"], batch["text_masks"], img_init, tag=self.bind_tag), k_modality
 
+    def pgd_attack(self, pl_module, batch, k_modality=None):
+        eng = pl_module.engine
+        img_init = device_image(eng, batch["image"][0])
+        pb, target = self.bind(pl_module, batch, img_init, k_modality)
+        delta_p = self.attack_patches(pl_module, pb, target, keep_prev=True)
+        # the reference leaves batch['image'][0] = img_init + delta_{K-1} behind (:144)
+        batch["image"][0] = img_init + eng.patches_to_image(pb.delta_prev, pb)
+        return eng.patches_to_image(delta_p, pb)
 
-class PGDAttack_moco(PGDAttack):
-    def __init__(self, config):
-        super().__init__(config, "moco")
-
-    def attack_patches(self, pl_module, pb, k, before_first_loss=None, clean_out=None, keep_prev=False, clean_op=None, key_stream=None, key_event=None):
+    def attack_patches(self, pl_module, pb, target, before_first_loss=None, clean_out=None, keep_prev=False, clean_op=None, key_stream=None,
+                       key_event=None):
         """K-step attack in patch layout.  Leaves delta_K in ``pb.delta`` and the ATTACKED VIEW's operand
         cast(img + delta_{K-1} + delta_K) (see compute_pgd / objectives.py:176) in ``pb.patchesT_full``; with ``keep_prev``
         also delta_{K-1} in ``pb.delta_prev`` (the public ``pgd_attack`` needs it for the batch image it leaves behind).
-
+        ``target``: the keys - VQA: VqaBuffers holding this batch's label / score tables (Engine.vqa_targets), the loop's head runs in them.
         ``before_first_loss``: callback run once between the first encoder forward and the first InfoNCE (the
         caller joins the key-encoder stream there).  ``clean_out``: dict that receives the clean-query statistics:
         step 0 evaluates the query encoder at img + delta_0 = img, i.e. it IS the clean forward of
         objectives.py:267-275, so that forward is not computed twice when dropout is off."""
         eng = pl_module.engine
+        loss = self.loss_of(pl_module, pb, target)
+        pb0, pb = pb, (eng.pgd_bufs(pb) if self.fp32_twin else pb)
+        lanes = eng.lanes(pb) if (self.split_lanes and pb is pb0) else None
+        if lanes is not None:
+            return self._attack_lanes(eng, pb, loss, lanes, before_first_loss, clean_out, keep_prev, clean_op, key_stream, key_event)
+        first = {n: v for n, v in (("before_loss", before_first_loss), ("clean_out", clean_out)) if v is not None}
+        return self._attack_chain(eng, pb, loss, first, clean_op if pb is pb0 else None, keep_prev, pb0.patchesT_full)
+
+    def _attack_chain(self, eng, pb, loss, first, clean_op=None, keep_prev=False, full=None):
+        """K steps as one chain on the current stream: the loss object's forward at img + delta (encoder, pooler / projection heads,
+        the objective's loss; step 0 with the hooks `first`) and its data-gradient backward, then ``ascent_tail``.  Every step's
+        update kernel also writes the next forward's operand, step 0 starts from the implicit delta_0 = 0: no zero fills, no separate
+        add + cast passes, no delta copy inside the loop.  ``clean_op``: the caller's cast of the clean image in pb.patchesT, if it
+        has one; ``full``: where the attacked view's operand goes (``ascent_tail``).  Returns ``pb.delta`` = delta_K."""
         K = self.adv_steps_img
+        op = clean_op if clean_op is not None else eng.make_operand(pb)     # img_init + delta_0, delta_0 = 0 (:136,144)
+        for step in range(K):
+            loss.forward(pb, op, L.MODE_DATA, K, wgrad=False, **(first if step == 0 else {}))
+            loss.backward(pb, op, L.MODE_DATA, dpatches=pb.gpatch)
+            op = ascent_tail(eng, pb, step, K, self.adv_lr_img, self.adv_max_norm_img, keep_prev, full)
+        return pb.delta
+
+
+class PGDAttack_moco(PGDAttack):
+    split_lanes = True
+
+    def __init__(self, config):
+        super().__init__(config, "moco")
+
+    def loss_of(self, pl_module, pb, k):
         if k is not None and k.data_ptr() != pb.k.data_ptr():
             pb.k.copy_(k)
-        pb0 = pb
-        pb = eng.pgd_bufs(pb)                                 # fp32 twin when the engine runs PGD in fp32 (:141)
-        lanes = eng.lanes(pb) if pb is pb0 else None
-        if lanes is not None:
-            return self._attack_lanes(eng, pb, lanes, K, before_first_loss, clean_out, keep_prev, clean_op, key_stream, key_event)
+        return InfoNceLoss(pl_module, metrics=False)          # CE(label 0) / K (:152-158); only dq and the prediction are read
 
-        def cls_grad(step):
-            eng.heads_forward(pb, key=False, wgrad=False)
-            if step == 0 and before_first_loss is not None:
-                before_first_loss()
-            # CE(label 0) / K, mean over the batch (:152-158); gradient wrt q only
-            eng.infonce(pb, grad_scale=1.0 / (pb.B * K), want_dq=True, metrics=False)     # (only dq and the prediction are read)
-            if step == 0 and clean_out is not None:
-                clean_out["prediction"] = pb.rows[:, 1].clone()
-                clean_out["q"] = pb.q.clone()
-            return pb.dq, None
-
-        return self._attack_chain(eng, pb, cls_grad, clean_op if pb is pb0 else None, keep_prev, pb0.patchesT_full)
-
-    def _attack_lanes(self, eng, pb, lanes, K, before_first_loss, clean_out, keep_prev, clean_op, key_stream, key_event=None):
+    def _attack_lanes(self, eng, pb, loss, lanes, before_first_loss, clean_out, keep_prev, clean_op, key_stream, key_event=None):
         """The same K steps as two independent half-batch chains (Engine.lanes): lane 0 on the current stream, lane 1 on
         ``eng.side_stream`` (RMCL_LANE_LAG_US: an extra start delay of lane 1; the host's call-by-call enqueue order already staggers them).
         Every per-sample buffer of a lane is a view of ``pb``'s, so ``pb`` ends up exactly as the one-chain loop leaves it.
         ``key_stream`` / ``key_event``: where the keys are produced, if not on the current stream (lane 1 waits for the event - or the
         whole stream - by itself before its first InfoNCE)."""
-        import os
-        from .._lib import lib, check
+        K = self.adv_steps_img
         main = torch.cuda.current_stream()
         # lane 1 runs on the engine's side stream, BEHIND the key-encoder forward the caller may have put there: HIP multiplexes its
         # streams onto four hardware queues, and a fifth stream of this process shared the main stream's queue - the lanes then ran
@@ -141,7 +153,7 @@ class PGDAttack_moco(PGDAttack):
                 for i, ln in enumerate(lanes):
                     with on(i):
                         eng.encoder_forward(ln, key=False, mode=L.MODE_DATA, patchesT=ops[i], cls_tail=True)
-                        eng.heads_forward(ln, key=False, wgrad=False)
+                        loss.pool(ln, False)
                 for i, ln in enumerate(lanes):
                     with on(i):
                         if step == 0:
@@ -151,11 +163,11 @@ class PGDAttack_moco(PGDAttack):
                                 streams[i].wait_event(key_event)
                             elif i > 0 and key_stream is not None and key_stream is not streams[i]:
                                 streams[i].wait_stream(key_stream)
-                        eng.infonce(ln, grad_scale=1.0 / (pb.B * K), want_dq=True, metrics=False)       # 1 / B of the WHOLE batch (:152-158)
+                        loss.loss_forward(ln, ln.cls, loss.scale(pb, K), True)                      # 1 / B of the WHOLE batch (:152-158)
                         if step == 0 and clean_out is not None:
                             clean_out["prediction"][i * ln.B:(i + 1) * ln.B].copy_(ln.rows[:, 1])
                             clean_out["q"][i * ln.B:(i + 1) * ln.B].copy_(ln.q)
-                        eng.heads_backward(ln, ln.dq, None, with_grads=False)
+                        loss.head_backward(ln, False)
                 for i, ln in enumerate(lanes):
                     with on(i):
                         eng.encoder_backward(ln, L.MODE_DATA, ops[i], ln.dcls, cls_only=True, dpatches=ln.gpatch)
@@ -170,46 +182,24 @@ class PGDAttack_moco(PGDAttack):
                 main.wait_stream(st)
         return pb.delta
 
-    def pgd_attack(self, pl_module, batch, k_modality=None):
-        eng = pl_module.engine
-        img_init = device_image(eng, batch["image"][0])
-        pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init)
-        delta_p = self.attack_patches(pl_module, pb, k_modality, keep_prev=True)
-        # the reference leaves batch['image'][0] = img_init + delta_{K-1} behind (:144)
-        batch["image"][0] = img_init + eng.patches_to_image(pb.delta_prev, pb)
-        return eng.patches_to_image(delta_p, pb)
-
 
 class PGDAttack_bartlowtwins(PGDAttack):
     """attack/pgd_attack_vilt.py:178-236 (the reference's spelling of the class name is kept): loss =
     (on_diag + adv_lr * off_diag) / K on c = q^T k / B over the LOCAL batch, q = barlowtwins_head(cls_feats) of a deep copy of
     the head: batch statistics in training (the module's running estimates stay untouched), the running estimates in
     validation."""
+    bind_tag = "bt"
+    fp32_twin = False         # (this loop has always run in the batch's own buffers)
 
     def __init__(self, config):
         super().__init__(config, "barlowtwins")
 
-    def attack_patches(self, pl_module, pb, zk, keep_prev=False, clean_op=None):
-        eng = pl_module.engine
-        K = self.adv_steps_img
-        bb = eng.bt_bufs(pb.B, "pgd")
-        mode = bool(pl_module.training)           # deepcopy(pl_module.barlowtwins_head) keeps the train / eval flag (:189)
+    def loss_of(self, pl_module, pb, zk):
+        return BarlowLoss(pl_module, "pgd", zk)
 
-        def cls_grad(step):
-            eng.heads_forward(pb, key=False, want_q=False, wgrad=False)
-            eng.bt_forward(bb, pb.cls, training=mode, track=False)
-            eng.bt_loss(bb, zk, float(pb.B), pl_module.adv_lr, 1.0 / K, want_dz=True)
-            return None, eng.bt_backward(bb, bb.dz, training=mode, with_grads=False)
-
-        return self._attack_chain(eng, pb, cls_grad, clean_op, keep_prev)
-
-    def pgd_attack(self, pl_module, batch, k_modality=None):
-        eng = pl_module.engine
-        img_init = device_image(eng, batch["image"][0])
-        pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init, tag="bt")
-        delta_p = self.attack_patches(pl_module, pb, k_modality.to(eng.device, torch.float32).contiguous(), keep_prev=True)
-        batch["image"][0] = img_init + eng.patches_to_image(pb.delta_prev, pb)
-        return eng.patches_to_image(delta_p, pb)
+    def bind(self, pl_module, batch, img_init, k_modality):
+        pb, _ = super().bind(pl_module, batch, img_init, None)
+        return pb, k_modality.to(pl_module.engine.device, torch.float32).contiguous()
 
 
 class PGDAttack_vqa(PGDAttack):
@@ -218,35 +208,17 @@ class PGDAttack_vqa(PGDAttack):
     module and its backward() also leaves weight gradients in .grad; under its fp16 recipe those are removed by the loss scale
     (INTEGRATION.md), so here the loop runs data gradients only: encoder MODE_DATA, head backward without weight gradients -
     nothing is written into the gradient arena."""
+    bind_tag = "vqa_att"
 
     def __init__(self, config):
         super().__init__(config, "vqa")
 
-    def attack_patches(self, pl_module, pb, vb_tables, clean_op=None, keep_prev=False):
-        """Leaves delta_K in ``pb.delta`` and the attacked view's operand cast(img + delta_{K-1} + delta_K) (compute_pgd,
-        objectives.py:176) in ``pb.patchesT_full``.  ``vb_tables``: VqaBuffers holding this batch's label / score tables
-        (Engine.vqa_targets); the loop's head passes run in them."""
-        eng = pl_module.engine
-        pb0 = pb
-        pb = eng.pgd_bufs(pb)                                 # fp32 twin when the engine runs PGD in fp32
-        vb = vb_tables
+    def loss_of(self, pl_module, pb, vb_tables):
+        return VqaLoss(pl_module, vb_tables)                    # :444-460 ... :464-481
 
-        def cls_grad(step):
-            eng.heads_forward(pb, key=False, want_q=False, wgrad=False)
-            eng.vqa_forward(vb, pb.cls)
-            eng.vqa_bce(vb, 1.0, want_dz=True)                                        # :444-460, d loss / d logits
-            return None, eng.vqa_backward(vb, vb.dz, with_grads=False)
-
-        return self._attack_chain(eng, pb, cls_grad, clean_op if pb is pb0 else None, keep_prev, pb0.patchesT_full)   # :464-481
-
-    def pgd_attack(self, pl_module, batch, k_modality=None):
-        eng = pl_module.engine
-        img_init = device_image(eng, batch["image"][0])
-        pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], img_init, tag="vqa_att")
-        vb = eng.vqa_targets(eng.vqa_bufs(pb.B, "pgd"), batch["vqa_labels"], batch["vqa_scores"])
-        delta_p = self.attack_patches(pl_module, pb, vb, keep_prev=True)
-        batch["image"][0] = img_init + eng.patches_to_image(pb.delta_prev, pb)
-        return eng.patches_to_image(delta_p, pb)
+    def bind(self, pl_module, batch, img_init, k_modality):
+        pb, eng = super().bind(pl_module, batch, img_init, None)[0], pl_module.engine
+        return pb, eng.vqa_targets(eng.vqa_bufs(pb.B, "pgd"), batch["vqa_labels"], batch["vqa_scores"])
 
 
 class PGDAttack_nlvr2(PGDAttack):
@@ -266,7 +238,7 @@ class PGDAttack_nlvr2(PGDAttack):
         objectives.py:166-174) in ``pv.patchesT_full``; with ``keep_prev`` also delta_{K-1} in ``pv.delta_prev``.  ``nb``: Nlvr2Buffers
         holding the batch's labels; the loop's head passes run in them."""
         eng = pl_module.engine
-        K = self.adv_steps_img
+        K, loss = self.adv_steps_img, Nlvr2Loss(pl_module, nb)
         a0, a1 = self.attack_idx[0], self.attack_idx[1]
         views = npass.views
         if npass.pair:
@@ -280,11 +252,8 @@ class PGDAttack_nlvr2(PGDAttack):
                 pv.delta_prev.zero_()
                 eng.make_operand(pv, out=pv.patchesT_full)
         for step in range(K):
-            cls2 = npass.forward(L.MODE_DATA, wgrad=False)
-            eng.nlvr2_forward(nb, cls2)
-            eng.nlvr2_ce(nb, 1.0 / K, want_dz=True)                          # CE / adv_steps_img (:296)
-            dcls2 = eng.nlvr2_backward(nb, nb.dz, with_grads=False)
-            npass.backward(dcls2, L.MODE_DATA, with_grads=False, dpatches=attacked)
+            loss.forward(npass, None, L.MODE_DATA, K, wgrad=False)                            # CE / adv_steps_img (:296)
+            loss.backward(npass, None, L.MODE_DATA, dpatches=attacked)
             for i, pv in enumerate(views):
                 if not attacked[i]:
                     continue
@@ -302,8 +271,6 @@ class PGDAttack_nlvr2(PGDAttack):
 
     def delta_log(self, pl_module, npass, batch):
         """(mean_c ||delta_0||_c + mean_c ||delta_1||_c) / sum(attack_idx) (objectives.py:179-184), from the patch-layout deltas."""
-        from .._lib import lib, check, P, I64
-        from ..runtime import stream_ptr
         eng = pl_module.engine
         n_att = sum(self.attack_idx)
         shapes = [tuple(batch["image_0"][0].shape), tuple(batch["image_1"][0].shape)]
@@ -312,14 +279,12 @@ class PGDAttack_nlvr2(PGDAttack):
             return (torch.linalg.norm(d0, dim=1).mean() + torch.linalg.norm(d1, dim=1).mean()) / n_att
         out = torch.zeros(len(npass.views), dtype=torch.float32, device=eng.device)
         for i, pv in enumerate(npass.views):                                 # (pair form: one sum over both images of the same extent)
-            check(lib.rmcl_delta_channel_norm(P(pv.delta), P(out[i:i + 1]), I64(pv.delta.shape[0]), 3, pv.d.patch_k // 3, stream_ptr()),
-                  "delta_norm")
+            eng.delta_channel_norm(pv, out[i:i + 1])
         n_pix = [float(npass.B * sh[2] * sh[3]) for sh in shapes]           # every image of a key: B x H x W pixels
         return ((out[0] / n_pix[0] if npass.pair else out[0] / n_pix[0] + out[1] / n_pix[1]) / n_att).reshape(())
 
     def pgd_attack(self, pl_module, batch, k_modality=None):
         """The reference's public form: returns (delta_0, delta_1) in image layout and leaves image_k = img_k + delta_{K-1} in the batch."""
-        from ..vilt.modules.objectives import Nlvr2Pass
         eng = pl_module.engine
         imgs = []
         for key in ("image_0", "image_1"):

@@ -828,6 +828,13 @@ class Engine:
         pb.loss_i += 1
         return pb.loss_sum
 
+    def delta_channel_norm(self, pb: PassBuffers, out: torch.Tensor = None) -> torch.Tensor:
+        """out (default: the next zeroed scalar of `pb`, i.e. ``pb.loss_sum``) += sum over the pixels of `pb`'s patch-layout delta of
+        the L2 norm over the three channels: the numerator of torch.linalg.norm(delta, dim=1).mean() (objectives.py:184)."""
+        out = self.zero_scalar(pb) if out is None else out
+        check(lib.rmcl_delta_channel_norm(P(pb.delta), P(out), I64(pb.delta.shape[0]), 3, pb.d.patch_k // 3, stream_ptr()), "delta_norm")
+        return out
+
     def infonce(self, pb: PassBuffers, grad_scale: float, want_dq: bool, metrics: bool = True):
         """metrics=False: the caller reads only loss / dq (PGD passes) - the bf16 engine's form then skips the queue-distance sums.
         bf16 passes run the split-bf16 matrix-core form (include/rmcl.h rmcl_infonce_split_bf16), fp32 passes the exact one."""

@@ -12,6 +12,7 @@ from ... import _lib as L
 from ..._lib import lib, check, P, I64
 from ...runtime import stream_ptr
 from ...attack.pgd_attack_vilt import device_image
+from ...task_loss import Nlvr2Pass, InfoNceLoss, BarlowLoss, VqaLoss, Nlvr2Loss
 from . import dist_utils
 
 
@@ -37,6 +38,34 @@ def _scalar(t):
     return t.reshape(())
 
 
+def _loss_view(pl_module, loss, view, op, **hooks):
+    """One loss view of an objective through its loss object (task_loss.py): forward on `op` (MODE_FULL where a gradient will be wanted);
+    returns the loss value, whose backward runs loss -> head -> pooler -> encoder into the gradient arena, then ``after_backward``."""
+    need_grad = torch.is_grad_enabled() and pl_module.training
+    loss.forward(view, op, L.MODE_FULL if need_grad else L.MODE_INFER, want_grad=need_grad, defer=True, **hooks)
+    value = loss.value
+    if not need_grad:
+        return value
+
+    def backward(grad_out):
+        loss.backward(view, op, L.MODE_FULL, g=grad_out)
+        # one attacked view = one backward per step: its gradient all-reduces can start layer by layer right away
+        # reduced over ranks once per step, after the step's last closure; a single closure (the image-view step) gets
+        # per-layer all-reduces that start while the layers below are still in their backward
+        pl_module.after_backward(overlap=True)
+
+    return _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+
+
+def _log_delta(pl_module, pb, task, phase):
+    """compute_pgd's delta log (:184) of a single-image objective, from the patch-layout delta the attack left in `pb`"""
+    pl_module.engine.delta_channel_norm(pb)
+    # mean over ALL pixels of the (padded) batch image like torch.linalg.norm(delta, dim=1).mean() (:184); the pad pixels of
+    # a zero-padded batch carry delta = 0 and are not stored in the patch layout
+    n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
+    pl_module.log(f"{task}_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
+
+
 def compute_pgd(pl_module, batch, loss_name, k_modality=None):
     """objectives.py:160-188 for loss_name == "moco"."""
     img_delta = pl_module.pgd_attacker.pgd_attack(pl_module, batch, k_modality=k_modality)
@@ -58,25 +87,11 @@ def compute_geometric(pl_module, batch, loss_name, k_modality=None):
     return batch
 
 
-def _only_moco(pl_module):
-    ln = pl_module.hparams.config["loss_names"]
-    return ln.get("moco", 0) > 0 and sum(1 for v in ln.values() if v > 0) == 1
-
-
 def _attacked_view(pl_module, pv, op, k, suffix, success_name, prediction_original, ret, phase, before_loss=None):
     """One loss view (objectives.py:287-317 / :324-354 / :362-392; suffix "clean": the clean query of :267-275 as a
     loss, BASELINE configs[1]): encoder forward on `op` with the text in `pv`, InfoNCE against the queue, metrics, and a
     loss tensor whose backward runs the HIP backward."""
-    eng = pl_module.engine
-    B = pv.B
-    need_grad = torch.is_grad_enabled() and pl_module.training
-    eng.encoder_forward(pv, key=False, mode=L.MODE_FULL if need_grad else L.MODE_INFER, patchesT=op, cls_tail=True)
-    eng.heads_forward(pv, key=False)
-    if before_loss is not None:
-        before_loss()                                  # e.g. join the key-encoder stream: k is needed from here on
-    if pv.k.data_ptr() != k.data_ptr():
-        pv.k.copy_(k)
-    eng.infonce(pv, 1.0 / B, want_dq=need_grad)
+    value = _loss_view(pl_module, InfoNceLoss(pl_module), pv, op, before_loss=before_loss, k=k)   # (before_loss: e.g. join the key-encoder stream)
     rows = pv.rows
     if phase == "train" and success_name is not None:
         pl_module.log(f"moco_attack/{success_name}", (rows[:, 1] != prediction_original).float().mean())
@@ -84,21 +99,8 @@ def _attacked_view(pl_module, pv, op, k, suffix, success_name, prediction_origin
     for j, name in ((3, "pos_dist"), (4, "pos_cosine"), (5, "pos_dot"), (6, "neg_dist"), (7, "neg_cosine"), (8, "neg_dot")):
         ret[f"{name}_attacked_{suffix}"] = means[j]
     ret[f"q_{suffix}_attack"] = pv.q.clone()
-    value = _scalar(pv.loss_sum.clone())
-    if not need_grad:
-        return value
-    dq_saved = pv.dq.clone()
-
-    def backward(grad_out, pv=pv, dq_saved=dq_saved, op=op):
-        dq = dq_saved * grad_out.to(dq_saved.dtype)
-        eng.heads_backward(pv, dq, None, with_grads=True)
-        eng.encoder_backward(pv, L.MODE_FULL, op, pv.dcls, cls_only=True, dpatches=None)
-        # one attacked view = one backward per step: its gradient all-reduces can start layer by layer right away
-        # reduced over ranks once per step, after the step's last closure; a single closure (the image-view step) gets
-        # per-layer all-reduces that start while the layers below are still in their backward
-        pl_module.after_backward(overlap=True)
-
-    return _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+    pl_module.log("moco_loss/clean_loss" if suffix == "clean" else f"moco_loss/attacked_{suffix}_loss", value.detach())
+    return value
 
 
 def compute_itm_wpa(pl_module, batch):
@@ -328,10 +330,8 @@ def compute_moco_contrastive(pl_module, batch):
         # every step but never turns them into a loss (quirk 3).
         pc = eng.bind_text(pb, pb.text_ids, pb.text_mask, tag="moco_clean")
         op_c = eng.make_operand(pb, out=pc.patchesT_full)
-        loss_c = _attacked_view(pl_module, pc, op_c, k, "clean", None, None, ret, phase, before_loss=join_key_stream)
+        loss = loss + _attacked_view(pl_module, pc, op_c, k, "clean", None, None, ret, phase, before_loss=join_key_stream)
         clean = {"prediction": pc.rows[:, 1].clone(), "q": pc.q.clone()}
-        pl_module.log("moco_loss/clean_loss", loss_c.detach())
-        loss = loss + loss_c
         loss_num += 1
     elif not fuse_clean and use_lanes and k_ready is not None:
         # clean query (:267-275) behind the key forward on the key stream, in buffers of its own (the lanes' passes use pb's)
@@ -339,18 +339,12 @@ def compute_moco_contrastive(pl_module, batch):
         pc.text_ids, pc.text_mask, pc.k = pb.text_ids, pb.text_mask, pb.k
         clean = {"prediction": torch.empty(B, dtype=torch.float32, device=eng.device), "q": torch.empty_like(pb.q)}
         with torch.cuda.stream(key_stream):
-            eng.encoder_forward(pc, key=False, mode=L.MODE_INFER, patchesT=op, cls_tail=True)
-            eng.heads_forward(pc, key=False, wgrad=False)
-            eng.infonce(pc, 0.0, want_dq=False, metrics=False)
+            InfoNceLoss(pl_module, metrics=False).forward(pc, op, L.MODE_INFER, want_grad=False, scale=0.0, wgrad=False)
             clean["prediction"].copy_(pc.rows[:, 1])
             clean["q"].copy_(pc.q)
         clean_on_key = True
     elif not fuse_clean:
-        eng.encoder_forward(pb, key=False, mode=L.MODE_INFER, patchesT=op, cls_tail=True)     # clean query
-        eng.heads_forward(pb, key=False)
-        join_key_stream()
-        eng.infonce(pb, 0.0, want_dq=False, metrics=False)
-        clean = {"prediction": pb.rows[:, 1].clone(), "q": pb.q.clone()}
+        InfoNceLoss(pl_module, metrics=False).forward(pb, op, L.MODE_INFER, want_grad=False, scale=0.0, before_loss=join_key_stream, clean_out=clean)   # clean query
     prediction_original = clean.get("prediction")
 
     txt_ids = txt_masks = None
@@ -359,9 +353,7 @@ def compute_moco_contrastive(pl_module, batch):
         txt_ids, txt_masks = aug["text_ids"], aug["text_masks"]
         pt = eng.bind_text(pb, txt_ids, txt_masks, tag="moco_txt")
         op_t = eng.make_operand(pb, out=pt.patchesT_full)                   # clean image, attacked text
-        loss_t = _attacked_view(pl_module, pt, op_t, k, "txt", "Geom_success_rate", prediction_original, ret, phase)
-        pl_module.log("moco_loss/attacked_txt_loss", loss_t.detach())
-        loss = loss + loss_t
+        loss = loss + _attacked_view(pl_module, pt, op_t, k, "txt", "Geom_success_rate", prediction_original, ret, phase)
         loss_num += 1
     if pl_module.image_view:                                                # :319-354
         if key_lanes is not None:
@@ -378,26 +370,18 @@ def compute_moco_contrastive(pl_module, batch):
             main.wait_stream(key_stream)                    # the clean query's prediction / q (key stream) are read from here on
         else:
             pl_module.pgd_attacker.attack_patches(pl_module, pb, k, clean_op=op)        # compute_pgd (:319-323)
-        check(lib.rmcl_delta_channel_norm(P(pb.delta), P(eng.zero_scalar(pb)), I64(pb.delta.shape[0]), 3,
-                                          pb.d.patch_k // 3, stream_ptr()), "delta_norm")
-        # mean over ALL pixels of the (padded) batch image like torch.linalg.norm(delta, dim=1).mean() (:184); the pad pixels of
-        # a zero-padded batch carry delta = 0 and are not stored in the patch layout
-        n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
-        pl_module.log(f"moco_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
+        _log_delta(pl_module, pb, "moco", phase)
         # attacked view = img + delta_{K-1} + delta_K  (pgd_attack_vilt.py:144 + objectives.py:176): written by the last PGD update
         op_att = pb.patchesT_full
         loss_i = _attacked_view(pl_module, pb, op_att, k, "img", "PGD_success_rate", prediction_original, ret, phase)
         ret["logit_pos_img_attack"] = pb.rows[:, 2].clone()
         ret["lse_img_attack"] = pb.rows[:, 9].clone()
-        pl_module.log("moco_loss/attacked_img_loss", loss_i.detach())
         loss = loss + loss_i
         loss_num += 1
     if pl_module.image_view and pl_module.text_view:                        # :356-392 attacked image AND attacked text
         pbo = eng.bind_text(pb, txt_ids, txt_masks, tag="moco_both")
         op_b = pbo.patchesT_full.copy_(pb.patchesT_full)                    # the same attacked image (own buffer: read again by the backward)
-        loss_b = _attacked_view(pl_module, pbo, op_b, k, "both", "Both_success_rate", prediction_original, ret, phase)
-        pl_module.log("moco_loss/attacked_both_loss", loss_b.detach())
-        loss = loss + loss_b
+        loss = loss + _attacked_view(pl_module, pbo, op_b, k, "both", "Both_success_rate", prediction_original, ret, phase)
         loss_num += 1
 
     if pl_module.training:                                                  # _dequeue_and_enqueue (:394-395)
@@ -423,45 +407,31 @@ def compute_moco_contrastive(pl_module, batch):
     return ret
 
 
-def _bt_view(pl_module, pv, op, zk, suffix, ret, phase, need_grad, training):
+def _bt_view(pl_module, pv, op, zk, suffix, name, ret, views, need_grad, training):
     """One Barlow-Twins loss view (objectives.py:464-498 text / :500-525 image / :527-546 both): forward of the view, the
     head (running estimates updated in training), c = q^T k / per_step_bs summed over ranks, on/off-diagonal loss, distance
-    logs; returns (loss value with a deferred HIP backward, on_diag, adv_lr * off_diag)."""
-    eng = pl_module.engine
-    eng.encoder_forward(pv, key=False, mode=L.MODE_FULL if need_grad else L.MODE_INFER, patchesT=op, cls_tail=True)
-    eng.heads_forward(pv, key=False, want_q=False)
-    bq = eng.bt_bufs(pv.B, "q_" + suffix)
-    eng.bt_forward(bq, pv.cls, training, track=training)
-
+    logs; returns the loss value with a deferred HIP backward; on_diag and adv_lr * off_diag go into `ret` under `name`."""
     def reduce_c(c):                                                            # torch.distributed.all_reduce(c) (:480,:507,:535)
         if dist_utils.world_size() > 1:
             torch.distributed.all_reduce(c)
 
-    loss2 = eng.bt_loss(bq, zk, float(pl_module.per_step_bs), pl_module.adv_lr, 1.0, want_dz=need_grad, reduce_c=reduce_c)
-    on_diag, red = loss2[0].clone(), pl_module.adv_lr * loss2[1]
-    rows = eng.bt_pair_metrics(bq, zk)
+    # NOTE on ranks: the reference all-reduces c WITHOUT autograd support, so each rank backpropagates d loss(c_global) / dq
+    # of its own rows and DDP then AVERAGES the gradients - the 1/world_size of that average is the prescale
+    loss = BarlowLoss(pl_module, "q_" + suffix, zk, track=training, denom=pl_module.per_step_bs, reduce_c=reduce_c)
+    value = _loss_view(pl_module, loss, pv, op)
+    on_diag, red = loss.on_diag, loss.red
+    rows = pl_module.engine.bt_pair_metrics(loss.bb, zk)
     ret[f"pos_dist_attacked_{suffix}"], ret[f"pos_cosine_attacked_{suffix}"], ret[f"pos_dot_attacked_{suffix}"] = \
         rows[:, 0].mean(), rows[:, 1].mean(), rows[:, 2].mean()
-    ret[f"q_{suffix}"] = bq.z.clone()
-    value = _scalar(on_diag + red)
+    ret[f"q_{suffix}"] = loss.bb.z.clone()
     if need_grad:
-        dz_saved = bq.dz.clone()
-
-        def backward(grad_out, pv=pv, bq=bq, dz_saved=dz_saved, op=op):
-            dz = dz_saved * grad_out.to(dz_saved.dtype)
-            dcls = eng.bt_backward(bq, dz, training=True, with_grads=True)
-            eng.heads_backward(pv, None, dcls, with_grads=True)
-            eng.encoder_backward(pv, L.MODE_FULL, op, pv.dcls, cls_only=True, dpatches=None)
-            pl_module.after_backward(overlap=True)
-
-        # NOTE on ranks: the reference all-reduces c WITHOUT autograd support, so each rank backpropagates d loss(c_global) / dq
-        # of its own rows and DDP then AVERAGES the gradients - the 1/world_size of that average is the prescale
-        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
         # Reference behaviour: training_step sums every returned value whose key contains "loss" (vilt_module.py:475), and the
         # logged components ARE live graph tensors there (:486-487) - each view is optimised with weight 1/loss_num + 1.  The
         # invariance component therefore carries the same deferred backward (as a zero-valued term).
         on_diag = on_diag + (value - value.detach())
-    return value, on_diag, red
+    ret[f"barlowtwins_loss_invariance_{name}"], ret[f"barlowtwins_loss_redundancy_{name}"] = on_diag, red
+    views.append((suffix, name))
+    return value
 
 
 def compute_barlowtwins_contrastive(pl_module, batch):
@@ -482,10 +452,10 @@ def compute_barlowtwins_contrastive(pl_module, batch):
     pb = eng.bind_batch(batch["text_ids"], batch["text_masks"], batch["image"][0], tag="bt")
     B = pb.B
     op = eng.make_operand(pb)
-    bk = eng.bt_bufs(B, "k")
+    key = BarlowLoss(pl_module, "k", track=training)
     eng.encoder_forward(pb, key=False, mode=L.MODE_INFER, patchesT=op, cls_tail=True)          # :460-462
-    eng.heads_forward(pb, key=False, want_q=False)
-    zk = eng.bt_forward(bk, pb.cls, training, track=training)
+    key.pool(pb, True)
+    zk = key.project(pb, pb.cls)
     loss, loss_num = 0, 0
     views = []
     txt_ids = txt_masks = None
@@ -494,28 +464,16 @@ def compute_barlowtwins_contrastive(pl_module, batch):
         txt_ids, txt_masks = aug["text_ids"], aug["text_masks"]
         pt = eng.bind_text(pb, txt_ids, txt_masks, tag="bt_txt")
         op_t = eng.make_operand(pb, out=pt.patchesT_full)
-        v, on_diag, red = _bt_view(pl_module, pt, op_t, zk, "txt", ret, phase, need_grad, training)
-        ret["barlowtwins_loss_invariance_text"], ret["barlowtwins_loss_redundancy_text"] = on_diag, red
-        loss, loss_num = loss + v, loss_num + 1
-        views.append(("txt", "text"))
+        loss, loss_num = loss + _bt_view(pl_module, pt, op_t, zk, "txt", "text", ret, views, need_grad, training), loss_num + 1
     if pl_module.image_view:                                                    # :500-525
         pl_module.pgd_attacker.attack_patches(pl_module, pb, zk, clean_op=op)   # compute_pgd (:503)
-        check(lib.rmcl_delta_channel_norm(P(pb.delta), P(eng.zero_scalar(pb)), I64(pb.delta.shape[0]), 3, pb.d.patch_k // 3,
-                                          stream_ptr()), "delta_norm")
-        n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
-        pl_module.log(f"barlowtwins_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
+        _log_delta(pl_module, pb, "barlowtwins", phase)
         op_att = pb.patchesT_full                                               # written by the last PGD update
-        v, on_diag, red = _bt_view(pl_module, pb, op_att, zk, "img", ret, phase, need_grad, training)
-        ret["barlowtwins_loss_invariance_img"], ret["barlowtwins_loss_redundancy_img"] = on_diag, red
-        loss, loss_num = loss + v, loss_num + 1
-        views.append(("img", "img"))
+        loss, loss_num = loss + _bt_view(pl_module, pb, op_att, zk, "img", "img", ret, views, need_grad, training), loss_num + 1
     if pl_module.image_view and pl_module.text_view:                            # :527-546
         pbo = eng.bind_text(pb, txt_ids, txt_masks, tag="bt_both")
         op_b = pbo.patchesT_full.copy_(pb.patchesT_full)
-        v, on_diag, red = _bt_view(pl_module, pbo, op_b, zk, "both", ret, phase, need_grad, training)
-        ret["barlowtwins_loss_invariance_both"], ret["barlowtwins_loss_redundancy_both"] = on_diag, red
-        loss, loss_num = loss + v, loss_num + 1
-        views.append(("both", "both"))
+        loss, loss_num = loss + _bt_view(pl_module, pbo, op_b, zk, "both", "both", ret, views, need_grad, training), loss_num + 1
     ret["k"] = zk.clone()
     ret["barlowtwins_loss"] = loss / loss_num                                   # :548
     pl_module.log(f"barlowtwins/{phase}/loss", ret["barlowtwins_loss"].detach())
@@ -533,27 +491,12 @@ def _vqa_head_loss(pl_module, pb, op, batch, task, vb_tag, tables=None):
     reference's dict with a ``vqa_loss`` whose backward runs BCE gradient -> head -> pooler -> encoder (MODE_FULL) into the
     gradient arena.  ``tables``: VqaBuffers whose label / score tables this batch already sent (the PGD loop's)."""
     eng = pl_module.engine
-    need_grad = torch.is_grad_enabled() and pl_module.training
-    eng.encoder_forward(pb, key=False, mode=L.MODE_FULL if need_grad else L.MODE_INFER, patchesT=op, cls_tail=True)
-    eng.heads_forward(pb, key=False, want_q=False, wgrad=need_grad)
     vb = eng.vqa_bufs(pb.B, vb_tag)
-    if tables is None:
-        eng.vqa_targets(vb, batch["vqa_labels"], batch["vqa_scores"])
-    else:
-        vb.labels, vb.scores, vb.A = tables.labels, tables.scores, tables.A
-    logits = eng.vqa_forward(vb, pb.cls)
-    loss2 = eng.vqa_bce(vb, 1.0, want_dz=False, loss2=torch.empty(2, dtype=torch.float32, device=eng.device))
-    value = _scalar(loss2[0])
-    if need_grad:
-        def backward(grad_out, pb=pb, vb=vb, op=op):
-            g = grad_out.to(torch.float32).reshape(1).contiguous()
-            eng.vqa_bce(vb, 1.0, want_dz=True, scale_dev=g, loss2=torch.empty(2, dtype=torch.float32, device=eng.device))
-            dcls = eng.vqa_backward(vb, vb.dz, with_grads=True)
-            eng.heads_backward(pb, None, dcls, with_grads=True)
-            eng.encoder_backward(pb, L.MODE_FULL, op, pb.dcls, cls_only=True, dpatches=None)
-            pl_module.after_backward(overlap=True)
 
-        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+    bind = (lambda: eng.vqa_targets(vb, batch["vqa_labels"], batch["vqa_scores"])) if tables is None else \
+        (lambda: vars(vb).update(labels=tables.labels, scores=tables.scores, A=tables.A))
+    loss = VqaLoss(pl_module, vb)
+    value, logits, loss2 = _loss_view(pl_module, loss, pb, op, before_loss=bind), loss.logits, loss.stats
     ret = {
         "vqa_loss": value,
         "vqa_logits": logits,
@@ -588,10 +531,7 @@ def compute_vqa_attack(pl_module, batch):
     if pl_module.image_view:
         op = eng.make_operand(pb)                                             # img + delta_0, delta_0 = 0
         pl_module.pgd_attacker.attack_patches(pl_module, pb, vp, clean_op=op)    # compute_pgd (:816)
-        check(lib.rmcl_delta_channel_norm(P(pb.delta), P(eng.zero_scalar(pb)), I64(pb.delta.shape[0]), 3, pb.d.patch_k // 3,
-                                          stream_ptr()), "delta_norm")
-        n_pix = pb.delta.numel() // 3 if pb.geom is None else pb.B * pb.geom.shape[2] * pb.geom.shape[3]
-        pl_module.log(f"vqa_attacked_attack/{phase}/delta", _scalar(pb.loss_sum / float(n_pix)))
+        _log_delta(pl_module, pb, "vqa_attacked", phase)
         op = pb.patchesT_full
     else:
         op = eng.make_operand(pb, out=pb.patchesT_full)                       # the clean image, built once
@@ -603,86 +543,14 @@ def compute_vqa_attack(pl_module, batch):
 
 
 # ---- NLVR2 (objectives.py:898-1060) ------------------------------------------------------------------------------------------------
-class Nlvr2Pass:
-    """The encoder passes of one NLVR2 batch.  Pair form (config["nlvr2_pair_pass"], default on): ONE pass of 2B sequences, sample 2b =
-    (text b, image_0[b], token type 1), 2b + 1 = (text b, image_1[b], token type 2) - its pooled cls [2B, D] IS the [B, 2D] input of
-    nlvr2_classifier and the head's [B, 2D] gradient IS the pass's cls gradient.  Two-pass form: the reference's two infer calls
-    (image_token_type_idx 1 and 2), one pass of B sequences each, the cls halves concatenated / split by copies."""
-
-    def __init__(self, eng, views, B, pair):
-        self.eng, self.views, self.B, self.pair = eng, views, B, pair
-        self.ops = [None] * len(views)
-
-    @classmethod
-    def bind(cls, pl_module, batch, tag):
-        eng = pl_module.engine
-        img0, img1 = batch["image_0"][0], batch["image_1"][0]
-        B = int(img0.shape[0])
-        if pl_module.hparams.config.get("nlvr2_pair_pass", True):
-            return cls(eng, [eng.bind_pair(batch["text_ids"], batch["text_masks"], img0, img1, tag=tag)], B, True)
-        views = []
-        for t, img in ((1, img0), (2, img1)):                  # geometry drawn in the reference's order: image_0, then image_1
-            pv = eng.bind_batch(batch["text_ids"], batch["text_masks"], img, tag=f"{tag}_{t}")
-            pv.d.img_type = t
-            views.append(pv)
-        return cls(eng, views, B, False)
-
-    def twin(self, tag):
-        """the same pairs in buffers of their own (the attacked pass): shares the text, the clean patch rows and the geometry"""
-        vs = []
-        for i, pv in enumerate(self.views):
-            pt = self.eng.twin(pv, f"{tag}_{i}")
-            pt.text_ids, pt.text_mask, pt.patches32 = pv.text_ids, pv.text_mask, pv.patches32
-            vs.append(pt)
-        return Nlvr2Pass(self.eng, vs, self.B, self.pair)
-
-    def clean_operands(self, full_buffer=True):
-        self.ops = [self.eng.make_operand(pv, out=pv.patchesT_full if full_buffer else None) for pv in self.views]
-        return self.ops
-
-    def forward(self, mode, wgrad):
-        eng = self.eng
-        for pv, op in zip(self.views, self.ops):
-            eng.encoder_forward(pv, key=False, mode=mode, patchesT=op, cls_tail=True)
-            eng.heads_forward(pv, key=False, want_q=False, wgrad=wgrad)
-        if self.pair:
-            return self.views[0].cls.view(self.B, -1)                         # [2B, D] -> [B, 2D]: no copy
-        return torch.cat([pv.cls for pv in self.views], dim=1)
-
-    def backward(self, dcls2, mode, with_grads, dpatches=False):
-        eng = self.eng
-        D = self.views[0].d.D
-        for i, (pv, op) in enumerate(zip(self.views, self.ops)):
-            dc = dcls2.view(2 * self.B, D) if self.pair else dcls2[:, i * D:(i + 1) * D].contiguous()
-            eng.heads_backward(pv, None, dc, with_grads=with_grads)
-            want = dpatches if isinstance(dpatches, bool) else dpatches[i]
-            eng.encoder_backward(pv, mode, op, pv.dcls, cls_only=True, dpatches=pv.gpatch if want else None)
-
-
 def _nlvr2_loss(pl_module, npass, batch, nb_tag, labels_from=None, ref=None):
-    """Forward of the pass on its operands, nlvr2_classifier and the CE: (value with a deferred backward, logits, Nlvr2Buffers)."""
+    """Forward of the pass on its operands, nlvr2_classifier and the CE: (value with a deferred backward, logits, Nlvr2Buffers, stats)."""
     eng = pl_module.engine
-    need_grad = torch.is_grad_enabled() and pl_module.training
-    mode = L.MODE_FULL if need_grad else L.MODE_INFER
-    cls2 = npass.forward(mode, wgrad=need_grad)
     nb = eng.nlvr2_bufs(npass.B, nb_tag)
-    if labels_from is None:
-        eng.nlvr2_labels(nb, batch["answers"])
-    else:
-        nb.labels.copy_(labels_from.labels)
-    logits = eng.nlvr2_forward(nb, cls2)
-    stats = eng.nlvr2_ce(nb, 1.0, want_dz=False, ref=ref, stats=torch.empty(3, dtype=torch.float32, device=eng.device))
-    value = _scalar(stats[0])
-    if need_grad:
-        def backward(grad_out, npass=npass, nb=nb):
-            g = grad_out.to(torch.float32).reshape(1).contiguous()
-            eng.nlvr2_ce(nb, 1.0, want_dz=True, scale_dev=g, stats=torch.empty(3, dtype=torch.float32, device=eng.device))
-            dcls2 = eng.nlvr2_backward(nb, nb.dz, with_grads=True)
-            npass.backward(dcls2, L.MODE_FULL, with_grads=True)
-            pl_module.after_backward(overlap=True)
-
-        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
-    return value, logits, nb, stats
+    loss = Nlvr2Loss(pl_module, nb, ref)
+    bind = (lambda: eng.nlvr2_labels(nb, batch["answers"])) if labels_from is None else (lambda: nb.labels.copy_(labels_from.labels))
+    value = _loss_view(pl_module, loss, npass, None, before_loss=bind)
+    return value, loss.logits, nb, loss.stats
 
 
 def _split_rows(batch):
@@ -744,11 +612,7 @@ def compute_nlvr2_attack(pl_module, batch):
         apass.clean_operands()
     if pl_module.text_view:
         aug = compute_geometric(pl_module, copy(batch), "nlvr2_attacked")     # (:927) on the clean pair
-        ids = aug["text_ids"].to(eng.device, torch.int64)
-        masks = aug["text_masks"].to(eng.device, torch.int64)
-        for pv in apass.views:
-            pv.text_ids = (ids.repeat_interleave(2, dim=0) if apass.pair else ids).contiguous()
-            pv.text_mask = (masks.repeat_interleave(2, dim=0) if apass.pair else masks).contiguous()
+        apass.set_text(aug["text_ids"].to(eng.device, torch.int64), aug["text_masks"].to(eng.device, torch.int64))
     v_att, lg_att, nb_a, st_a = _nlvr2_loss(pl_module, apass, batch, "att", labels_from=nb_c, ref=nb_c)
     ret["nlvr2_attacked_logits"] = lg_att
     ret["nlvr2_attacked_loss"] = v_att
