@@ -536,9 +536,12 @@ int rmcl_layernorm_fwd(const float* x, const float* w, const float* b, float eps
 int rmcl_layernorm_bwd(const void* dy, int dt_dy, const float* x, const float* mean, const float* rstd, const float* w,
                        const float* b, float* dx, int add, float* dgamma, float* dbeta, int M, int D, int relu, void* stream);
 /* Masked multi-head self-attention on a packed qkv [B*N, 3*H*64] (Attention.forward,
- * vision_transformer.py:309-332).  out [B*N, H*64]; probs (stash) and scores (scratch) sized by
- * rmcl_attention_scratch_elems.  With dtype bf16 and exact=0 the fused flash-style kernels run and
- * `probs` holds only the per-row log-sum-exp.                                                                  */
+ * vision_transformer.py:309-332), 1 <= N <= 512 (checked before anything is written).  out [B*N, H*64]; probs (stash), scores
+ * and dscores (scratch) hold rmcl_attention_scratch_elems(B, H, N) ELEMENTS of their type each (probs, dscores: dtype; scores: fp32):
+ * max(B*H*N*ldp, 2*B*H*NKP) with ldp = N rounded up to 8 and NKP = 64 / 128 / 192 / 256 for N <= 64 / 128 / 192 / 256.  With dtype
+ * bf16, exact=0 and N <= 256 the fused flash-style kernels run: `probs` then holds only the per-row log-sum-exp, fp32 [B, H, NKP],
+ * and the two-kernel backward keeps its delta, as many floats, in `scores` - the second term of the size, which is the larger one for
+ * N <= 8.  Every other case materialises the [B, H, N, ldp] scores and probabilities (batched GEMM + softmax kernels).            */
 int64_t rmcl_attention_scratch_elems(int B, int H, int N);
 int rmcl_attention_fwd(const void* qkv, const int32_t* mask, void* out, void* probs, float* scores, int B, int N, int H,
                        int dtype, int exact, void* stream);

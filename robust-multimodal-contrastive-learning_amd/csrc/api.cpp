@@ -490,7 +490,7 @@ int rmcl_layernorm_bwd(const void* dy, int dt_dy, const float* x, const float* m
                        const float* b, float* dx, int add, float* dgamma, float* dbeta, int M, int D, int relu, void* stream) {
   return rmcl_ln_bwd(dy, D, dt_dy, x, D, mean, rstd, w, b, dx, D, add, dgamma, dbeta, M, D, relu, (hipStream_t)stream);
 }
-int64_t rmcl_attention_scratch_elems(int B, int H, int N) { return (int64_t)B * H * N * ((N + 7) / 8 * 8); }
+int64_t rmcl_attention_scratch_elems(int B, int H, int N) { return (int64_t)rmcl_attn_scratch_elems(B, H, N); }
 int rmcl_attention_fwd(const void* qkv, const int32_t* mask, void* out, void* probs, float* scores, int B, int N, int H, int dtype,
                        int exact, void* stream) {
   RMCL_REQUIRE(qkv && mask && out && probs && scores, "attention_fwd: NULL argument");

@@ -70,7 +70,7 @@ size_t carve_stash(const rmcl_dims& d, int mode, void* base, Stash* st) {
     ls.mean1 = b.take<float>(M); ls.rstd1 = b.take<float>(M);
     ls.mean2 = b.take<float>(M); ls.rstd2 = b.take<float>(M);
     ls.qkv = b.take_bytes(M * 3 * D * e);
-    ls.probs = b.take_bytes((size_t)d.B * d.H * N * ldp_of((int)N) * e);
+    ls.probs = b.take_bytes((size_t)rmcl_attn_scratch_elems(d.B, d.H, (int)N) * e);
     ls.u = b.take_bytes(M * d.mlp * e);
     ls.ao = b.take_bytes(M * D * e);
     if (mode == RMCL_MODE_FULL) {
@@ -97,7 +97,7 @@ size_t carve_work(const rmcl_dims& d, void* base, Work* w) {
   Bump b(base);
   const size_t M = (size_t)d.B * (d.L + 1 + d.P), D = d.D, N = d.L + 1 + d.P;
   const size_t e = esz(d.dtype);
-  const size_t zn = (size_t)d.B * d.H * N * ldp_of((int)N);
+  const size_t zn = (size_t)rmcl_attn_scratch_elems(d.B, d.H, (int)N);
   Work k{};
   k.scores = b.take<float>(zn);
   k.pe = b.take<float>((size_t)d.B * d.P * D);
@@ -257,6 +257,7 @@ extern "C" int rmcl_grad_ready_wait(int layer, void* stream) {
 
 int rmcl_attention_fwd_impl(const void* qkv, const int* mask, void* out, void* probs, float* scores, int B, int N, int H, int dt,
                             int exact, hipStream_t s) {
+  RMCL_REQUIRE(N >= 1 && N <= 512, "attention: N must be in 1..512");   // (before the score GEMM writes into the caller's buffers)
   // bf16 fast path: fused kernel; `probs` then holds only the per-row log-sum-exp (fp32 [B,H,NKP])
   if (dt == RMCL_BF16 && !exact && N <= 256) return rmcl_attn_fused_fwd(qkv, mask, out, (float*)probs, B, N, H, s);
   const int D = H * 64, ldp = ldp_of(N);
@@ -280,6 +281,7 @@ int rmcl_attention_fwd_impl(const void* qkv, const int* mask, void* out, void* p
 
 int rmcl_attention_bwd_impl(const void* qkv, const int* mask, const void* probs, const void* dout, const void* out, void* dqkv,
                             float* scores, void* dS, int B, int N, int H, int dt, int exact, hipStream_t s) {
+  RMCL_REQUIRE(N >= 1 && N <= 512, "attention: N must be in 1..512");
   // bf16 fast path: probs = saved log-sum-exp, scores = scratch for delta (both fp32 [B,H,NKP]); with the forward's output
   // `out` (stashed in DATA and FULL mode) ONE kernel produces dQ, dK and dV
   if (dt == RMCL_BF16 && !exact && N <= 256)

@@ -68,6 +68,15 @@ int rmcl_launch_gemm_chain(const ChainArgs& a, hipStream_t s);
 int rmcl_softmax_fwd(const float* S, long lds, const int* mask, void* P, long ldp, int dt, int Z, int N, int H, hipStream_t s);
 int rmcl_softmax_bwd(const void* P, long ldp, const float* dP, long lddp, void* dS, long ldds, int dt, int Z, int N,
                      float scale, hipStream_t s);
+// fp32 per-row statistics of the fused attention kernels: B * H * NKP floats (NKP = the key-tile count of N times 16)
+long rmcl_attn_stat_elems(int B, int H, int N);
+// Elements of each attention scratch / stash buffer (probs, scores, dS): the [B,H,N,ldp] matrices of the unfused path, and never
+// less than 2 * B * H * NKP, so that a bf16 `probs` of that many elements holds the fused forward's fp32 log-sum-exp and a fp32
+// `scores` the two-kernel backward's delta (N * ldp < 2 * NKP only for N <= 8).  The C ABI and the engine's arenas both size by it.
+inline long rmcl_attn_scratch_elems(int B, int H, int N) {
+  const long mat = (long)B * H * N * ((N + 7) / 8 * 8), stat = 2 * rmcl_attn_stat_elems(B, H, N);
+  return mat > stat ? mat : stat;
+}
 int rmcl_attn_fused_fwd(const void* qkv, const int* mask, void* out, float* lse, int B, int N, int H, hipStream_t s);
 int rmcl_attn_fused_bwd(const void* qkv, const int* mask, const void* dout, const void* out, const float* lse, float* delta, void* dqkv,
                         int B, int N, int H, hipStream_t s);
