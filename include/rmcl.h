@@ -37,6 +37,13 @@ extern "C" {
  * Requires dropout off and B <= 1024.  Results equal the dense pass on the cls rows up to fp32 summation order (the tail
  * uses the fp32 master weights).                                                                                     */
 #define RMCL_MODE_CLS_TAIL 16
+/* OR-ed into the mode of rmcl_encoder_forward, rmcl_encoder_forward_rank and rmcl_encoder_backward (and accepted by rmcl_stash_bytes):
+ * with dtype bf16, exact = 0 and N = L + 1 + P > 256 every layer's attention runs the streaming kernels (rmcl_attention_stream_fwd / _bwd
+ * below) instead of the unfused score / probability matrices; the layer's `probs` stash then holds the log-sum-exp.  In every other
+ * case (fp32, exact, N <= 256) the bit changes nothing.  A forward and the backward that reads its stash must agree on the bit: the
+ * library remembers (host side, by address) what the last forward left in each of the 64 most recent stashes, and a backward whose
+ * setting differs from it returns -1.                                                                                         */
+#define RMCL_MODE_STREAM_ATTN 32
 
 typedef struct rmcl_dims {
   int B;        /* samples in this pass                                              */
@@ -549,6 +556,18 @@ int rmcl_attention_fwd(const void* qkv, const int32_t* mask, void* out, void* pr
  * (delta = rowsum(dO * O)); NULL selects the two-kernel form that recomputes delta from P and dP.                 */
 int rmcl_attention_bwd(const void* qkv, const int32_t* mask, const void* probs, const void* dout, const void* out, void* dqkv,
                        float* scores, void* dscores, int B, int N, int H, int dtype, int exact, void* stream);
+/* The same attention for bf16 storage at every 1 <= N <= 512 WITHOUT the [B, H, N, ldp] matrices: keys and values (backward: queries and
+ * dO too) stream through LDS in blocks of 64 rows, online softmax in fp32 (csrc/attention_stream.hip).  Arguments as above without
+ * dtype / exact; the buffers keep the sizes above.  The forward writes `out` and the per-row log-sum-exp, fp32 [B, H, NKP], into `probs`
+ * (NKP = N rounded up to 64; rmcl_attention_stream_stat_elems = B * H * NKP floats, which rmcl_attention_scratch_elems bf16 elements always
+ * hold); `scores` is not touched.  The backward recomputes P from that log-sum-exp, takes delta = rowsum(dO * O) from `out` (required),
+ * keeps it in `scores` (as many floats) and writes dqkv; `dscores` is not touched.  dK / dV rows of masked keys are exactly zero, no
+ * float atomics, identical bits run to run.  N outside 1..512 or a NULL argument returns -1 before anything is written.
+ * rmcl_encoder_forward / _backward route their attention here when RMCL_MODE_STREAM_ATTN is set (above).                          */
+int64_t rmcl_attention_stream_stat_elems(int B, int H, int N);
+int rmcl_attention_stream_fwd(const void* qkv, const int32_t* mask, void* out, void* probs, float* scores, int B, int N, int H, void* stream);
+int rmcl_attention_stream_bwd(const void* qkv, const int32_t* mask, const void* probs, const void* dout, const void* out, void* dqkv,
+                              float* scores, void* dscores, int B, int N, int H, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("RMCL_LIB") or os.path.join(_HERE, "lib", "librmcl_hip
 F32, BF16 = 0, 1
 MODE_INFER, MODE_DATA, MODE_FULL = 0, 1, 2
 MODE_CLS_TAIL = 16        # include/rmcl.h RMCL_MODE_CLS_TAIL
+MODE_STREAM_ATTN = 32     # include/rmcl.h RMCL_MODE_STREAM_ATTN
 PGD_DELTA_ZERO, PGD_SUM_PREV = 1, 2   # include/rmcl.h RMCL_PGD_*
 HEADS_NO_WGRAD = 1                    # include/rmcl.h RMCL_HEADS_NO_WGRAD
 EPI_BIAS, EPI_GELU, EPI_SAVE_PREACT, EPI_RESIDUAL, EPI_DGELU, EPI_ATOMIC, EPI_ACCUM, EPI_TANH = 1, 2, 4, 8, 16, 32, 64, 128
@@ -82,7 +83,7 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     lib.rmcl_last_error.restype = C.c_char_p
     for name in ("rmcl_stash_bytes", "rmcl_workspace_bytes", "rmcl_heads_stash_bytes", "rmcl_infonce_ws_bytes",
-                 "rmcl_attention_scratch_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats",
+                 "rmcl_attention_scratch_elems", "rmcl_attention_stream_stat_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats",
                  "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats"):
         getattr(lib, name).restype = C.c_int64
     return lib
@@ -98,7 +99,7 @@ EXPORTS = (
     "rmcl_delta_channel_norm", "rmcl_ema_f32", "rmcl_enqueue_f32", "rmcl_cast_f32", "rmcl_adamw_f32", "rmcl_ipot_f32", "rmcl_gemm_batched", "rmcl_l2norm_rows_fwd", "rmcl_l2norm_rows_bwd",
     "rmcl_wpa_cost_finish", "rmcl_wpa_distance", "rmcl_itm_fwd", "rmcl_itm_bwd",
     "rmcl_gemm", "rmcl_gemm_chain", "rmcl_l2_prefetch_experiment", "rmcl_gemm_route", "rmcl_gemm_kblk", "rmcl_layernorm_fwd", "rmcl_layernorm_bwd", "rmcl_attention_scratch_elems", "rmcl_attention_fwd",
-    "rmcl_attention_bwd",
+    "rmcl_attention_bwd", "rmcl_attention_stream_stat_elems", "rmcl_attention_stream_fwd", "rmcl_attention_stream_bwd",
     "rmcl_bt_stash_floats", "rmcl_bt_head_forward", "rmcl_bt_head_backward", "rmcl_bt_corr", "rmcl_bt_loss_ws_floats", "rmcl_bt_loss",
     "rmcl_bt_dz", "rmcl_bt_pair_metrics",
     "rmcl_vqa_stash_floats", "rmcl_vqa_head_forward", "rmcl_vqa_bce", "rmcl_vqa_targets_dense", "rmcl_vqa_head_backward",

@@ -501,6 +501,18 @@ int rmcl_attention_bwd(const void* qkv, const int32_t* mask, const void* probs, 
   RMCL_REQUIRE(qkv && mask && probs && dout && dqkv && scores && dscores, "attention_bwd: NULL argument");
   return rmcl_attention_bwd_impl(qkv, mask, probs, dout, out, dqkv, scores, dscores, B, N, H, dtype, exact, (hipStream_t)stream);
 }
+int64_t rmcl_attention_stream_stat_elems(int B, int H, int N) { return (int64_t)rmcl_attn_stream_stat_elems(B, H, N); }
+int rmcl_attention_stream_fwd(const void* qkv, const int32_t* mask, void* out, void* probs, float* scores, int B, int N, int H, void* stream) {
+  RMCL_REQUIRE(qkv && mask && out && probs && scores, "attention_stream_fwd: NULL argument");
+  RMCL_REQUIRE(B >= 1 && H >= 1 && N >= 1 && N <= 512, "attention_stream_fwd: N must be in 1..512 (B, H >= 1)");
+  return rmcl_attn_stream_fwd(qkv, mask, out, (float*)probs, B, N, H, (hipStream_t)stream);
+}
+int rmcl_attention_stream_bwd(const void* qkv, const int32_t* mask, const void* probs, const void* dout, const void* out, void* dqkv,
+                              float* scores, void* dscores, int B, int N, int H, void* stream) {
+  RMCL_REQUIRE(qkv && mask && probs && dout && out && dqkv && scores && dscores, "attention_stream_bwd: NULL argument");
+  RMCL_REQUIRE(B >= 1 && H >= 1 && N >= 1 && N <= 512, "attention_stream_bwd: N must be in 1..512 (B, H >= 1)");
+  return rmcl_attn_stream_bwd(qkv, mask, dout, out, (const float*)probs, scores, dqkv, B, N, H, (hipStream_t)stream);
+}
 
 int rmcl_word_saliency(const float* g, const int32_t* spans, float* out, int B, int W, int L, int D, int row0, int row_step, void* stream) {
   RMCL_REQUIRE(g && spans && out, "word_saliency: NULL argument");

@@ -8,8 +8,34 @@
 #include "rmcl_common.h"
 #include "kernels.h"
 #include "../../include/rmcl.h"
+#include <mutex>
 
 namespace {
+
+// RMCL_MODE_STREAM_ATTN: the attention of a pass runs the streaming kernels (attention_stream.hip) when the bit is set and the pass is
+// one the unfused path would otherwise take at bf16 speed settings: N > 256.  Everything else ignores the bit.
+inline bool stream_attn(const rmcl_dims& d, int mode_bits) {
+  return (mode_bits & RMCL_MODE_STREAM_ATTN) && d.dtype == RMCL_BF16 && !d.exact && d.L + 1 + d.P > 256;
+}
+// What the last forward left in the `probs` slots of a stash (log-sum-exp or probabilities), by stash address: host-side memory of the
+// most recent stashes, so that a backward called with the other setting is refused instead of reading one as the other.
+struct StashNote { const void* stash; bool stream; };
+StashNote g_stash_notes[64];
+int g_stash_next = 0;
+std::mutex g_stash_mu;
+void note_stash(const void* stash, bool stream) {
+  std::lock_guard<std::mutex> lk(g_stash_mu);
+  for (auto& n : g_stash_notes)
+    if (n.stash == stash) { n.stream = stream; return; }
+  g_stash_notes[g_stash_next] = StashNote{stash, stream};
+  g_stash_next = (g_stash_next + 1) % 64;
+}
+bool stash_disagrees(const void* stash, bool stream) {
+  std::lock_guard<std::mutex> lk(g_stash_mu);
+  for (auto& n : g_stash_notes)
+    if (n.stash == stash) return n.stream != stream;
+  return false;                                                // a stash this table no longer knows: nothing to compare
+}
 
 struct Bump {
   char* base;
@@ -350,7 +376,8 @@ void rmcl_param_layout(const rmcl_dims* d, rmcl_layout* o) {
   o->total = off;
 }
 
-int64_t rmcl_stash_bytes(const rmcl_dims* d, int mode) { return (int64_t)carve_stash(*d, mode, nullptr, nullptr) + 256; }
+// (RMCL_MODE_STREAM_ATTN does not change the stash: the `probs` slots stay sized for the unfused matrices)
+int64_t rmcl_stash_bytes(const rmcl_dims* d, int mode) { return (int64_t)carve_stash(*d, mode & ~RMCL_MODE_STREAM_ATTN, nullptr, nullptr) + 256; }
 int64_t rmcl_workspace_bytes(const rmcl_dims* d) { return (int64_t)carve_work(*d, nullptr, nullptr) + 256; }
 
 // rank != NULL: the image tokens and their mask come from a cache of rmcl_visual_embed outputs (rmcl_encoder_forward_rank); `patches`
@@ -365,7 +392,8 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
   RMCL_REQUIRE(params32 && text_ids && text_mask && (patches || rank) && co_mask && workspace && xn, "encoder_forward: NULL argument");
   RMCL_REQUIRE(d->dtype == RMCL_F32 || params_lp, "encoder_forward: bf16 mode needs the bf16 shadow arena");
   const bool tail_req = (mode & RMCL_MODE_CLS_TAIL) != 0;     // only the cls rows of xn will be read (include/rmcl.h)
-  mode &= ~RMCL_MODE_CLS_TAIL;
+  const bool streamed = stream_attn(*d, mode);                // attention through the streaming kernels (include/rmcl.h)
+  mode &= ~(RMCL_MODE_CLS_TAIL | RMCL_MODE_STREAM_ATTN);
   RMCL_REQUIRE(mode == RMCL_MODE_INFER || stash, "encoder_forward: stash required unless mode is INFER");
   RMCL_REQUIRE(!tail_req || d->B <= 1024, "encoder_forward: the cls-only tail needs B <= 1024");
   Ctx c{*d, params32, params_lp, {}, (hipStream_t)stream, d->dtype};
@@ -375,6 +403,7 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
   Work w{};
   carve_stash(*d, mode, stash, &st);
   carve_work(*d, workspace, &w);
+  if (mode != RMCL_MODE_INFER) note_stash(stash, streamed);
   const int B = d->B, L = d->L, P = d->P, N = L + 1 + P, D = d->D, M = B * N, dt = d->dtype;
   const bool keep = mode != RMCL_MODE_INFER, full = mode == RMCL_MODE_FULL;
   hipStream_t s = c.s;
@@ -466,7 +495,8 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
       g.epi = EPI_BIAS; g.bias = c.V(c.L(l, y.qkv_b)); g.tag = GEMM_TAG_QKV;
       RMCL_TRY(gemm(c, g, dt, dt, 1, 1));
     }
-    RMCL_TRY(rmcl_attention_fwd_impl(qkv, co_mask, ao, probs, w.scores, B, N, d->H, dt, d->exact, s));
+    if (streamed) RMCL_TRY(rmcl_attn_stream_fwd(qkv, co_mask, ao, (float*)probs, B, N, d->H, s));   // `probs` keeps the log-sum-exp
+    else RMCL_TRY(rmcl_attention_fwd_impl(qkv, co_mask, ao, probs, w.scores, B, N, d->H, dt, d->exact, s));
     if (tail_req && l + 1 == d->layers) {
       // cls-only tail: of the last block's output only row 0 of every sample is read (the pooler takes hidden_states[:, 0],
       // heads.py:17), and everything behind the attention is row-wise - proj, LayerNorm 2, the MLP and the final LayerNorm run
@@ -551,7 +581,7 @@ int rmcl_encoder_forward_rank(const rmcl_dims* d, int mode, const float* params3
                               const int64_t* text_mask, const rmcl_rank_src* src, int32_t* co_mask, void* workspace, float* xn,
                               const rmcl_fold* fold, void* stream) {
   RMCL_REQUIRE(d && src && src->embeds && src->masks && src->img_of, "encoder_forward_rank: NULL argument");
-  RMCL_REQUIRE((mode & ~RMCL_MODE_CLS_TAIL) == RMCL_MODE_INFER, "encoder_forward_rank: INFER mode only (the rank pass keeps no stash)");
+  RMCL_REQUIRE((mode & ~(RMCL_MODE_CLS_TAIL | RMCL_MODE_STREAM_ATTN)) == RMCL_MODE_INFER, "encoder_forward_rank: INFER mode only (the rank pass keeps no stash)");
   RMCL_REQUIRE(src->n_img >= 1 && d->P >= 1 && d->P + 1 <= src->ld_tok, "encoder_forward_rank: the cache slots hold fewer than 1 + P token rows");
   RMCL_REQUIRE(d->img_type == 0 || d->img_type == 1, "encoder_forward_rank: image tokens take token-type row 1");
   return encoder_forward_impl(d, mode, params32, params_lp, text_ids, text_mask, nullptr, co_mask, nullptr, workspace, xn, 0u, 0.f, nullptr,
@@ -591,9 +621,12 @@ int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, c
                           int cls_only, void* dpatches, float* dtext, float* G, uint32_t drop_seed, float drop_p,
                           const rmcl_ragged* ragged, const void* params_lpT, void* stream) {
   RMCL_TRY(check_dims(d));
+  const bool streamed = stream_attn(*d, mode);
+  mode &= ~RMCL_MODE_STREAM_ATTN;
   RMCL_REQUIRE(!ragged || mode != RMCL_MODE_FULL || ragged->dpos_tok, "encoder_backward: rmcl_ragged.dpos_tok needed in FULL mode");
   RMCL_REQUIRE(mode == RMCL_MODE_DATA || mode == RMCL_MODE_FULL, "encoder_backward: mode must be DATA or FULL");
   RMCL_REQUIRE(params32 && stash && workspace && dxn && co_mask, "encoder_backward: NULL argument");
+  RMCL_REQUIRE(!stash_disagrees(stash, streamed), "encoder_backward: RMCL_MODE_STREAM_ATTN differs from the forward that filled this stash");
   RMCL_REQUIRE(mode != RMCL_MODE_FULL || (G && text_ids && patches), "encoder_backward: FULL mode needs grads32, text_ids, patches");
   RMCL_REQUIRE(d->dtype == RMCL_F32 || params_lp, "encoder_backward: bf16 mode needs the bf16 shadow arena");
   Ctx c{*d, params32, params_lp, {}, (hipStream_t)stream, d->dtype};
@@ -803,7 +836,8 @@ int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, c
     }
     }   // !tail_l
     if (use_side && !grouped && l + 2 < Lr) HIP_TRY(hipStreamWaitEvent(s, EV(2, l + 2), 0));   // dqkv buffer free again
-    RMCL_TRY(rmcl_attention_bwd_impl(ls.qkv, co_mask, ls.probs, w.dao, ls.ao, dqkv, w.scores, w.dS, B, N, d->H, dt, d->exact, s));
+    if (streamed) RMCL_TRY(rmcl_attn_stream_bwd(ls.qkv, co_mask, w.dao, ls.ao, (const float*)ls.probs, w.scores, dqkv, B, N, d->H, s));
+    else RMCL_TRY(rmcl_attention_bwd_impl(ls.qkv, co_mask, ls.probs, w.dao, ls.ao, dqkv, w.scores, w.dS, B, N, d->H, dt, d->exact, s));
     if (full && !grouped) {
       if (use_side) { HIP_TRY(hipEventRecord(EV(0, 2 * l + 1), s)); HIP_TRY(hipStreamWaitEvent(cs.s, EV(0, 2 * l + 1), 0)); }
       if (!tail_l) {

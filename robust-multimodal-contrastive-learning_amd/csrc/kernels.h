@@ -80,6 +80,13 @@ inline long rmcl_attn_scratch_elems(int B, int H, int N) {
 int rmcl_attn_fused_fwd(const void* qkv, const int* mask, void* out, float* lse, int B, int N, int H, hipStream_t s);
 int rmcl_attn_fused_bwd(const void* qkv, const int* mask, const void* dout, const void* out, const float* lse, float* delta, void* dqkv,
                         int B, int N, int H, hipStream_t s);
+// attention_stream.hip: the same contract for 1 <= N <= 512, keys / queries streamed through LDS in 64-row blocks.  lse / delta are fp32
+// [B, H, NKP] with NKP = N rounded up to 64 (rmcl_attn_stream_stat_elems: never more than rmcl_attn_stat_elems, so the sizing above holds);
+// the backward takes delta = rowsum(dO * O) and therefore needs `out`.
+long rmcl_attn_stream_stat_elems(int B, int H, int N);
+int rmcl_attn_stream_fwd(const void* qkv, const int* mask, void* out, float* lse, int B, int N, int H, hipStream_t s);
+int rmcl_attn_stream_bwd(const void* qkv, const int* mask, const void* dout, const void* out, const float* lse, float* delta, void* dqkv,
+                         int B, int N, int H, hipStream_t s);
 int rmcl_colsum(const void* X, long ld, int dt, float* out, int M, int N, hipStream_t s);
 
 int rmcl_text_embed_fwd(const long* ids, const float* word, const float* pos, const float* btype0, const float* g,

@@ -368,6 +368,11 @@ class Engine:
         # measurement / parity mode, ~6x slower than bf16 PGD).  None: PGD runs in the engine's dtype.
         self.pgd_dtype = {None: None, "f32": L.F32, "fp32": L.F32, "bf16": None}[pgd_dtype] if self.dtype == L.BF16 else None
         self.num_negative = int(cfg.get("num_negative", 65536))
+        # config["long_sequences"] (bool, default False): a bf16 engine runs passes of 257..512 tokens (max_image_len = -1 of the fine-tuning
+        # tasks: 384 x 640 gives 240 + 1 + 40 = 281) through the streaming attention kernels (include/rmcl.h RMCL_MODE_STREAM_ATTN) instead
+        # of refusing them; every encoder pass of more than 256 tokens then carries the mode bit (stream_bit).
+        self.long_sequences = bool(cfg.get("long_sequences", False)) and self.dtype == L.BF16
+        self.token_cap = 512 if self.long_sequences else 256       # tokens per sequence on the bf16 path
         d0 = self.dims(1)
         self.layout = L.Layout()
         lib.rmcl_param_layout(C.byref(d0), C.byref(self.layout))
@@ -604,7 +609,9 @@ class Engine:
         mil = self.cfg.get("max_image_len", -1) if max_image_len is None else max_image_len
         if isinstance(mil, int) and mil > 0:
             n = min(n, mil)                                                # vision_transformer.py:602-616
-        if check_tokens and n + 1 + self.cfg["max_text_len"] > 256 and self.dtype == L.BF16:
+        if check_tokens and n + 1 + self.cfg["max_text_len"] > self.token_cap and self.dtype == L.BF16:
+            if self.long_sequences:
+                raise self.token_limit_error(n)
             raise NotImplementedError(f"{n} image patches + text exceed the 256-token limit of the fused attention kernels")
         over = []
         if select is not None:
@@ -783,6 +790,10 @@ class Engine:
         return out
 
     # ---- encoder passes ------------------------------------------------------------------------
+    def stream_bit(self, d) -> int:
+        """RMCL_MODE_STREAM_ATTN for a pass of more than 256 tokens on an engine built with long_sequences, else 0."""
+        return L.MODE_STREAM_ATTN if (self.long_sequences and d.L + 1 + d.P > 256) else 0
+
     def encoder_forward(self, pb: PassBuffers, key: bool, mode: int, patchesT: torch.Tensor, cls_tail: bool = False):
         """cls_tail: the caller reads only the cls row of every sample of pb.xn (the contrastive objectives: pooler -> head); the
         last block then runs its row-wise part on B rows (include/rmcl.h RMCL_MODE_CLS_TAIL).  Remembered per (buffers, mode):
@@ -802,7 +813,7 @@ class Engine:
             self.pass_log.append({"seed": seed, "p": p, "mode": mode, "key": bool(key), "B": pb.B, "lane": getattr(pb, "lane", None), "tail": tail})
         p32, plp = (self.k32, self.k_lp) if key else (self.q32, self.q_lp)
         stash = {L.MODE_INFER: None, L.MODE_DATA: pb.stash_data, L.MODE_FULL: pb.stash_full}[mode]
-        check(lib.rmcl_encoder_forward(C.byref(pb.d), mode | (L.MODE_CLS_TAIL if tail else 0), P(p32), P(plp), P(pb.text_ids), P(pb.text_mask), P(patchesT),
+        check(lib.rmcl_encoder_forward(C.byref(pb.d), mode | (L.MODE_CLS_TAIL if tail else 0) | self.stream_bit(pb.d), P(p32), P(plp), P(pb.text_ids), P(pb.text_mask), P(patchesT),
                                        P(pb.co_mask), P(stash), P(pb.workspace), P(pb.xn), C.c_uint32(seed), F(p), self._rg(pb),
                                        self.fold_of(key) if (mode != L.MODE_FULL and pb.dtype == L.BF16) else None, stream_ptr()),
               "encoder_forward")
@@ -861,7 +872,7 @@ class Engine:
         co = (2 if pb.tail.get(mode) else 1) if cls_only else 0
         if pb.tail.get(mode) and not cls_only:
             raise L.RmclError("encoder_backward: the forward of these buffers kept only the cls rows (cls_tail) - a full-row gradient has nowhere to go")
-        check(lib.rmcl_encoder_backward(C.byref(pb.d), mode, P(self.q32), P(self.q_lp), P(pb.text_ids), P(patchesT),
+        check(lib.rmcl_encoder_backward(C.byref(pb.d), mode | self.stream_bit(pb.d), P(self.q32), P(self.q_lp), P(pb.text_ids), P(patchesT),
                                         P(pb.co_mask), P(stash), P(pb.workspace), P(dxn), co, P(dpatches), P(dtext),
                                         P(self.g32 if mode == L.MODE_FULL else None), C.c_uint32(seed), F(p), self._rg(pb),
                                         P(self.weights_T() if pb.dtype == L.BF16 else None), stream_ptr()), "encoder_backward")
@@ -1125,15 +1136,38 @@ class Engine:
         return dcls
 
     def token_limit_error(self, n_patches: int):
-        """the message of a rank pass / recall evaluation that cannot run: names the two ways out"""
+        """the message of a rank pass / recall evaluation that cannot run: names the ways out"""
         Lt = int(self.cfg["max_text_len"])
+        if self.long_sequences:
+            return NotImplementedError(
+                f"{n_patches} image patches + 1 cls + {Lt} text tokens = {n_patches + 1 + Lt} tokens exceed the 512-token limit of the streaming "
+                f"bf16 attention kernels (long_sequences): set max_image_len <= {511 - Lt}, or build the model with compute_dtype='f32' (the "
+                f"fp32 engine has no such limit)")
         return NotImplementedError(
             f"{n_patches} image patches + 1 cls + {Lt} text tokens = {n_patches + 1 + Lt} tokens exceed the 256-token limit of the fused bf16 "
-            f"attention kernels: set max_image_len <= {255 - Lt}, or build the model with compute_dtype='f32' (the fp32 engine has no such limit)")
+            f"attention kernels: set max_image_len <= {255 - Lt}, or build the model with compute_dtype='f32' (the fp32 engine has no such limit), "
+            f"or set config['long_sequences'] = True (streaming attention kernels, up to 512 tokens)")
+
+    def patch_count(self, images: torch.Tensor, max_image_len=None) -> int:
+        """the padded image length n that visual_embed(images, max_image_len) would produce, without embedding or drawing anything
+        (patch_geometry's count and cap, not its selection: the host generator is left alone)"""
+        img = images.to(self.device, torch.float32).contiguous()
+        B, Cc, Hh, Ww = img.shape
+        ps = self.cfg["patch_size"]
+        if Cc != 3 or Hh % ps or Ww % ps or (Hh // ps) * (Ww // ps) > 1024:
+            return self.patch_geometry(img, None, max_image_len=max_image_len, check_tokens=False).n      # raises its ValueError
+        sel = torch.empty(B, (Hh // ps) * (Ww // ps), dtype=torch.int32, device=self.device)
+        counts = torch.empty(B, dtype=torch.int32, device=self.device)
+        hw = torch.empty(B, 2, dtype=torch.int32, device=self.device)
+        check(lib.rmcl_patch_select(P(img), B, 3, Hh, Ww, ps, P(sel), P(counts), P(hw), stream_ptr()), "patch_select")
+        n = int(counts.max())
+        mil = self.cfg.get("max_image_len", -1) if max_image_len is None else max_image_len
+        return min(n, mil) if isinstance(mil, int) and mil > 0 else n
 
     def visual_embed(self, images: torch.Tensor, max_image_len=None, select: torch.Tensor = None):
         """VisionTransformer.visual_embed (vision_transformer.py:559-677, mask_it=False): (embeds [B, 1 + n, D] f32 WITHOUT the token-type
-        row, masks [B, 1 + n] int64, patch_index [B, n, 2]).  No token limit applies here (the pass has no text): the rank pass checks.
+        row, masks [B, 1 + n] int64, patch_index [B, n, 2]).  The 256-token limit does not apply here (the pass has no text): the rank pass
+        checks; with long_sequences an image that cannot fit 512 tokens with its text is refused here already.
         Runs once per image, so its buffers are allocated per call (the caching allocator hands the same blocks back)."""
         if self.lp_stale:
             self.refresh_shadows()
@@ -1143,6 +1177,10 @@ class Engine:
         geom = self.patch_geometry(img, select, max_image_len=max_image_len, check_tokens=False)
         g = self.cfg["image_size"] // ps
         n = g * g if geom is None else geom.n
+        if self.long_sequences and n + 1 + int(self.cfg["max_text_len"]) > self.token_cap:
+            # 512 tokens is also where the library's own dims check ends: name the ways out instead.  compute_irtr_recall never gets here:
+            # it takes patch_count() first and raises on every rank together
+            raise self.token_limit_error(n)
         d = self.dims(B, None, n)
         ws = torch.empty(int(lib.rmcl_workspace_bytes(C.byref(d))), dtype=torch.uint8, device=self.device)
         pat32 = torch.empty(B * n, d.patch_k, dtype=torch.float32, device=self.device)
@@ -1181,7 +1219,7 @@ class Engine:
         if tuple(masks.shape) != (n_img, ld_tok) or img_of.numel() != B or n_patches + 1 > ld_tok or n_patches < 1 or D != self.cfg["hidden_size"]:
             raise ValueError(f"rank_forward: shapes do not fit (embeds {tuple(embeds.shape)}, masks {tuple(masks.shape)}, {B} sequences, "
                              f"{n_patches} patches)")
-        if n_patches + 1 + self.cfg["max_text_len"] > 256 and self.dtype == L.BF16:
+        if n_patches + 1 + self.cfg["max_text_len"] > self.token_cap and self.dtype == L.BF16:
             raise self.token_limit_error(n_patches)
         if self._rank_pass is None:
             self._rank_pass = RankPass(self)
@@ -1193,7 +1231,7 @@ class Engine:
         src = L.RankSrc(embeds=embeds.data_ptr(), masks=masks.data_ptr(), img_of=img_of.data_ptr(), n_img=n_img, ld_tok=ld_tok)
         tail = bool(cls_tail) and B <= 1024 and os.environ.get("RMCL_NO_CLS_TAIL", "0") != "1"
         fold = self.fold_of(False) if rp.dtype == L.BF16 else None
-        check(lib.rmcl_encoder_forward_rank(C.byref(rp.d), L.MODE_INFER | (L.MODE_CLS_TAIL if tail else 0), P(self.q32), P(self.q_lp),
+        check(lib.rmcl_encoder_forward_rank(C.byref(rp.d), L.MODE_INFER | (L.MODE_CLS_TAIL if tail else 0) | self.stream_bit(rp.d), P(self.q32), P(self.q_lp),
                                             P(rp.text_ids), P(rp.text_mask), C.byref(src), P(rp.co_mask), P(rp.workspace), P(rp.xn), fold,
                                             stream_ptr()), "encoder_forward_rank")
         rp.keep_alive = (embeds, masks, img_of)

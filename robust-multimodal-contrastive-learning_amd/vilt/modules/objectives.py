@@ -792,19 +792,27 @@ def compute_irtr_recall(pl_module, text_dset=None, image_dset=None, tile_images:
     world, rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if dist_on else (1, 0)
     mine = irtr_rank_split(len(image_dset), world, rank)
     per_image, iids = [], []
+    over = 0
     for b in _irtr_batches(image_dset, mine, 1, mlm):
+        if eng.long_sequences:
+            # an image past the 512-token limit cannot be embedded at all (the library's dims end there): it is only counted, so that
+            # this rank reaches the reduction below and every rank raises together
+            n_i = eng.patch_count(b["image"][0], cfg["max_image_len"])
+            if n_i + 1 + int(cfg["max_text_len"]) > eng.token_cap:
+                over = max(over, n_i)
+                continue
         ie, im, _, _ = pl_module.visual_embed(b["image"][0].to(dev), max_image_len=cfg["max_image_len"], mask_it=False)
         per_image.append((ie, im))
         iids.append(int(b["img_index"][0]))
     counts = [int(ie.shape[1]) - 1 for ie, _ in per_image]
-    n_max = max(counts)
+    n_max = max(counts + [over])
     if world > 1:
         # every rank sees the longest image of the WHOLE split: all of them raise below, none is left waiting in the gather
         longest = torch.tensor([n_max], dtype=torch.int64, device=dev)
         torch.distributed.all_reduce(longest, op=torch.distributed.ReduceOp.MAX)
         n_max = int(longest)
     # the token limit is checked HERE, on the whole image cache, before the first pair is scored
-    if eng.dtype == L.BF16 and n_max + 1 + int(cfg["max_text_len"]) > 256:
+    if eng.dtype == L.BF16 and n_max + 1 + int(cfg["max_text_len"]) > eng.token_cap:
         raise eng.token_limit_error(n_max)
     embeds = torch.zeros(len(per_image), n_max + 1, int(cfg["hidden_size"]), dtype=torch.float32, device=dev)
     masks = torch.zeros(len(per_image), n_max + 1, dtype=torch.int32, device=dev)
