@@ -365,6 +365,48 @@ int rmcl_mlm_backward(const rmcl_mlm_head* h, const float* params, const void* p
 int rmcl_mlm_logits(const rmcl_mlm_head* h, const float* params, const void* params_lp, int dtype, float* ws, int rows, int rows_out,
                     float* logits, int64_t ldl, void* stream);
 
+/* ---- Masked patch prediction (task_mlm_itm_mpp) ----------------------------------------------------------------------------
+ * VisionTransformer.mask_tokens (vision_transformer.py:525-557), MPPHead (heads.py:198-207) and compute_mpp (objectives.py:632-665):
+ * mpp_score = Linear(D,D) - GELU (exact erf) - LayerNorm(D, eps 1e-12) - Linear(D, 768) + bias; the 768 logits are 3 channels x 256
+ * intensity classes; loss = cross_entropy(logits.view(-1, 256), labels.view(-1), ignore_index -100), the mean over the labelled
+ * (row, channel) pairs.  mt [D] (transformer.mask_token), tw [D,D], tb [D], lg / lb [D] (LayerNorm), dw [768,D], db [768]: element
+ * offsets in ONE fp32 arena (parameters and, at the same offsets, gradients).  D in {256, 768}.  `rows`, dtype and the no-atomics rule
+ * are those of the MLM head above: the head runs on the COMPACTED masked image rows, n stays on the device.                        */
+typedef struct rmcl_mpp_head {
+  int32_t D, reserved;
+  int64_t mt, tw, tb, lg, lb, dw, db;
+} rmcl_mpp_head;
+/* floats of the workspace `ws` shared by forward / backward / logits for this launch extent (monotone in rows) */
+int64_t rmcl_mpp_ws_floats(const rmcl_mpp_head* h, int rows);
+/* labels [B, P, 3] int32 of the float image img [B, 3, H, W] (H, W multiples of the 32-pixel patch): per patch and channel
+ * trunc(((sum of img * 0.5 + 0.5 over the patch) * (1 / 1024)) * 255), fp32.  sel = NULL: the whole grid, P = (H / 32) (W / 32), slot j =
+ * patch j; else the selected slots of an rmcl_ragged selection (sel [B, sel_ld], counts [B], gw = W / 32): slot j < counts[b] reads patch
+ * sel[b, j], every other slot gets -100 in all three channels.                                                                   */
+int rmcl_mpp_labels(const float* img, int B, int H, int W, const int32_t* sel, const int32_t* counts, int sel_ld, int gw, int P,
+                    int32_t* labels, void* stream);
+/* labels [B, P, 3], masked [B, P] int32 -> idx [cap]: row b * N + L + 1 + j of xn [B N, D] for every masked valid slot (ascending) whose
+ * three labels lie in [0, 256); lab [cap, 3] its labels; count [2]: count[0] = n, count[1] = the label entries outside [0, 256) of masked
+ * valid slots (such a slot is skipped; callers turn a non-zero count[1] into an error).  A masked pad slot (labels -100) is ignored.
+ * Entries behind n: idx -1, lab -100.  all_rows = 1 (the dense-logits pass): every image row b * N + L + t, t = 0 .. P, is listed (the
+ * cls row first) and lab keeps -100 wherever the compacted form lists nothing.  cap >= B * (P + all_rows).                         */
+int rmcl_mpp_compact(const int32_t* labels, const int32_t* masked, int B, int P, int L, int N, int all_rows, int cap, int32_t* idx, int32_t* lab,
+                     int32_t* count, void* stream);
+/* gather xn[idx] -> transform -> decoder -> three 256-way cross-entropies per row.  Per listed row r < n: lse [rows, 3], argmax [rows, 3]
+ * (first maximum), rowloss [rows] = the sum over its labelled channels of lse - z[label]; rows >= n: 0 / -1 / 0.
+ * stats [3] = (sum rowloss / pairs, pairs with argmax == label, pairs), pairs = 3 n on the compacted path; n = 0 gives a NaN loss like
+ * F.cross_entropy over an all-ignored batch.  `ws` keeps what the backward / the logits writer need (the dense [rows, 768] logits). */
+int rmcl_mpp_forward(const rmcl_mpp_head* h, const float* params, const void* params_lp, int dtype, const float* xn, const int32_t* idx,
+                     const int32_t* lab, const int32_t* count, int rows, float* ws, float* lse, float* rowloss, int32_t* argmax, float* stats,
+                     void* stream);
+/* dz = grad_scale s (softmax(z) - onehot) / (3 n) (s = *grad_scale_dev, read on the device, or 1 when NULL), after a forward on the
+ * compacted rows; G != NULL: the six head gradients are ACCUMULATED into G at the head's offsets; dxn != NULL: the gradient of the
+ * gathered rows is stored to dxn[idx[r]] (dxn [B N, D] zero-filled by the caller).  n = 0: dz = 0, nothing changes.                */
+int rmcl_mpp_backward(const rmcl_mpp_head* h, const float* params, const void* params_lp, int dtype, const int32_t* idx, const int32_t* lab,
+                      const int32_t* count, int rows, float* ws, const float* lse, float grad_scale, const float* grad_scale_dev, float* G,
+                      float* dxn, void* stream);
+/* logits [rows_out, 768] of the first rows_out listed rows of the last rmcl_mpp_forward on `ws` */
+int rmcl_mpp_logits(const rmcl_mpp_head* h, float* ws, int rows, int rows_out, float* logits, void* stream);
+
 /* ---- Text attack on the fine-tuning tasks (GreedyAttack_vqa / GreedyAttack_nlvr2) ------------------------------------------
  * get_important_scores (attack/greedy_attack_vilt.py:221-228) on the device: the L1 norm over the hidden columns of the MEAN saliency
  * gradient over a word's sub-word tokens,
@@ -390,6 +432,16 @@ int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, co
                          int32_t* co_mask, void* stash, void* workspace, float* xn,
                          uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold, void* stream);
 
+/* rmcl_encoder_forward with the mask-token substitution of masked patch prediction: replaced [B, P] int32; where replaced[b, j] != 0 the
+ * patch-projection output (bias included) of slot j is replaced by the mask token params32[mask_token_off .. + D) BEFORE the position
+ * rows and the token type are added (vision_transformer.py:602-603).  Every mode; RMCL_MODE_CLS_TAIL is refused (the loss reads the
+ * image rows).  replaced = NULL (or all zero): rmcl_encoder_forward, bit for bit.                                                 */
+int rmcl_encoder_forward_mpp(const rmcl_dims* d, int mode, const float* params32, const void* params_lp,
+                             const int64_t* text_ids, const int64_t* text_mask, const void* patches,
+                             int32_t* co_mask, void* stash, void* workspace, float* xn,
+                             uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold,
+                             const int32_t* replaced, int64_t mask_token_off, void* stream);
+
 /* ---- Image-text retrieval (IRTR) ---------------------------------------------------------------------------------------
  * The image side of VisionTransformer.visual_embed (vision_transformer.py:559-677, mask_it = False) for the patch rows of
  * rmcl_encoder_forward: patch GEMM + (resized) position rows + cls token, WITHOUT the token-type row (the reference adds it in infer,
@@ -397,6 +449,10 @@ int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, co
  * workspace: rmcl_workspace_bytes(d).  ragged as for rmcl_encoder_forward (dpos_tok is not used).                             */
 int rmcl_visual_embed(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
                       void* workspace, float* out, int32_t* masks, void* stream);
+
+/* rmcl_visual_embed with the mask-token substitution of rmcl_encoder_forward_mpp (visual_embed(mask_it=True)): replaced [B, P] int32 */
+int rmcl_visual_embed_mpp(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
+                          void* workspace, float* out, int32_t* masks, const int32_t* replaced, int64_t mask_token_off, void* stream);
 
 /* The image tokens of a rank pass come from a device-resident cache of rmcl_visual_embed outputs instead of pixels
  * (compute_irtr_recall, objectives.py:1226-1346: every image against every caption).  embeds [n_img, ld_tok, D] f32 and
@@ -444,6 +500,17 @@ int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, c
                           void* stash, void* workspace, const float* dxn, int cls_only,
                           void* dpatches, float* dtext, float* grads32, uint32_t drop_seed, float drop_p,
                           const rmcl_ragged* ragged, const void* params_lpT, void* stream);
+
+/* rmcl_encoder_backward (full-row dxn: cls_only = 0) of a pass run by rmcl_encoder_forward_mpp with the same `replaced`: the gradient
+ * arriving at the patch-embedding rows of replaced patches (image-token dropout mask applied, fp32, rows ascending) is ACCUMULATED into
+ * grads32[mask_token_off .. + D) in FULL mode, and those rows are zeroed before dpatches, the patch-weight and the patch-bias gradients
+ * read them: a replaced patch contributes nothing to patch_embed.proj.  replaced = NULL: rmcl_encoder_backward, bit for bit.        */
+int rmcl_encoder_backward_mpp(const rmcl_dims* d, int mode, const float* params32, const void* params_lp,
+                              const int64_t* text_ids, const void* patches, const int32_t* co_mask,
+                              void* stash, void* workspace, const float* dxn,
+                              void* dpatches, float* dtext, float* grads32, uint32_t drop_seed, float drop_p,
+                              const rmcl_ragged* ragged, const void* params_lpT,
+                              const int32_t* replaced, int64_t mask_token_off, void* stream);
 
 /* Pooler + MoCo head + L2 normalise (vilt/modules/heads.py:10-20,129-143; objectives.py:264-269).
  * pool32: arena that owns the pooler (always the query arena); head32: arena that owns the

@@ -66,6 +66,12 @@ class MlmHead(C.Structure):
                 ("tw", C.c_int64), ("tb", C.c_int64), ("lg", C.c_int64), ("lb", C.c_int64), ("dw", C.c_int64), ("db", C.c_int64)]
 
 
+class MppHead(C.Structure):
+    """include/rmcl.h rmcl_mpp_head: width of mpp_score and the arena offsets of transformer.mask_token and the head's six tensors."""
+    _fields_ = [("D", C.c_int32), ("reserved", C.c_int32),
+                ("mt", C.c_int64), ("tw", C.c_int64), ("tb", C.c_int64), ("lg", C.c_int64), ("lb", C.c_int64), ("dw", C.c_int64), ("db", C.c_int64)]
+
+
 class RankSrc(C.Structure):
     """include/rmcl.h rmcl_rank_src: the cache of visual_embed outputs a rank pass gathers its image tokens from (device pointers)."""
     _fields_ = [("embeds", C.c_void_p), ("masks", C.c_void_p), ("img_of", C.c_void_p), ("n_img", C.c_int32), ("ld_tok", C.c_int32)]
@@ -84,7 +90,7 @@ def _load():
     lib.rmcl_last_error.restype = C.c_char_p
     for name in ("rmcl_stash_bytes", "rmcl_workspace_bytes", "rmcl_heads_stash_bytes", "rmcl_infonce_ws_bytes",
                  "rmcl_attention_scratch_elems", "rmcl_attention_stream_stat_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats",
-                 "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats"):
+                 "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats", "rmcl_mpp_ws_floats"):
         getattr(lib, name).restype = C.c_int64
     return lib
 
@@ -106,6 +112,8 @@ EXPORTS = (
     "rmcl_nlvr2_ce",
     "rmcl_visual_embed", "rmcl_encoder_forward_rank", "rmcl_irtr_score", "rmcl_irtr_ce", "rmcl_irtr_bwd",
     "rmcl_mlm_ws_floats", "rmcl_mlm_compact", "rmcl_mlm_weight_transpose", "rmcl_mlm_forward", "rmcl_mlm_backward", "rmcl_mlm_logits",
+    "rmcl_mpp_ws_floats", "rmcl_mpp_labels", "rmcl_mpp_compact", "rmcl_mpp_forward", "rmcl_mpp_backward", "rmcl_mpp_logits",
+    "rmcl_encoder_forward_mpp", "rmcl_encoder_backward_mpp", "rmcl_visual_embed_mpp",
     "rmcl_word_saliency",
 )
 

@@ -253,6 +253,66 @@ int rmcl_image_assemble_bwd(const float* dx, void* dpe, int dt, float* dpos, flo
 }
 
 // ---------------------------------------------------------------------------------------------
+// Masked patch prediction (VisionTransformer.mask_tokens, vision_transformer.py:525-557): the patch-projection output (bias included)
+// of a replaced patch becomes the learned mask token, before the position rows and the token type are added.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mask_token_fwd_kernel(float* __restrict__ pe, const int* __restrict__ replaced,
+                                                             const float* __restrict__ mask_token, int rows, int D) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const int dv = D / 4;
+  if (i >= (long)rows * dv) return;
+  const int r = (int)(i / dv), c = (int)(i - (long)r * dv) * 4;
+  if (replaced[r] != 0) *reinterpret_cast<float4*>(pe + (long)r * D + c) = *reinterpret_cast<const float4*>(mask_token + c);
+}
+int rmcl_mask_token_fwd(float* pe, const int* replaced, const float* mask_token, int rows, int D, hipStream_t s) {
+  RMCL_REQUIRE(D % 4 == 0, "mask_token: D%4");
+  RMCL_LAUNCH(mask_token_fwd_kernel, dim3(cdiv((long)rows * (D / 4), 256)), dim3(256), 0, s, pe, replaced, mask_token, rows, D);
+  RMCL_CHECK_LAUNCH();
+  return 0;
+}
+// backward, two steps with a fixed order and one owner per output (no atomics): workgroup (column block, sample b) adds the gradient of
+// sample b's replaced rows in ascending slot order (the value image_assemble_bwd formed: dx times the image-token dropout mask, here in
+// fp32) into part[b][c] and zeroes their dpe entries, so a replaced patch contributes nothing to the patch projection's gradients or to
+// dpatches; then one thread per column adds the samples' partials in ascending order into dmask_token.
+template <typename T>
+__global__ __launch_bounds__(64) void mask_token_bwd_kernel(const float* __restrict__ dx, T* __restrict__ dpe, const int* __restrict__ replaced,
+                                                            float* __restrict__ part, int B, int P, int L, int N, int D, uint32_t dseed,
+                                                            uint32_t dthresh, float dinv) {
+  const int c = blockIdx.x * 64 + threadIdx.x, b = blockIdx.y;
+  if (c >= D) return;
+  float acc = 0.f;
+  for (int j = 0; j < P; ++j) {
+    if (replaced[b * P + j] == 0) continue;                  // (uniform over the workgroup)
+    const int tok = j + 1;
+    const float raw = dx[((long)b * N + L + tok) * D + c];
+    acc += dthresh ? raw * drop_scale(dseed, (uint32_t)(((long)b * (P + 1) + tok) * D + c), dthresh, dinv) : raw;
+    dpe[((long)b * P + j) * D + c] = from_f32<T>(0.f);
+  }
+  if (part) part[(long)b * D + c] = acc;
+}
+__global__ __launch_bounds__(64) void mask_token_merge_kernel(const float* __restrict__ part, float* __restrict__ dmask, int B, int D) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= D) return;
+  float s = 0.f;
+  for (int b = 0; b < B; ++b) s += part[(long)b * D + c];
+  dmask[c] += s;
+}
+int rmcl_mask_token_bwd(const float* dx, void* dpe, int dt, const int* replaced, float* dmask_token, float* part, int B, int P, int L, int N,
+                        int D, uint32_t dseed, uint32_t dthresh, float dinv, hipStream_t s) {
+  RMCL_REQUIRE(!dmask_token || part, "mask_token_bwd: the mask-token gradient needs the [B, D] partial buffer");
+  const dim3 grid(cdiv(D, 64), B);
+  float* pt = dmask_token ? part : nullptr;
+  if (dt == RMCL_F32) RMCL_LAUNCH(mask_token_bwd_kernel<float>, grid, dim3(64), 0, s, dx, (float*)dpe, replaced, pt, B, P, L, N, D, dseed, dthresh, dinv);
+  else RMCL_LAUNCH(mask_token_bwd_kernel<bf16_t>, grid, dim3(64), 0, s, dx, (bf16_t*)dpe, replaced, pt, B, P, L, N, D, dseed, dthresh, dinv);
+  RMCL_CHECK_LAUNCH();
+  if (dmask_token) {
+    RMCL_LAUNCH(mask_token_merge_kernel, dim3(cdiv(D, 64)), dim3(64), 0, s, part, dmask_token, B, D);
+    RMCL_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Patch layout: image [B,C,Hh,Ww] f32 <-> patches [B*gh*gw, C*ps*ps] f32, K ordered (c,ky,kx)
 // (the GEMM view of Conv2d(3,D,ps,ps,stride ps), vision_transformer.py:397-409).  ps % 4 == 0.
 // ---------------------------------------------------------------------------------------------

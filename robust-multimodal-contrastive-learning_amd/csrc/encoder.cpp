@@ -385,7 +385,7 @@ int64_t rmcl_workspace_bytes(const rmcl_dims* d) { return (int64_t)carve_work(*d
 static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
                                 const int64_t* text_mask, const void* patches, int32_t* co_mask, void* stash, void* workspace,
                                 float* xn, uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold,
-                                const rmcl_rank_src* rank, void* stream) {
+                                const rmcl_rank_src* rank, const int32_t* replaced, int64_t mask_token_off, void* stream) {
   RMCL_TRY(check_dims(d));
   RMCL_REQUIRE(!ragged || (ragged->sel && ragged->counts && ragged->hw && ragged->pos_tok), "encoder_forward: incomplete rmcl_ragged");
   RMCL_REQUIRE(rank || ragged || d->Pp == 0 || d->Pp == d->P, "encoder_forward: P != Pp needs the rmcl_ragged selection");
@@ -426,6 +426,8 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
     GemmArgs g = gemm_args(patches, c.W(y.patch_w), w.pe, B * P, D, d->patch_k, d->patch_k, d->patch_k, D);
     g.epi = EPI_BIAS; g.bias = c.V(y.patch_b); g.tag = GEMM_TAG_PATCH;
     RMCL_TRY(gemm(c, g, dt, RMCL_F32, 1, 1));
+    // masked patch prediction: the learned mask token takes the place of the replaced patches' embeddings (rmcl_encoder_forward_mpp)
+    if (replaced) RMCL_TRY(rmcl_mask_token_fwd(w.pe, replaced, c.V(mask_token_off), B * P, D, s));
     if (ragged) {
       // zero-padded batch: per-sample position rows = the table resized to each image's (h, w), gathered at its selected
       // patches (vision_transformer.py:570-600, 645-650); recomputed every pass from the arena of THIS pass (query or momentum)
@@ -574,7 +576,17 @@ int rmcl_encoder_forward(const rmcl_dims* d, int mode, const float* params32, co
                          const int64_t* text_mask, const void* patches, int32_t* co_mask, void* stash, void* workspace,
                          float* xn, uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold, void* stream) {
   return encoder_forward_impl(d, mode, params32, params_lp, text_ids, text_mask, patches, co_mask, stash, workspace, xn, drop_seed, drop_p,
-                              ragged, fold, nullptr, stream);
+                              ragged, fold, nullptr, nullptr, 0, stream);
+}
+
+int rmcl_encoder_forward_mpp(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                             const int64_t* text_mask, const void* patches, int32_t* co_mask, void* stash, void* workspace, float* xn,
+                             uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const rmcl_fold* fold, const int32_t* replaced,
+                             int64_t mask_token_off, void* stream) {
+  RMCL_REQUIRE(!(mode & RMCL_MODE_CLS_TAIL), "encoder_forward_mpp: no cls-only tail (the loss reads the image rows)");
+  RMCL_REQUIRE(!replaced || (d && mask_token_off >= 0 && mask_token_off % 4 == 0), "encoder_forward_mpp: bad mask_token offset");
+  return encoder_forward_impl(d, mode, params32, params_lp, text_ids, text_mask, patches, co_mask, stash, workspace, xn, drop_seed, drop_p,
+                              ragged, fold, nullptr, replaced, mask_token_off, stream);
 }
 
 int rmcl_encoder_forward_rank(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
@@ -585,11 +597,13 @@ int rmcl_encoder_forward_rank(const rmcl_dims* d, int mode, const float* params3
   RMCL_REQUIRE(src->n_img >= 1 && d->P >= 1 && d->P + 1 <= src->ld_tok, "encoder_forward_rank: the cache slots hold fewer than 1 + P token rows");
   RMCL_REQUIRE(d->img_type == 0 || d->img_type == 1, "encoder_forward_rank: image tokens take token-type row 1");
   return encoder_forward_impl(d, mode, params32, params_lp, text_ids, text_mask, nullptr, co_mask, nullptr, workspace, xn, 0u, 0.f, nullptr,
-                              fold, src, stream);
+                              fold, src, nullptr, 0, stream);
 }
 
-int rmcl_visual_embed(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
-                      void* workspace, float* out, int32_t* masks, void* stream) {
+}  // extern "C"
+
+static int visual_embed_impl(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
+                             void* workspace, float* out, int32_t* masks, const int32_t* replaced, int64_t mask_token_off, void* stream) {
   RMCL_TRY(check_dims(d));
   RMCL_REQUIRE(params32 && patches && workspace && out && masks, "visual_embed: NULL argument");
   RMCL_REQUIRE(!ragged || (ragged->sel && ragged->counts && ragged->hw && ragged->pos_tok), "visual_embed: incomplete rmcl_ragged");
@@ -606,6 +620,7 @@ int rmcl_visual_embed(const rmcl_dims* d, const float* params32, const void* par
     g.epi = EPI_BIAS; g.bias = c.V(y.patch_b); g.tag = GEMM_TAG_PATCH;
     RMCL_TRY(gemm(c, g, d->dtype, RMCL_F32, 1, 1));
   }
+  if (replaced) RMCL_TRY(rmcl_mask_token_fwd(w.pe, replaced, c.V(mask_token_off), B * P, D, c.s));
   if (ragged) {
     RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
                                  ragged->pos_tok, c.s));
@@ -616,10 +631,27 @@ int rmcl_visual_embed(const rmcl_dims* d, const float* params32, const void* par
   return 0;
 }
 
-int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
-                          const void* patches, const int32_t* co_mask, void* stash, void* workspace, const float* dxn,
-                          int cls_only, void* dpatches, float* dtext, float* G, uint32_t drop_seed, float drop_p,
-                          const rmcl_ragged* ragged, const void* params_lpT, void* stream) {
+extern "C" {
+
+int rmcl_visual_embed(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
+                      void* workspace, float* out, int32_t* masks, void* stream) {
+  return visual_embed_impl(d, params32, params_lp, patches, ragged, workspace, out, masks, nullptr, 0, stream);
+}
+
+int rmcl_visual_embed_mpp(const rmcl_dims* d, const float* params32, const void* params_lp, const void* patches, const rmcl_ragged* ragged,
+                          void* workspace, float* out, int32_t* masks, const int32_t* replaced, int64_t mask_token_off, void* stream) {
+  RMCL_REQUIRE(!replaced || (mask_token_off >= 0 && mask_token_off % 4 == 0), "visual_embed_mpp: bad mask_token offset");
+  return visual_embed_impl(d, params32, params_lp, patches, ragged, workspace, out, masks, replaced, mask_token_off, stream);
+}
+
+}  // extern "C"
+
+// replaced != NULL: the forward substituted the mask token (rmcl_encoder_backward_mpp)
+static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                                 const void* patches, const int32_t* co_mask, void* stash, void* workspace, const float* dxn,
+                                 int cls_only, void* dpatches, float* dtext, float* G, uint32_t drop_seed, float drop_p,
+                                 const rmcl_ragged* ragged, const void* params_lpT, const int32_t* replaced, int64_t mask_token_off,
+                                 void* stream) {
   RMCL_TRY(check_dims(d));
   const bool streamed = stream_attn(*d, mode);
   mode &= ~RMCL_MODE_STREAM_ATTN;
@@ -901,6 +933,11 @@ int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, c
                                    full ? Gp(y.vtype) + (d->img_type == 2 ? 2 : 1) * D : nullptr, B, P, L, N, D,
                                    rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, (ragged && full) ? ragged->dpos_tok : nullptr,
                                    d->img_type == -1 ? 1 : 0, s));
+  // the replaced patches' gradient goes to the mask token; their dpe rows are zeroed BEFORE dpatches, the patch-weight gradient and the
+  // patch-bias column sum read them
+  if (replaced)
+    RMCL_TRY(rmcl_mask_token_bwd(w.dx, w.dpe, dt, replaced, full ? Gp(mask_token_off) : nullptr, w.dln /* free until the text rows */, B, P, L, N, D,
+                                 rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, s));
   if (ragged && full)                                          // position-table gradient through the per-sample resize
     RMCL_TRY(rmcl_pos_resize_bwd(ragged->dpos_tok, ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
                                  Gp(y.pos_img), s));
@@ -924,6 +961,25 @@ int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, c
     if (full) RMCL_TRY(rmcl_text_embed_scatter((const long*)text_ids, de, Gp(y.word), Gp(y.pos), Gp(y.btype), B, L, D, 0, s));
   }
   return 0;
+}
+
+extern "C" {
+
+int rmcl_encoder_backward(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                          const void* patches, const int32_t* co_mask, void* stash, void* workspace, const float* dxn,
+                          int cls_only, void* dpatches, float* dtext, float* G, uint32_t drop_seed, float drop_p,
+                          const rmcl_ragged* ragged, const void* params_lpT, void* stream) {
+  return encoder_backward_impl(d, mode, params32, params_lp, text_ids, patches, co_mask, stash, workspace, dxn, cls_only, dpatches, dtext, G,
+                               drop_seed, drop_p, ragged, params_lpT, nullptr, 0, stream);
+}
+
+int rmcl_encoder_backward_mpp(const rmcl_dims* d, int mode, const float* params32, const void* params_lp, const int64_t* text_ids,
+                              const void* patches, const int32_t* co_mask, void* stash, void* workspace, const float* dxn, void* dpatches,
+                              float* dtext, float* G, uint32_t drop_seed, float drop_p, const rmcl_ragged* ragged, const void* params_lpT,
+                              const int32_t* replaced, int64_t mask_token_off, void* stream) {
+  RMCL_REQUIRE(!replaced || (mask_token_off >= 0 && mask_token_off % 4 == 0), "encoder_backward_mpp: bad mask_token offset");
+  return encoder_backward_impl(d, mode, params32, params_lp, text_ids, patches, co_mask, stash, workspace, dxn, 0, dpatches, dtext, G,
+                               drop_seed, drop_p, ragged, params_lpT, replaced, mask_token_off, stream);
 }
 
 }  // extern "C"

@@ -110,6 +110,13 @@ int rmcl_image_assemble_fwd(const float* pe, const float* cls, const float* pos,
                             int L, int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, int pos_per_sample, int pair, hipStream_t s);
 int rmcl_image_assemble_bwd(const float* dx, void* dpe, int dt, float* dpos, float* dcls, float* dvtype1, int B, int P, int L,
                             int N, int D, uint32_t dseed, uint32_t dthresh, float dinv, float* dpos_tok, int pair, hipStream_t s);
+// masked patch prediction (vision_transformer.py:525-557 `feats[replaced] = mask_token`): pe[r] = mask_token where replaced[r] != 0, r < rows
+int rmcl_mask_token_fwd(float* pe, const int* replaced, const float* mask_token, int rows, int D, hipStream_t s);
+// its backward, after rmcl_image_assemble_bwd: dmask_token[c] (optional) += the sum over the replaced rows of the gradient arriving at that
+// patch-embedding row (dx with the image-token dropout mask, fp32) - per sample in ascending slot order into part [B, D] (scratch), then
+// the samples in ascending order - and the dpe rows of replaced patches are ZEROED
+int rmcl_mask_token_bwd(const float* dx, void* dpe, int dt, const int* replaced, float* dmask_token, float* part, int B, int P, int L, int N,
+                        int D, uint32_t dseed, uint32_t dthresh, float dinv, hipStream_t s);
 int rmcl_weight_transpose(const unsigned short* src, unsigned short* dst, long layer0, long stride, int layers, const long* offs, const int* rows,
                           const int* cols, hipStream_t s);
 int rmcl_patch_select(const float* img, int B, int C, int Hh, int Ww, int ps, int* sel, int* counts, int* hw, hipStream_t s);

@@ -238,6 +238,47 @@ class MlmBuffers:
         self.labels = None                                      # the bound [B, L] int64 labels on the device
 
 
+def mpp_layout(cfg: dict, base: int):
+    """transformer.mask_token (vision_transformer.py: nn.Parameter(zeros(1, 1, D))) and mpp_score (heads.MPPHead, heads.py:198-207:
+    BertPredictionHeadTransform + Linear(D, 768)) appended to the parameter arena at element offset `base`: returns (rmcl_mpp_head
+    struct, specs, elements used)."""
+    D = int(cfg["hidden_size"])
+    n = "mpp_score."
+    offs, specs, used = _pack(base, [("mt", "transformer.mask_token", (1, 1, D), None),
+                                     ("tw", n + "transform.dense.weight", (D, D), None), ("tb", n + "transform.dense.bias", (D,), None),
+                                     ("lg", n + "transform.LayerNorm.weight", (D,), None), ("lb", n + "transform.LayerNorm.bias", (D,), None),
+                                     ("dw", n + "decoder.weight", (768, D), None), ("db", n + "decoder.bias", (768,), None)])
+    return L.MppHead(D=D, reserved=0, **offs), specs, used
+
+
+def mpp_draw_masks(B: int, G: int):
+    """The two mask draws of VisionTransformer.mask_tokens (vision_transformer.py:547-554) over the full patch grid [B, G], on torch's
+    global CPU generator and in the reference's order: masked ~ Bernoulli(0.15), then replaced = Bernoulli(0.8) & masked.  Under the same
+    torch.manual_seed the draws coincide with the reference's.  Returns two bool tensors on the host."""
+    masked = torch.bernoulli(torch.full((B, G), 0.15)).bool()
+    replaced = torch.bernoulli(torch.full((B, G), 0.8)).bool() & masked
+    return masked, replaced
+
+
+class MppBuffers:
+    """Per-(batch, tag, image length) buffers of the MPP head for B x P image slots: the slot labels, the masks gathered through the
+    batch's patch selection, the compaction (row list, labels, device-side counts), the per-row outputs and the workspace the forward
+    leaves for the backward.  ``rows``: launch extent for the bound batch (a multiple of 128 >= the host-known number of masked slots)."""
+
+    def __init__(self, eng: "Engine", B: int, Pn: int):
+        dev = eng.device
+        self.B, self.P = B, Pn
+        self.cap = (B * (Pn + 1) + 127) // 128 * 128            # (all image rows, the cls rows included: the dense-logits pass)
+        i32 = lambda *n: torch.empty(*n, dtype=torch.int32, device=dev)
+        f32 = lambda *n: torch.empty(*n, dtype=torch.float32, device=dev)
+        self.labels = i32(B, Pn, 3)
+        self.idx, self.lab, self.count = i32(self.cap), i32(self.cap, 3), i32(2)
+        self.lse, self.rowloss, self.argmax = f32(self.cap, 3), f32(self.cap), i32(self.cap, 3)
+        self.ws = f32(int(lib.rmcl_mpp_ws_floats(C.byref(eng.mpp), self.cap)))
+        self.rows = self.cap
+        self.masked = self.replaced = None                      # [B, P] int32 on the device, of the bound batch
+
+
 class PassBuffers:
     """Everything sized by the per-GPU batch B (allocated once, reused every step)."""
 
@@ -385,11 +426,13 @@ class Engine:
         #   nlvr2 NLVR2 classifier (loss_names["nlvr2"] / ["nlvr2_attacked"] > 0); the 3-row token-type table of these models is part
         #         of the C layout (rmcl_dims.n_types = 3, make_dims)
         #   mlm   MLM head (loss_names["mlm"] > 0)
+        #   mpp   transformer.mask_token + MPP head (loss_names["mpp"] > 0)
         ln = cfg.get("loss_names", {})
         extra = 0
         for attr, present, layout_of in (("bt", ln.get("barlowtwins", 0) > 0, bt_layout),
                                          ("vqa", ln.get("vqa", 0) > 0 or ln.get("vqa_attacked", 0) > 0, vqa_layout),
-                                         ("nlvr2", is_nlvr2(cfg), nlvr2_layout), ("mlm", ln.get("mlm", 0) > 0, mlm_layout)):
+                                         ("nlvr2", is_nlvr2(cfg), nlvr2_layout), ("mlm", ln.get("mlm", 0) > 0, mlm_layout),
+                                         ("mpp", ln.get("mpp", 0) > 0, mpp_layout)):
             head, specs, used = layout_of(cfg, int(lay.total) + extra) if present else (None, [], 0)
             setattr(self, attr, head)
             setattr(self, attr + "_specs", specs)
@@ -428,7 +471,7 @@ class Engine:
         # transposed bf16 shadows of the layer weights for the data-gradient GEMMs (include/rmcl.h rmcl_weight_transpose_bf16)
         self.q_lpT = z(lay.total, torch.bfloat16) if (self.dtype == L.BF16 and os.environ.get("RMCL_NO_WT", "0") != "1") else None
         self.lpT_stale = True
-        self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs + self.nlvr2_specs + self.mlm_specs
+        self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs + self.nlvr2_specs + self.mlm_specs + self.mpp_specs
         self._bufs: Dict[tuple, PassBuffers] = {}
         self.lp_stale = True
         self.drop_p = float(cfg.get("drop_rate", 0.0))
@@ -794,8 +837,10 @@ class Engine:
         """RMCL_MODE_STREAM_ATTN for a pass of more than 256 tokens on an engine built with long_sequences, else 0."""
         return L.MODE_STREAM_ATTN if (self.long_sequences and d.L + 1 + d.P > 256) else 0
 
-    def encoder_forward(self, pb: PassBuffers, key: bool, mode: int, patchesT: torch.Tensor, cls_tail: bool = False):
-        """cls_tail: the caller reads only the cls row of every sample of pb.xn (the contrastive objectives: pooler -> head); the
+    def encoder_forward(self, pb: PassBuffers, key: bool, mode: int, patchesT: torch.Tensor, cls_tail: bool = False,
+                        replaced: torch.Tensor = None):
+        """replaced [B, P] int32 (MPP): the pass of rmcl_encoder_forward_mpp - the mask token takes the place of those patch embeddings.
+        cls_tail: the caller reads only the cls row of every sample of pb.xn (the contrastive objectives: pooler -> head); the
         last block then runs its row-wise part on B rows (include/rmcl.h RMCL_MODE_CLS_TAIL).  Remembered per (buffers, mode):
         the matching encoder_backward picks the compact form by itself.  Under dropout the compact rows draw the masks of the dense
         rows they stand for (csrc/gemm.h drop_row_mul): the tail gives the dense block's numbers there too."""
@@ -813,6 +858,14 @@ class Engine:
             self.pass_log.append({"seed": seed, "p": p, "mode": mode, "key": bool(key), "B": pb.B, "lane": getattr(pb, "lane", None), "tail": tail})
         p32, plp = (self.k32, self.k_lp) if key else (self.q32, self.q_lp)
         stash = {L.MODE_INFER: None, L.MODE_DATA: pb.stash_data, L.MODE_FULL: pb.stash_full}[mode]
+        if replaced is not None:
+            if key or tail or self.mpp is None:
+                raise L.RmclError("encoder_forward(replaced=...): the MPP pass runs on the query arena of a model with the mpp head, without the cls-only tail")
+            check(lib.rmcl_encoder_forward_mpp(C.byref(pb.d), mode | self.stream_bit(pb.d), P(p32), P(plp), P(pb.text_ids), P(pb.text_mask), P(patchesT),
+                                               P(pb.co_mask), P(stash), P(pb.workspace), P(pb.xn), C.c_uint32(seed), F(p), self._rg(pb),
+                                               self.fold_of(key) if (mode != L.MODE_FULL and pb.dtype == L.BF16) else None, P(replaced),
+                                               I64(self.mpp.mt), stream_ptr()), "encoder_forward_mpp")
+            return
         check(lib.rmcl_encoder_forward(C.byref(pb.d), mode | (L.MODE_CLS_TAIL if tail else 0) | self.stream_bit(pb.d), P(p32), P(plp), P(pb.text_ids), P(pb.text_mask), P(patchesT),
                                        P(pb.co_mask), P(stash), P(pb.workspace), P(pb.xn), C.c_uint32(seed), F(p), self._rg(pb),
                                        self.fold_of(key) if (mode != L.MODE_FULL and pb.dtype == L.BF16) else None, stream_ptr()),
@@ -866,9 +919,18 @@ class Engine:
                                       P(pb.dcls), P(self.g32 if with_grads else None), P(pb.workspace), stream_ptr()),
               "heads_backward")
 
-    def encoder_backward(self, pb: PassBuffers, mode: int, patchesT, dxn, cls_only: bool, dpatches, dtext=None):
+    def encoder_backward(self, pb: PassBuffers, mode: int, patchesT, dxn, cls_only: bool, dpatches, dtext=None, replaced: torch.Tensor = None):
         stash = pb.stash_data if mode == L.MODE_DATA else pb.stash_full
         seed, p = pb.drop[mode]
+        if replaced is not None:                                       # the backward of an encoder_forward(replaced=...) pass (full-row dxn)
+            if cls_only or self.mpp is None:
+                raise L.RmclError("encoder_backward(replaced=...): the MPP pass takes a full-row gradient on a model with the mpp head")
+            check(lib.rmcl_encoder_backward_mpp(C.byref(pb.d), mode | self.stream_bit(pb.d), P(self.q32), P(self.q_lp), P(pb.text_ids), P(patchesT),
+                                                P(pb.co_mask), P(stash), P(pb.workspace), P(dxn), P(dpatches), P(dtext),
+                                                P(self.g32 if mode == L.MODE_FULL else None), C.c_uint32(seed), F(p), self._rg(pb),
+                                                P(self.weights_T() if pb.dtype == L.BF16 else None), P(replaced), I64(self.mpp.mt), stream_ptr()),
+                  "encoder_backward_mpp")
+            return
         co = (2 if pb.tail.get(mode) else 1) if cls_only else 0
         if pb.tail.get(mode) and not cls_only:
             raise L.RmclError("encoder_backward: the forward of these buffers kept only the cls rows (cls_tail) - a full-row gradient has nowhere to go")
@@ -1109,6 +1171,75 @@ class Engine:
                                   stream_ptr()), "mlm_logits")
         return out
 
+    # ---- MPP head (include/rmcl.h rmcl_mpp_*) ------------------------------------------------------------------------
+    def mpp_bufs(self, B: int, tag: str, Pn: int) -> MppBuffers:
+        key = (MppBuffers, B, tag, Pn)
+        if key not in self._head_bufs:
+            self._head_bufs[key] = MppBuffers(self, B, Pn)
+        return self._head_bufs[key]
+
+    def mpp_bind(self, mp: MppBuffers, img: torch.Tensor, pb: PassBuffers, masked: torch.Tensor, replaced: torch.Tensor,
+                 all_rows: bool = False) -> MppBuffers:
+        """Labels of the batch's image slots from the float image `img` [B, 3, H, W] (on the device), the two full-grid masks [B, G]
+        gathered through `pb`'s patch selection into [B, P] (pad slots: 0), and the compaction of the masked valid slots.  The launch
+        extent comes from the host-known number of masked patches; n stays on the device.  A pixel mean outside [0, 1] (pixels outside
+        [-1, 1]) is a ValueError, like the reference's cross_entropy raising on a label outside 0..255."""
+        B, _, Hh, Ww = img.shape
+        ps = int(self.cfg["patch_size"])
+        if ps != 32:
+            raise NotImplementedError("MPP labels are built for patch_size = 32")
+        G = (Hh // ps) * (Ww // ps)
+        if tuple(masked.shape) != (B, G) or tuple(replaced.shape) != (B, G):
+            raise ValueError(f"mpp masks must be [B, G] = {(B, G)} over the full patch grid (got {tuple(masked.shape)}, {tuple(replaced.shape)})")
+        d, geom = pb.d, pb.geom
+        Pn = d.P
+        n_host = int(masked.sum()) if masked.device.type == "cpu" else B * Pn
+        mk = masked.to(self.device).to(torch.int32)
+        rp = (replaced.to(self.device) & masked.to(self.device)).to(torch.int32) if replaced.dtype == torch.bool else replaced.to(self.device, torch.int32) * mk
+        if geom is None:
+            check(lib.rmcl_mpp_labels(P(img), B, Hh, Ww, None, None, 0, Ww // ps, Pn, P(mp.labels), stream_ptr()), "mpp_labels")
+            mp.masked, mp.replaced = mk.contiguous(), rp.contiguous()
+        else:
+            check(lib.rmcl_mpp_labels(P(img), B, Hh, Ww, P(geom.sel), P(geom.counts), geom.sel.shape[1], geom.gw, Pn, P(mp.labels), stream_ptr()),
+                  "mpp_labels")
+            sel = geom.sel[:, :Pn].to(torch.int64).clamp_(0, G - 1)
+            valid = (torch.arange(Pn, device=self.device)[None, :] < geom.counts[:, None]).to(torch.int32)
+            mp.masked = (torch.gather(mk, 1, sel) * valid).contiguous()
+            mp.replaced = (torch.gather(rp, 1, sel) * valid).contiguous()
+        mp.rows = mp.cap if all_rows else min(mp.cap, max(128, (min(n_host, B * Pn) + 127) // 128 * 128))
+        N = d.L + 1 + d.P
+        check(lib.rmcl_mpp_compact(P(mp.labels), P(mp.masked), B, Pn, d.L, N, int(all_rows), mp.cap, P(mp.idx), P(mp.lab), P(mp.count), stream_ptr()),
+              "mpp_compact")
+        return mp
+
+    def mpp_check_labels(self, mp: MppBuffers):
+        """count[1] of the compaction: label entries outside 0..255 (one read-back of two ints)"""
+        n_bad = int(mp.count.tolist()[1])
+        if n_bad:
+            raise ValueError(f"mpp: {n_bad} patch label(s) outside 0..255 - the pixels of `image` must lie in [-1, 1] (the labels are "
+                             "trunc(mean(image * 0.5 + 0.5) * 255) per patch and channel)")
+
+    def mpp_forward(self, mp: MppBuffers, xn: torch.Tensor, stats: torch.Tensor = None) -> torch.Tensor:
+        """stats = (mpp_loss, correct (row, channel) pairs, labelled pairs) of the bound batch; per listed row mp.lse / .rowloss / .argmax."""
+        if self.lp_stale:
+            self.refresh_shadows()
+        stats = torch.empty(3, dtype=torch.float32, device=self.device) if stats is None else stats
+        check(lib.rmcl_mpp_forward(C.byref(self.mpp), P(self.q32), P(self.q_lp), self.dtype, P(xn), P(mp.idx), P(mp.lab), P(mp.count), mp.rows,
+                                   P(mp.ws), P(mp.lse), P(mp.rowloss), P(mp.argmax), P(stats), stream_ptr()), "mpp_forward")
+        return stats
+
+    def mpp_backward(self, mp: MppBuffers, grad_scale: float, scale_dev: torch.Tensor, dxn: torch.Tensor, with_grads: bool = True):
+        """CE gradient -> decoder -> transform -> stored into the zero-filled dxn [B N, D]; head gradients into the arena."""
+        check(lib.rmcl_mpp_backward(C.byref(self.mpp), P(self.q32), P(self.q_lp), self.dtype, P(mp.idx), P(mp.lab), P(mp.count), mp.rows,
+                                    P(mp.ws), P(mp.lse), F(grad_scale), P(scale_dev), P(self.g32 if with_grads else None), P(dxn),
+                                    stream_ptr()), "mpp_backward")
+
+    def mpp_logits(self, mp: MppBuffers, rows_out: int) -> torch.Tensor:
+        """dense logits [rows_out, 768] of the first rows_out listed rows of the last mpp_forward on `mp`"""
+        out = torch.empty(rows_out, 768, dtype=torch.float32, device=self.device)
+        check(lib.rmcl_mpp_logits(C.byref(self.mpp), P(mp.ws), mp.rows, rows_out, P(out), stream_ptr()), "mpp_logits")
+        return out
+
     # ---- IRTR: rank head, visual_embed, the cached rank pass (include/rmcl.h "Image-text retrieval") ------------------------------------
     def rank_params(self, arena: torch.Tensor = None):
         """(weight [D], bias [1]) of rank_output = row 1 of the ITM head's slots, in `arena` (default: the parameters)."""
@@ -1164,7 +1295,7 @@ class Engine:
         mil = self.cfg.get("max_image_len", -1) if max_image_len is None else max_image_len
         return min(n, mil) if isinstance(mil, int) and mil > 0 else n
 
-    def visual_embed(self, images: torch.Tensor, max_image_len=None, select: torch.Tensor = None):
+    def visual_embed(self, images: torch.Tensor, max_image_len=None, select: torch.Tensor = None, mpp_masks=None):
         """VisionTransformer.visual_embed (vision_transformer.py:559-677, mask_it=False): (embeds [B, 1 + n, D] f32 WITHOUT the token-type
         row, masks [B, 1 + n] int64, patch_index [B, n, 2]).  The 256-token limit does not apply here (the pass has no text): the rank pass
         checks; with long_sequences an image that cannot fit 512 tokens with its text is refused here already.
@@ -1200,6 +1331,14 @@ class Engine:
             check(lib.rmcl_add_cast_f32(P(pat32), None, None, P(op), self.dtype, I64(pat32.numel()), stream_ptr()), "add_cast")
         out = torch.empty(B, n + 1, d.D, dtype=torch.float32, device=self.device)
         masks = torch.empty(B, n + 1, dtype=torch.int32, device=self.device)
+        if mpp_masks is not None:
+            # visual_embed(mask_it=True): the full-grid masks (masked, replaced) [B, G] go through mpp_bind like compute_mpp's - labels of
+            # this call's slots, masks gathered through its selection - and the MppBuffers come back as the fourth value
+            import types
+            mp = self.mpp_bind(self.mpp_bufs(B, "visual_embed", n), img, types.SimpleNamespace(d=d, geom=geom), mpp_masks[0], mpp_masks[1])
+            check(lib.rmcl_visual_embed_mpp(C.byref(d), P(self.q32), P(self.q_lp), P(op), C.byref(rg) if rg is not None else None, P(ws), P(out),
+                                            P(masks), P(mp.replaced), I64(self.mpp.mt), stream_ptr()), "visual_embed_mpp")
+            return out, masks.to(torch.int64), patch_index, mp
         check(lib.rmcl_visual_embed(C.byref(d), P(self.q32), P(self.q_lp), P(op), C.byref(rg) if rg is not None else None, P(ws), P(out),
                                     P(masks), stream_ptr()), "visual_embed")
         return out, masks.to(torch.int64), patch_index

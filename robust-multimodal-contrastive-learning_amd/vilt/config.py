@@ -182,6 +182,16 @@ def task_mlm_itm(**over):
     return cfg
 
 
+def task_mlm_itm_mpp(**over):
+    """reference config.py:223-230: ViLT pre-training with masked patch prediction on top of MLM and ITM."""
+    cfg = default_config(
+        exp_name="mlm_itm_mpp", datasets=["coco", "vg", "sbu", "gcc"], loss_names=_loss_names({"itm": 1, "mlm": 1, "mpp": 1}),
+        batch_size=4096, max_epoch=10, max_image_len=200,
+    )
+    cfg.update(over)
+    return cfg
+
+
 def task_mlm_itm_randaug(**over):
     """reference config.py:212-220 (the RandAugment train transform itself is the caller's)."""
     cfg = default_config(

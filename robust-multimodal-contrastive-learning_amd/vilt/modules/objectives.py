@@ -244,6 +244,89 @@ def compute_mlm(pl_module, batch):
     return ret
 
 
+def _mpp_pass(pl_module, batch, text_ids, tag, mode):
+    """The masked-image encoder pass shared by compute_mpp and infer(mask_image=True): the float image on the device, the two mask draws
+    (batch["mpp_masked"] / ["mpp_replaced"] [B, G] bool replace them) BEFORE the patch selection's own draws - the reference's order
+    (vision_transformer.py:602-603 before :632-645) -, the labels and the compaction, then the encoder forward with the mask-token
+    substitution.  Returns (pb, mp, op, img)."""
+    from ...runtime import mpp_draw_masks
+    eng = pl_module.engine
+    if eng.mpp is None:
+        raise NotImplementedError("MPP masking (mask_image=True / compute_mpp) needs a model built with loss_names['mpp'] > 0 "
+                                  "(transformer.mask_token and the mpp_score head)")
+    image = batch["image"][0]
+    if not torch.is_tensor(image):
+        raise NotImplementedError("the MPP pass reads its labels from the float image: Uint8Batch / RawUint8Batch feeds are not built for it")
+    img = image.to(eng.device, torch.float32).contiguous()
+    B, _, Hh, Ww = img.shape
+    ps = int(pl_module.hparams.config["patch_size"])
+    G = (Hh // ps) * (Ww // ps)
+    if "mpp_masked" in batch and "mpp_replaced" in batch:
+        masked, replaced = batch["mpp_masked"].bool(), batch["mpp_replaced"].bool()
+    else:
+        masked, replaced = mpp_draw_masks(B, G)
+    pb = eng.bind_batch(text_ids, batch["text_masks"], img, tag=tag)
+    mp = eng.mpp_bind(eng.mpp_bufs(pb.B, tag, pb.d.P), img, pb, masked, replaced)
+    eng.mpp_check_labels(mp)
+    op = eng.make_operand(pb, out=pb.patchesT_full)
+    eng.encoder_forward(pb, key=False, mode=mode, patchesT=op, replaced=mp.replaced)
+    return pb, mp, op, img
+
+
+def mpp_image_labels(mp) -> torch.Tensor:
+    """image_labels [B, 1 + P, 3] int64 with the reference's meaning (vision_transformer.py:549, 653-659): the label of every masked
+    valid slot, -100 everywhere else and in the prepended cls row."""
+    lab = torch.where(mp.masked.bool().unsqueeze(-1), mp.labels, torch.full_like(mp.labels, -100)).to(torch.int64)
+    return torch.cat([torch.full((mp.B, 1, 3), -100, dtype=torch.int64, device=lab.device), lab], dim=1)
+
+
+def compute_mpp(pl_module, batch):
+    """objectives.compute_mpp (:632-665): one FULL-mode encoder pass with masked patches (no cls-only tail: the loss reads image rows),
+    then mpp_score and three 256-way cross-entropies per masked valid slot - on those rows only, compacted (csrc/mpp.hip).
+    ``mpp_logits`` [B, 1 + P, 3, 256] is the dense tensor when config["mpp_return_logits"] is true or the call runs under no_grad in
+    eval mode, else None (INTEGRATION.md "MPP")."""
+    eng = pl_module.engine
+    cfg = pl_module.hparams.config
+    need_grad = torch.is_grad_enabled() and pl_module.training
+    pb, mp, op, img = _mpp_pass(pl_module, batch, batch["text_ids"], "mpp", L.MODE_FULL if need_grad else L.MODE_INFER)
+    d = pb.d
+    N = d.L + 1 + d.P
+    stats = eng.mpp_forward(mp, pb.xn)                                      # (loss, correct pairs, labelled pairs), all on the device
+    value = _scalar(stats[0:1].clone())
+    if need_grad:
+        def backward(grad_out, pb=pb, mp=mp, op=op, N=N):
+            g = grad_out.to(torch.float32).reshape(1).contiguous()
+            dxn = torch.zeros(pb.B * N, pb.d.D, dtype=torch.float32, device=eng.device)
+            eng.mpp_backward(mp, 1.0, g, dxn, with_grads=True)
+            eng.encoder_backward(pb, L.MODE_FULL, op, dxn, cls_only=False, dpatches=None, replaced=mp.replaced)
+            pl_module.after_backward()
+
+        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+    labels = mpp_image_labels(mp)
+    logits = None
+    if cfg.get("mpp_return_logits", False) or not (torch.is_grad_enabled() or pl_module.training):
+        ma = eng.mpp_bufs(pb.B, "mpp_dense", d.P)
+        ma.labels.copy_(mp.labels)
+        ma.masked, ma.replaced = mp.masked, mp.replaced
+        ma.rows = ma.cap
+        check(lib.rmcl_mpp_compact(P(ma.labels), P(ma.masked), pb.B, d.P, d.L, N, 1, ma.cap, P(ma.idx), P(ma.lab), P(ma.count), stream_ptr()),
+              "mpp_compact")
+        eng.mpp_forward(ma, pb.xn)
+        logits = eng.mpp_logits(ma, pb.B * (d.P + 1)).view(pb.B, d.P + 1, 3, 256)
+    ret = {"mpp_loss": value, "mpp_logits": logits, "mpp_labels": labels}
+    phase = "train" if pl_module.training else "val"
+    # Accuracy (gadgets/my_metrics.py:5-28): correct / total over the labelled (row, channel) pairs, per step and over the epoch
+    acc = getattr(pl_module, "mpp_epoch_counts", None)
+    if acc is None:
+        acc = pl_module.mpp_epoch_counts = {}
+    if phase not in acc:
+        acc[phase] = torch.zeros(2, dtype=torch.float32, device=eng.device)
+    acc[phase] += stats[1:3]
+    pl_module.log(f"mpp/{phase}/loss", value.detach())
+    pl_module.log(f"mpp/{phase}/accuracy", stats[1] / stats[2])
+    return ret
+
+
 def compute_moco_contrastive(pl_module, batch):
     """objectives.py:217-447 (image view).  Returns {"moco_loss", pos_/neg_{dist,cosine,dot}_attacked_img}."""
     eng = pl_module.engine

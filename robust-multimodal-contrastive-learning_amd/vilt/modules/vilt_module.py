@@ -84,6 +84,9 @@ class ViLTransformerSS(nn.Module):
             # arithmetic an attacked IRTR step (or compute_attacked_irtr_recall / GreedyAttack_irtr) could be pinned to
             raise NotImplementedError("loss_names['irtr_attacked'] > 0: the reference's PGDAttack_irtr.pgd_attack reads the undefined name "
                                       "`text_representation` (attack/pgd_attack_vilt.py:391), so there is nothing to reproduce; use loss_names['irtr']")
+        if config["loss_names"].get("mpp", 0) > 0 and (config["loss_names"].get("moco", 0) > 0 or config["loss_names"].get("barlowtwins", 0) > 0):
+            # the reference names no such recipe; a momentum copy of transformer.mask_token is not built
+            raise NotImplementedError("loss_names['mpp'] > 0 together with 'moco' or 'barlowtwins' is not built (no reference recipe combines them)")
         self.engine = Engine(config, device, compute_dtype, exact, pgd_dtype)
         eng = self.engine
         if config.get("ln_fold") is False:
@@ -270,7 +273,9 @@ class ViLTransformerSS(nn.Module):
                 continue
             leaf = name.split(".")[-1]
             is_ln = any(t in name for t in ("LayerNorm", "norm1", "norm2", "transformer.norm", "projector.1"))
-            if name.startswith(("vqa_classifier.", "nlvr2_classifier.")):
+            if name == "transformer.mask_token":
+                p.zero_()                         # VisionTransformer.__init__ leaves nn.Parameter(torch.zeros(1, 1, D)) as it is
+            elif name.startswith(("vqa_classifier.", "nlvr2_classifier.")):
                 # objectives.init_weights (:1505-1516) applied to the head (vilt_module.py:172, :200): Linear N(0, 0.02) / bias 0, LayerNorm
                 # 1 / 0 (the substring rule below would miss the LayerNorm gain "vqa_classifier.1.weight")
                 if name.startswith(("vqa_classifier.1.", "nlvr2_classifier.1.")):
@@ -375,7 +380,12 @@ class ViLTransformerSS(nn.Module):
     # ---- inference API ---------------------------------------------------------------------
     def _infer(self, batch, key, mask_text, mask_image, image_token_type_idx, image_embeds, image_masks):
         if mask_image:
-            raise NotImplementedError("MPP masking (mask_image=True) is outside the RMCL hot path")
+            if self.engine.mpp is None:
+                raise NotImplementedError("MPP masking (mask_image=True) needs a model built with loss_names['mpp'] > 0")
+            if key or mask_text or image_embeds is not None or image_masks is not None or image_token_type_idx != 1:
+                raise NotImplementedError("infer(mask_image=True) is built for the query pass on pixels alone (not infer_k, mask_text, "
+                                          "image_embeds or another token type)")
+            return self._infer_mpp(batch)
         if image_embeds is not None or image_masks is not None:
             if mask_text:
                 raise NotImplementedError("infer(mask_text=True, image_embeds=...) is not built (the reference never calls it)")
@@ -451,6 +461,21 @@ class ViLTransformerSS(nn.Module):
             ret["text_labels"] = batch.get(f"text_labels{do_mlm}")
         return ret
 
+    def _infer_mpp(self, batch):
+        """infer(batch, mask_image=True) (vilt_module.py:296-306 with mask_it): the pass compute_mpp runs, as an inference call - the features
+        carry no backward (train through compute_mpp / training_step).  image_labels [B, 1 + P, 3] as the reference builds them."""
+        eng = self.engine
+        eng.dropout_on = self.training and eng.drop_p > 0
+        pb, mp, _, _ = objectives._mpp_pass(self, batch, batch["text_ids"], "mpp_infer", L.MODE_INFER)
+        eng.heads_forward(pb, key=False, want_q=False)
+        d = pb.d
+        x = pb.xn.view(pb.B, d.L + 1 + d.P, d.D)
+        return {
+            "text_feats": x[:, : d.L].clone(), "image_feats": x[:, d.L:].clone(), "cls_feats": pb.cls.clone(), "raw_cls_feats": x[:, 0].clone(),
+            "image_labels": objectives.mpp_image_labels(mp), "image_masks": pb.co_mask[:, d.L:].to(torch.int64),
+            "text_labels": batch.get("text_labels"), "text_ids": batch["text_ids"], "text_masks": batch["text_masks"], "patch_index": None,
+        }
+
     def _infer_embeds(self, batch, key, image_token_type_idx, image_embeds, image_masks):
         """infer(batch, image_embeds=..., image_masks=...) (vilt_module.py:296-313): the image tokens are a visual_embed output instead
         of pixels.  Inference only, like every use the reference makes of it (compute_irtr_recall, under no_grad)."""
@@ -490,15 +515,29 @@ class ViLTransformerSS(nn.Module):
         }
 
     @torch.no_grad()
-    def visual_embed(self, images, max_image_len=None, mask_it=False, select=None):
+    def visual_embed(self, images, max_image_len=None, mask_it=False, select=None, mpp_masks=None):
         """VisionTransformer.visual_embed (vision_transformer.py:559-677) as the reference's compute_irtr_recall calls it: patch embedding
         + resized position rows + cls token, WITHOUT the token-type row.  Returns (image_embeds [B, 1 + n, D] fp32, image_masks [B, 1 + n],
         (patch_index, (H, W)), None).  max_image_len None: the config's.  select: the caller's patch draw (parity tests)."""
-        if mask_it:
-            raise NotImplementedError("visual_embed(mask_it=True) (MPP masking) is outside the RMCL hot path")
-        emb, msk, patch_index = self.engine.visual_embed(images, max_image_len=max_image_len, select=select)
+        if mask_it and self.engine.mpp is None:
+            raise NotImplementedError("visual_embed(mask_it=True) (MPP masking) needs a model built with loss_names['mpp'] > 0")
         ps = self.config["patch_size"]
+        if mask_it:
+            return self._visual_embed_mpp(images, max_image_len, select, mpp_masks)
+        emb, msk, patch_index = self.engine.visual_embed(images, max_image_len=max_image_len, select=select)
         return emb, msk, (patch_index, (int(images.shape[2]) // ps, int(images.shape[3]) // ps)), None
+
+    def _visual_embed_mpp(self, images, max_image_len, select, mpp_masks=None):
+        """visual_embed(mask_it=True): the reference's order - the two mask draws (or the caller's `mpp_masks` = (masked, replaced) [B, G]),
+        then the patch selection -, the embeddings with the mask token in place of the replaced patches, and the label [B, 1 + n, 3] as the
+        fourth value.  Labels and masks take the path of compute_mpp (Engine.mpp_bind)."""
+        from ...runtime import mpp_draw_masks
+        eng, ps = self.engine, self.config["patch_size"]
+        img = images.to(eng.device, torch.float32).contiguous()
+        B, _, Hh, Ww = img.shape
+        masks = mpp_masks if mpp_masks is not None else mpp_draw_masks(B, (Hh // ps) * (Ww // ps))
+        emb, msk, patch_index, mp = eng.visual_embed(img, max_image_len=max_image_len, select=select, mpp_masks=masks)
+        return emb, msk, (patch_index, (Hh // ps, Ww // ps)), objectives.mpp_image_labels(mp)
 
     def _infer_slot_take(self) -> int:
         for slot in range(self.MAX_PENDING_INFER):
@@ -528,6 +567,8 @@ class ViLTransformerSS(nn.Module):
             return ret
         if "mlm" in self.current_tasks:                                   # first, like the reference (vilt_module.py:426-436)
             ret.update(objectives.compute_mlm(self, batch))
+        if "mpp" in self.current_tasks:                                   # second, like the reference (vilt_module.py:430-432)
+            ret.update(objectives.compute_mpp(self, batch))
         if "itm" in self.current_tasks:
             ret.update(objectives.compute_itm_wpa(self, batch))
         if "moco" in self.current_tasks:
@@ -544,7 +585,7 @@ class ViLTransformerSS(nn.Module):
             ret.update(objectives.compute_nlvr2_attack(self, batch))
         if "irtr" in self.current_tasks:
             ret.update(objectives.compute_irtr(self, batch))
-        unsupported = [t for t in self.current_tasks if t not in ("mlm", "itm", "moco", "barlowtwins", "vqa", "vqa_attacked", "nlvr2", "nlvr2_attacked", "irtr")]
+        unsupported = [t for t in self.current_tasks if t not in ("mlm", "mpp", "itm", "moco", "barlowtwins", "vqa", "vqa_attacked", "nlvr2", "nlvr2_attacked", "irtr")]
         if unsupported:
             raise NotImplementedError(f"tasks {unsupported} are outside the RMCL hot path (SURVEY 8)")
         return ret

@@ -36,6 +36,10 @@ def epoch_wrapup(pl_module):
         # the epoch value of the reference's Accuracy metric: correct / total over every labelled row seen this epoch, then reset
         correct, total = counts.tolist()
         out[f"mlm/{phase}/accuracy_epoch"] = correct / total if total else float("nan")
+    counts = getattr(pl_module, "mpp_epoch_counts", {}).pop(phase, None)
+    if counts is not None:
+        correct, total = counts.tolist()                      # (row, channel) pairs with a label seen this epoch
+        out[f"mpp/{phase}/accuracy_epoch"] = correct / total if total else float("nan")
     if pl_module.hparams.config.get("get_recall_metric", False) and not pl_module.training:
         # vilt_utils.py:90-97: image-text retrieval recalls at the end of a validation / test epoch; ir_r1 + tr_r1 joins the_metric.
         # The datasets come from pl_module.irtr_eval_dsets = (text_dset, image_dset) when set, else from the trainer's datamodule
