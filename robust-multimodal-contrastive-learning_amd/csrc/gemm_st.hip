@@ -107,13 +107,23 @@ struct STCtx {
   int wave;
 };
 
+// residual through LDS (gemm_st_epi.h, RESL): what st_tile needs to stage a residual chunk in place of an operand tile
+struct STRes {
+  const GemmArgs& g;
+  int m0, n0, lane;
+};
+
 // MODE 0: steady state (stage tile t+2, vmcnt(6)); 1: second-to-last tile (no stage, vmcnt(0)); 2: last tile (no stage, no wait)
+// RES (MODE 1 / 2, PH = 2): the stage `nxt2` that has no operand tile to take any more - (t+2) % 3 in MODE 1, the stage of the second-to-last
+// k-tile in MODE 2 - takes residual chunk MODE - 1 instead: three LDS-DMA per wave and phase, issued where MODE 0 issues its operand halves
+// (that stage's last reads lie one phase back, as in steady state).  MODE 1 then waits vmcnt(6): the last k-tile has landed, the chunk flies on.
 // PH = 2: one phase per k-step (18 MFMA between barriers); PH = 1: ONE phase per k-tile - both k-steps' fragments are read
 // up front (72 fragment registers) and 36 MFMAs run between barriers, halving the barrier / role-switch overhead per FLOP.
 // With PH = 1 the DMA into stage (t+2)%3 is issued one phase after that stage's last ds_reads, so those reads are retired
 // (lgkmcnt(0)) BEFORE the phase's first barrier rather than after it.
-template <int MODE, bool A_KC, bool B_KC, int PH>
-__device__ __forceinline__ void st_tile(f32x4 (&acc)[6][3], const STCtx& c, const char* cur, char* nxt2, int t2) {
+template <int MODE, bool A_KC, bool B_KC, int PH, bool RES = false>
+__device__ __forceinline__ void st_tile(f32x4 (&acc)[6][3], const STCtx& c, const char* cur, char* nxt2, int t2, const STRes* rx = nullptr) {
+  static_assert(!RES || (PH == 2 && MODE != 0), "residual staging: the last two k-tiles of the two-phase form");
   if constexpr (PH == 2) {
     bf16x8 a[6], b[3];
 #pragma unroll
@@ -127,6 +137,10 @@ __device__ __forceinline__ void st_tile(f32x4 (&acc)[6][3], const STCtx& c, cons
         // reads, which is why those reads are retired before the barrier below
         if (s == 0) st_stage_op(c.A, c.oa, (long)t2 * c.kstep_a, nxt2, c.wave);
         else { st_stage_op(c.B, c.ob, (long)t2 * c.kstep_b, nxt2 + ST_OP_BYTES, c.wave); st_wait_vm<6>(); }
+      } else if constexpr (RES) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) st_stage_res(rx->g, rx->m0, rx->n0, MODE - 1, s * 3 + q, nxt2, c.wave, rx->lane);
+        if (MODE == 1 && s == 1) st_wait_vm<6>();
       } else if (MODE == 1 && s == 1) {
         st_wait_vm<0>();
       }
@@ -278,7 +292,9 @@ __device__ __forceinline__ void st_epilogue(const f32x4 (&acc)[6][3], const Gemm
 }
 
 
-template <bool A_KC, bool B_KC, int AUX, typename TO, bool DROP, int PH, int LNF = 0>
+// RESL: the fp32 residual arrives through LDS during the last two k-tiles (gemm_st_epi.h).  Only for launches in which every workgroup has
+// ONE tile (the launchers check): the stages a streaming workgroup would fill with its next tile's operands are then idle.
+template <bool A_KC, bool B_KC, int AUX, typename TO, bool DROP, int PH, int LNF = 0, bool RESL = false>
 __global__ __launch_bounds__(512) void gemm_st_kernel(GemmArgs g, int tiles_m, int tiles_n, int rows_per_tile, int xflags) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x, lane = t & 63;
@@ -321,6 +337,19 @@ __global__ __launch_bounds__(512) void gemm_st_kernel(GemmArgs g, int tiles_m, i
 #pragma unroll
   for (int q = 0; q < 3; ++q) { c.oa[q] = cur.oa[q]; c.ob[q] = cur.ob[q]; }
 
+  if constexpr (RESL) {
+    // the tile's row centres (LNF = 2) and bias values are parked behind the stages HERE, by LDS-DMA ahead of the operand tiles (the
+    // prologue's vmcnt(6) and barrier publish them): an ordinary load consumed in the epilogue would drain the residual chunks in flight
+    float* park = reinterpret_cast<float*>(smem + ST_LDS);
+    if (LNF == 2 && wave < 3) {
+      if (g.ln_center) __builtin_amdgcn_global_load_lds((glb_void*)(g.ln_center + min(cur.m0 + wave * 64 + lane, g.M - 1)), (lds_void*)(park + wave * 64), 4, 0, 0);
+      else park[wave * 64 + lane] = 0.f;
+    } else if (wave >= 4 && wave < 7) {
+      if (g.epi & EPI_BIAS) __builtin_amdgcn_global_load_lds((glb_void*)(g.bias + cur.n0 + (wave - 4) * 64 + lane), (lds_void*)(park + ST_RES_BIAS + (wave - 4) * 64), 4, 0, 0);
+      else park[ST_RES_BIAS + (wave - 4) * 64 + lane] = 0.f;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
   // prologue: the first two k-tiles of the first work item
   st_stage_op(c.A, c.oa, (long)cur.kt0 * c.kstep_a, smem, wave);
   st_stage_op(c.B, c.ob, (long)cur.kt0 * c.kstep_b, smem + ST_OP_BYTES, wave);
@@ -335,7 +364,7 @@ __global__ __launch_bounds__(512) void gemm_st_kernel(GemmArgs g, int tiles_m, i
   ST_STAMP(1);
   int sc = 0, sn = 2;                                        // LDS stage of the current k-tile / of the k-tile two ahead
   for (int r = 0;; ++r) {
-    const int nid = st_tile_id(bidx, r + 1, G, ntiles);
+    const int nid = RESL ? -1 : st_tile_id(bidx, r + 1, G, ntiles);
     f32x4 acc[6][3];
 #pragma unroll
     for (int i = 0; i < 6; ++i)
@@ -357,6 +386,14 @@ __global__ __launch_bounds__(512) void gemm_st_kernel(GemmArgs g, int tiles_m, i
         sc = sc == 2 ? 0 : sc + 1;
         sn = sn == 2 ? 0 : sn + 1;
       }
+    } else if constexpr (RESL) {
+      int rl = lane;
+      asm volatile("" : "+v"(rl));                             // (the chunks' source addresses are not hoisted into the k-loop)
+      const STRes rx{g, cur.m0, cur.n0, rl};
+      const int s1 = sc;
+      st_tile<1, A_KC, B_KC, PH, true>(acc, c, smem + sc * ST_STAGE, smem + sn * ST_STAGE, 0, &rx);     // chunk 0 -> stage (t + 2) % 3
+      sc = sc == 2 ? 0 : sc + 1;
+      st_tile<2, A_KC, B_KC, PH, true>(acc, c, smem + sc * ST_STAGE, smem + s1 * ST_STAGE, 0, &rx);     // chunk 1 -> the stage just read
     } else {
       st_tile<1, A_KC, B_KC, PH>(acc, c, smem + sc * ST_STAGE, nullptr, 0);
       sc = sc == 2 ? 0 : sc + 1;
@@ -365,8 +402,8 @@ __global__ __launch_bounds__(512) void gemm_st_kernel(GemmArgs g, int tiles_m, i
     ST_STAMP(2);
     // the stage the tile's last k-tile was read from (sc has already moved on when the stream continues): 24 KiB per group
     const int s_free = nid >= 0 ? (sc == 0 ? 2 : sc - 1) : sc;
-    st_epilogue_lds<AUX, TO, DROP, LNF>(acc, g, cur, wm, wn, lane, wave, smem + s_free * ST_STAGE + wm * (ST_STAGE / 2),
-                                        reinterpret_cast<float*>(smem + ST_LDS));
+    st_epilogue_lds<AUX, TO, DROP, LNF, false, RESL>(acc, g, cur, wm, wn, lane, wave, smem + s_free * ST_STAGE + wm * (ST_STAGE / 2),
+                                                     reinterpret_cast<float*>(smem + ST_LDS), s_free);
     if (nid < 0) break;
     cur = nxt;
   }
@@ -575,6 +612,12 @@ double rmcl_gemm_st_fill(const GemmArgs& g, int cus) {
 
 int g_st_reserve_cus = 8;            // CUs left to other kernels (rmcl_tune_set key 1; RCCL channels, side-stream kernels): free at M = 64*185
 int g_st_xflags = 0;                 // experiment switch (rmcl_tune_set key 0, values 61.. -> xflags = value - 60)
+int g_st_res_lds = 1;                // rmcl_tune_set key 14: 0 = the fp32 residual always through registers (A/B, bit-comparison tests)
+
+// residual through LDS: fp32 residual producers with a PLAIN epilogue, and only when no workgroup walks a second tile
+static bool st_res_lds_ok(const GemmArgs& g, int items, int grid) {
+  return g_st_res_lds != 0 && items <= grid && g.aux && g.splitk <= 1 && !(g.epi & (EPI_GELU | EPI_SAVE_PREACT | EPI_ACCUM));
+}
 
 static int st_num_cus() {
   static int n = 0;
@@ -600,6 +643,15 @@ static int launch_st3(const GemmArgs& g, hipStream_t s) {
   const int grid = min(items, cdiv(items, gres) > cdiv(items, ncu) ? ncu : gres);
   // one phase per k-tile measures 4-5 % faster with transposed-read operands (dX, dW), two phases 1.5 % faster for [rows][K] x [cols][K]
   const bool one_phase = ((g_st_xflags & 4) != 0) != (!A_KC || !B_KC);
+  if constexpr (A_KC && B_KC && AUX == ST_AUX_RES && sizeof(TO) == 4) {
+    if (!one_phase && st_res_lds_ok(g, items, grid)) {
+      static RmclLdsOnce once_r;
+      RMCL_TRY(rmcl_set_max_lds(once_r, reinterpret_cast<const void*>(gemm_st_kernel<true, true, AUX, TO, DROP, 2, 0, true>), ST_LDS + 2048));
+      RMCL_LAUNCH((gemm_st_kernel<true, true, AUX, TO, DROP, 2, 0, true>), dim3(grid), dim3(512), ST_LDS + 2048, s, g, tm, tn, rows, g_st_xflags);
+      RMCL_CHECK_LAUNCH();
+      return 0;
+    }
+  }
   if (one_phase) RMCL_LAUNCH((gemm_st_kernel<A_KC, B_KC, AUX, TO, DROP, 1>), dim3(grid), dim3(512), ST_LDS, s, g, tm, tn, rows, g_st_xflags);
   else RMCL_LAUNCH((gemm_st_kernel<A_KC, B_KC, AUX, TO, DROP, 2>), dim3(grid), dim3(512), ST_LDS, s, g, tm, tn, rows, g_st_xflags);
   RMCL_CHECK_LAUNCH();
@@ -627,6 +679,15 @@ static int launch_st_lnf(const GemmArgs& g, hipStream_t s) {
   RMCL_TRY(rmcl_set_max_lds(once, reinterpret_cast<const void*>((gemm_st_kernel<true, true, AUX, TO, DROP, 2, LNF>)), LDS));
   const int tm = cdiv(g.M, ST_T), tn = g.N / ST_T, rows = cdiv(g.M, tm);
   const int grid = min(tm * tn, max(8, st_num_cus() - g_st_reserve_cus));
+  if constexpr (LNF == 2 && AUX == ST_AUX_RES && sizeof(TO) == 4) {
+    if (st_res_lds_ok(g, tm * tn, grid)) {
+      static RmclLdsOnce once_r;
+      RMCL_TRY(rmcl_set_max_lds(once_r, reinterpret_cast<const void*>((gemm_st_kernel<true, true, AUX, TO, DROP, 2, LNF, true>)), LDS));
+      RMCL_LAUNCH((gemm_st_kernel<true, true, AUX, TO, DROP, 2, LNF, true>), dim3(grid), dim3(512), LDS, s, g, tm, tn, rows, g_st_xflags);
+      RMCL_CHECK_LAUNCH();
+      return 0;
+    }
+  }
   RMCL_LAUNCH((gemm_st_kernel<true, true, AUX, TO, DROP, 2, LNF>), dim3(grid), dim3(512), LDS, s, g, tm, tn, rows, g_st_xflags);
   RMCL_CHECK_LAUNCH();
   return 0;
