@@ -177,7 +177,9 @@ int rmcl_version(void);
  * Further keys (csrc/api.cpp rmcl_tune_set has the list): 2 two-kernel attention backward, 3 per-GEMM weight gradients, 4 waves of the attention
  * forward, 5 InfoNCE form, 6 skinny-GEMM form, 7 gemm_dp stagger, 8 / 9 attention-backward experiments, 10 chains sharing the chip (half-batch
  * lanes), 11 (round 4) 0 = the UNCENTRED LayerNorm fold of round 2, 12 / 13 (round 4) stash prefetch of the backward: buffer mask / touch
- * workgroups - measured negative, 0 by default.  These are process-global: callers that change one around a region restore it in a finally
+ * workgroups - measured negative, 0 by default, 14 residual GEMMs: 0 = the fp32 residual through registers only, 15 the MLP pre-activation
+ * stash: 1 (default) = in tile order wherever both GEMMs that touch it run on the 192x384 kernel (EPI_PREACT_TILED below), 0 = row-major
+ * in every pass (A/B runs, bit-comparison tests).  These are process-global: callers that change one around a region restore it in a finally
  * block (attack/pgd_attack_vilt.py, vilt/modules/objectives.py).                                                                          */
 int rmcl_tune_set(int key, int value);
 
@@ -593,7 +595,16 @@ int rmcl_itm_bwd(const float* dlogits, const float* cls, const float* W, float* 
                  float scale, void* stream);
 
 /* ---- kernel-level entry points (unit parity tests) ----------------------------------------- */
-/* C = epilogue(alpha * op(A) op(B)); layout kinds and epilogue flags: csrc/gemm.h                 */
+/* C = epilogue(alpha * op(A) op(B)); layout kinds and epilogue flags: csrc/gemm.h.
+ * EPI_PREACT_TILED (16384), with bf16 output, b_kc = 1 and a shape the 192x384 kernel takes (rmcl_gemm_route = 2) - anything else is an
+ * error, never a row-major fallback: the pre-activation of an MLP in TILE ORDER.  With EPI_GELU | EPI_SAVE_PREACT, C2 is not [M][ldc] but
+ * one block of 192 x 384 bf16 (147 456 bytes) per output tile, blocks ordered by (row tile, column tile), inside a block the order in
+ * which the kernel's accumulator registers hold the tile (csrc/gemm.h rmcl_preact_tiled_off); with EPI_DGELU (no bias), aux is such a
+ * buffer and ld_aux stays the logical row length.  Size in elements: ceil(M / 192) * (N / 384) * 192 * 384 - the rows padded to whole
+ * blocks; rows of a block behind the tile's live rows hold anything.  Only a GEMM of the same M and N reads what another wrote.
+ * (rmcl_encoder_forward keeps rmcl_stash_bytes as it was: a layer's tiled buffer begins in the tail of the layer's `probs` slot, free under
+ * the fused / streamed attention every tiled pass runs, and ends with the `u` slot.)
+ * rmcl_linear_lnfold(_c): bit 1 of `gelu` asks for the tiled `preact`.                                                           */
 int rmcl_gemm(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux, int M, int N, int K,
               int64_t lda, int64_t ldb, int ldc, int ld_aux, float alpha, int epi, int splitk, int dt_in, int dt_out,
               int a_kc, int b_kc, int exact, void* stream);

@@ -31,6 +31,9 @@ int rmcl_launch_gemm(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_k
   const bool timed = g_prof.on && (g.tag & g_prof.mask) && g_prof.n < g_prof.cap;
   if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], stream);
   int rc;
+  // (a tiled stash is the 192x384 bf16 kernel's own layout: never the exact kernels, which would read / write it row-major)
+  RMCL_REQUIRE(!(g.epi & EPI_PREACT_TILED) || (!exact && rmcl_gemm_fast_supported(g, dt_in, dt_out, a_kc, b_kc)),
+               "gemm: EPI_PREACT_TILED needs the bf16 192x384 kernel (bf16 in and out, exact = 0)");
   if (!exact && rmcl_gemm_fast_supported(g, dt_in, dt_out, a_kc, b_kc)) rc = rmcl_launch_gemm_fast(g, dt_out, a_kc, b_kc, stream);
   else rc = rmcl_launch_gemm_exact(g, dt_in, dt_out, a_kc, b_kc, stream);
   if (timed) {
@@ -124,6 +127,7 @@ extern int g_gemm_share;
 extern bool g_lnfold_centred;
 extern int g_prefetch_mask, g_prefetch_wgs;
 extern int g_st_res_lds;
+extern bool g_preact_tiled;
 int rmcl_l2_prefetch_experiment(const void* A, int64_t lda_bytes, int M, int rows_per_tile, int tiles_per_xcd, int col_tiles, const void* B,
                                 int64_t ldb_bytes, int nB, int nk, int tick, int lead, int per_xcd, int wgs, int* counter, int64_t* stamps, void* stream) {
   RMCL_REQUIRE(A && B && counter && M > 0 && nk > 0 && per_xcd > 0 && wgs > 0 && col_tiles > 0, "l2_prefetch_experiment: bad argument");
@@ -134,6 +138,7 @@ int rmcl_tune_set(int key, int value) {
   if (key == 11) { g_lnfold_centred = value != 0; return 0; }
   if (key == 12) { g_prefetch_mask = value & 7; return 0; }                                          // stash prefetch one layer ahead of the backward (encoder.cpp)
   if (key == 13) { g_prefetch_wgs = value < 0 ? 0 : (value > 64 ? 64 : value); return 0; }       // (0: the event traffic only, no touch launches)
+  if (key == 15) { g_preact_tiled = value != 0; return 0; }                                          // 0: the MLP pre-activation stash row-major everywhere (encoder.cpp)
   if (key == 14) { g_st_res_lds = value != 0; return 0; }                                            // 0: residual GEMMs fetch the fp32 residual through registers only (gemm_st.hip)
   if (key == 7) { g_dp_stagger = value < 0 ? 0 : value; return 0; }                                  // gemm_dp: start delay of every CU's second workgroup (10 ns ticks)
   if (key == 10) { g_gemm_share = value < 1 ? 1 : (value > 8 ? 8 : value); return 0; }                 // chains sharing the chip (GEMM routing sizes a launch against CUs / share)
@@ -312,7 +317,7 @@ int rmcl_linear_lnfold_c(const void* xb, const void* wf, const float* s, const f
                          void* out, void* preact, int M, int N, int K, int gelu, float eps, float* mean, float* rstd, void* stream) {
   RMCL_REQUIRE(xb && wf && s && c && part && out, "linear_lnfold: NULL argument");
   GemmArgs g = ga(xb, wf, out, M, N, K, K, K, N);
-  g.epi = EPI_LNFOLD | (gelu ? EPI_GELU : 0) | (preact ? EPI_SAVE_PREACT : 0); g.C2 = preact;
+  g.epi = EPI_LNFOLD | ((gelu & 1) ? EPI_GELU : 0) | (preact ? EPI_SAVE_PREACT : 0) | ((gelu & 2) ? EPI_PREACT_TILED : 0); g.C2 = preact;
   g.ln_s = s; g.ln_c = c; g.ln_part = const_cast<float*>(part); g.ln_nparts = nparts; g.ln_cols = K; g.ln_eps = eps;
   g.ln_mean = mean; g.ln_rstd = rstd; g.ln_center = center;
   RMCL_REQUIRE(rmcl_gemm_routes_to_tile192(g, 1, 1), "linear_lnfold: shape does not run on the 192-row tile kernels");

@@ -17,18 +17,27 @@ namespace {
 inline bool stream_attn(const rmcl_dims& d, int mode_bits) {
   return (mode_bits & RMCL_MODE_STREAM_ATTN) && d.dtype == RMCL_BF16 && !d.exact && d.L + 1 + d.P > 256;
 }
-// What the last forward left in the `probs` slots of a stash (log-sum-exp or probabilities), by stash address: host-side memory of the
-// most recent stashes, so that a backward called with the other setting is refused instead of reading one as the other.
-struct StashNote { const void* stash; bool stream; };
+// What the last forward left in the `probs` slots of a stash (log-sum-exp or probabilities) and in its `u` slots (the MLP pre-activation
+// row-major or in tile order, gemm.h EPI_PREACT_TILED), by stash address: host-side memory of the most recent stashes, so that a
+// backward called with the other attention setting is refused instead of reading one as the other, and reads `u` in the layout the
+// forward wrote - never one re-derived from tuning keys that may have changed in between.
+struct StashNote { const void* stash; bool stream; bool tiled; };
 StashNote g_stash_notes[64];
 int g_stash_next = 0;
 std::mutex g_stash_mu;
-void note_stash(const void* stash, bool stream) {
+void note_stash(const void* stash, bool stream, bool tiled) {
   std::lock_guard<std::mutex> lk(g_stash_mu);
   for (auto& n : g_stash_notes)
-    if (n.stash == stash) { n.stream = stream; return; }
-  g_stash_notes[g_stash_next] = StashNote{stash, stream};
+    if (n.stash == stash) { n.stream = stream; n.tiled = tiled; return; }
+  g_stash_notes[g_stash_next] = StashNote{stash, stream, tiled};
   g_stash_next = (g_stash_next + 1) % 64;
+}
+// 1 / 0: the forward that filled this stash wrote `u` tiled / row-major; -1: a stash this table no longer knows
+int stash_tiled(const void* stash) {
+  std::lock_guard<std::mutex> lk(g_stash_mu);
+  for (auto& n : g_stash_notes)
+    if (n.stash == stash) return n.tiled ? 1 : 0;
+  return -1;
 }
 bool stash_disagrees(const void* stash, bool stream) {
   std::lock_guard<std::mutex> lk(g_stash_mu);
@@ -58,6 +67,7 @@ inline int ldp_of(int N) { return (N + 7) / 8 * 8; }
 struct LayerStash {
   float *x_in, *x_mid, *mean1, *rstd1, *mean2, *rstd2;
   void *qkv, *probs, *u, *ao;      // DATA+ (ao: the attention output, for the one-kernel attention backward's delta)
+  void* u_t;                       // where the TILED form of u starts (carve_stash), NULL: it has no room in this stash
   void *ln1, *ln2, *h;             // FULL (workspace-aliased otherwise)
 };
 
@@ -96,8 +106,20 @@ size_t carve_stash(const rmcl_dims& d, int mode, void* base, Stash* st) {
     ls.mean1 = b.take<float>(M); ls.rstd1 = b.take<float>(M);
     ls.mean2 = b.take<float>(M); ls.rstd2 = b.take<float>(M);
     ls.qkv = b.take_bytes(M * 3 * D * e);
-    ls.probs = b.take_bytes((size_t)rmcl_attn_scratch_elems(d.B, d.H, (int)N) * e);
+    const size_t probs_bytes = (size_t)rmcl_attn_scratch_elems(d.B, d.H, (int)N) * e;
+    ls.probs = b.take_bytes(probs_bytes);
+    const size_t probs_off = b.off - probs_bytes;
     ls.u = b.take_bytes(M * d.mlp * e);
+    const size_t u_off = b.off - M * d.mlp * e;
+    // The tiled form of u (gemm.h EPI_PREACT_TILED) holds whole 192-row blocks: (ceil(M / 192) * 192 - M) rows more than the slot.  The stash
+    // keeps its size: the tiled buffer starts that much IN FRONT of the slot, in the tail of the `probs` slot before it, and ends where the
+    // slot ends.  That tail is free in every pass that takes the tiled form: those are bf16 passes whose attention is fused or streamed
+    // (encoder_forward_impl checks it), which keep B * H * NKP fp32 row statistics at the head of `probs` and nothing else.
+    {
+      const size_t pad = ((((size_t)cdiv((long)M, 192) * 192 - M) * d.mlp * e) + 255) & ~(size_t)255;
+      const size_t stat = (size_t)rmcl_attn_stat_elems(d.B, d.H, (int)N) * sizeof(float);
+      ls.u_t = (ls.u && d.dtype == RMCL_BF16 && u_off >= probs_off + stat + pad) ? (void*)((char*)ls.u - pad) : nullptr;
+    }
     ls.ao = b.take_bytes(M * D * e);
     if (mode == RMCL_MODE_FULL) {
       ls.ln1 = b.take_bytes(M * D * e);
@@ -266,6 +288,7 @@ static int g_npev = 0;
 extern "C" int rmcl_set_prefetch_stream(void* stream) { g_pref = (hipStream_t)stream; return 0; }
 bool g_lnfold_centred = true;        // rmcl_tune_set key 11: 0 = the uncentred LayerNorm fold of round 2 (A/B, precision tests)
 bool rmcl_lnfold_centred() { return g_lnfold_centred; }
+bool g_preact_tiled = true;          // rmcl_tune_set key 15: 0 = the MLP pre-activation stash row-major in every pass (A/B, bit-comparison tests)
 bool g_dw_grouped = true;            // rmcl_tune_set key 3: 0 selects the per-GEMM weight-gradient path (A/B and parity tests)
 
 extern "C" int rmcl_set_side_stream(void* stream) { g_side = (hipStream_t)stream; return 0; }
@@ -403,7 +426,6 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
   Work w{};
   carve_stash(*d, mode, stash, &st);
   carve_work(*d, workspace, &w);
-  if (mode != RMCL_MODE_INFER) note_stash(stash, streamed);
   const int B = d->B, L = d->L, P = d->P, N = L + 1 + P, D = d->D, M = B * N, dt = d->dtype;
   const bool keep = mode != RMCL_MODE_INFER, full = mode == RMCL_MODE_FULL;
   hipStream_t s = c.s;
@@ -459,6 +481,21 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
              rmcl_gemm_routes_to_tile192(t4, 1, 1);
   }
   const bf16_t* fw = folded ? (const bf16_t*)fold->wf : nullptr;
+  // Tiled pre-activation stash (gemm.h EPI_PREACT_TILED): decided ONCE per pass - both the pass's fc1 form and the backward's fc2-dX
+  // (transposed weight shadows, [cols][K]) must go to the 192x384 kernel with the flag - and recorded with the stash: the backward
+  // reads the record.  (The cls-only tail's compact fp32 u_c of the last layer is not a GEMM stash of this kind and stays as it is.)
+  // (and the attention must leave the tail of the `probs` slots to the tiled buffer, carve_stash: the fused kernels, N <= 256, or the streamed ones)
+  bool tiled = g_preact_tiled && keep && dt == RMCL_BF16 && !d->exact && (N <= 256 || streamed) && st.layer[0].u_t != nullptr;
+  if (tiled) {
+    GemmArgs p1 = gemm_args(w.xb_mid, c.W(c.L(0, y.fc1_w)), w.h, M, d->mlp, D, D, D, d->mlp);
+    p1.epi = (folded ? EPI_LNFOLD : EPI_BIAS) | EPI_GELU | EPI_SAVE_PREACT | EPI_PREACT_TILED | (dth ? EPI_DROPOUT : 0); p1.C2 = w.u;
+    if (folded) { p1.ln_s = fold->sc; p1.ln_c = fold->sc; p1.ln_part = w.part_mid; p1.ln_nparts = nparts; p1.ln_cols = D; }
+    GemmArgs p2 = gemm_args(w.dxT, c.W(c.L(0, y.fc2_w)), w.du, M, d->mlp, D, D, D, d->mlp);
+    p2.epi = EPI_DGELU | EPI_PREACT_TILED | (dth ? EPI_DROP_BWD : 0); p2.aux = w.u; p2.ld_aux = d->mlp;
+    tiled = rmcl_gemm_route_code(p1, RMCL_BF16, 1, 1) == 2 && rmcl_gemm_route_code(p2, RMCL_BF16, 1, 1) == 2;
+  }
+  if (keep) note_stash(stash, streamed, tiled);
+  const int epi_tiled = tiled ? EPI_PREACT_TILED : 0;
   // shift-robust form of the fold (gemm.h ln_center): every producer stores bf16(x - c) and the partial sums of (x - c), c = the row mean
   // of the row's PREVIOUS LayerNorm (LN is shift-invariant: exact for any c), so the operand's rounding follows the row's spread instead of
   // its offset.  rmcl_tune_set(11, 0) restores the uncentred round-2 form (A/B, precision tests).
@@ -477,7 +514,7 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
     void* probs = keep ? ls.probs : w.probs;
     void* ao = keep ? ls.ao : w.ao;
     void* h = full ? ls.h : w.h;
-    void* u = keep ? ls.u : nullptr;
+    void* u = keep ? (tiled ? ls.u_t : ls.u) : nullptr;
     const float* sc_l = folded ? fold->sc + (long)l * 2 * fold_rows : nullptr;        // s[0..rows), c[rows..2 rows)
     // LayerNorm 2's row means of the previous layer = the centre the previous fc2 used for this layer's LayerNorm-1 operand
     const float* m2_prev = l > 0 ? (keep ? st.layer[l - 1].mean2 : w.stat + 2 * M) : nullptr;
@@ -546,7 +583,7 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
     }
     if (folded) {
       GemmArgs g = gemm_args(w.xb_mid, fw + ((long)l * fold_rows + 3 * D) * D, h, M, d->mlp, D, D, D, d->mlp);
-      g.epi = EPI_LNFOLD | EPI_GELU | (u ? EPI_SAVE_PREACT : 0); g.C2 = u; g.tag = GEMM_TAG_FC1;
+      g.epi = EPI_LNFOLD | EPI_GELU | (u ? EPI_SAVE_PREACT | epi_tiled : 0); g.C2 = u; g.tag = GEMM_TAG_FC1;
       g.ln_s = sc_l + 3 * D; g.ln_c = sc_l + fold_rows + 3 * D; g.ln_part = w.part_mid; g.ln_nparts = nparts; g.ln_cols = D; g.ln_eps = 1e-6f;
       g.ln_mean = m2; g.ln_rstd = r2; g.ln_center = centred ? m1 : nullptr;
       with_drop(g, l, DROP_SITE_HIDDEN);
@@ -554,7 +591,7 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
     } else {
       RMCL_TRY(rmcl_ln_fwd(x_mid, D, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), 1e-6f, ln2, D, dt, m2, r2, M, D, 0, s));
       GemmArgs g = gemm_args(ln2, c.W(c.L(l, y.fc1_w)), h, M, d->mlp, D, D, D, d->mlp);
-      g.epi = EPI_BIAS | EPI_GELU | (u ? EPI_SAVE_PREACT : 0); g.bias = c.V(c.L(l, y.fc1_b)); g.C2 = u; g.tag = GEMM_TAG_FC1;
+      g.epi = EPI_BIAS | EPI_GELU | (u ? EPI_SAVE_PREACT | epi_tiled : 0); g.bias = c.V(c.L(l, y.fc1_b)); g.C2 = u; g.tag = GEMM_TAG_FC1;
       with_drop(g, l, DROP_SITE_HIDDEN);
       RMCL_TRY(gemm(c, g, dt, dt, 1, 1));
     }
@@ -660,6 +697,12 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
   RMCL_REQUIRE(params32 && stash && workspace && dxn && co_mask, "encoder_backward: NULL argument");
   RMCL_REQUIRE(!stash_disagrees(stash, streamed), "encoder_backward: RMCL_MODE_STREAM_ATTN differs from the forward that filled this stash");
   RMCL_REQUIRE(mode != RMCL_MODE_FULL || (G && text_ids && patches), "encoder_backward: FULL mode needs grads32, text_ids, patches");
+  // layout of the `u` slots: what the forward that filled this stash recorded
+  const int u_tiled = d->dtype == RMCL_BF16 && !d->exact ? stash_tiled(stash) : 0;
+  RMCL_REQUIRE(u_tiled >= 0, "encoder_backward: no forward on record for this stash (the layout of its pre-activation slots is unknown)");
+  RMCL_REQUIRE(!u_tiled || (d->L + 1 + d->P <= 256 || streamed), "encoder_backward: a tiled pre-activation stash goes with fused or streamed attention");
+  RMCL_REQUIRE(!u_tiled || params_lpT, "encoder_backward: this stash holds the tiled pre-activation (rmcl_tune_set key 15), whose backward needs the "
+                                       "transposed weight shadows params_lpT");
   RMCL_REQUIRE(d->dtype == RMCL_F32 || params_lp, "encoder_backward: bf16 mode needs the bf16 shadow arena");
   Ctx c{*d, params32, params_lp, {}, (hipStream_t)stream, d->dtype};
   rmcl_param_layout(d, &c.lay);
@@ -838,7 +881,8 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
     if (use_side && !grouped && l + 2 < Lr) HIP_TRY(hipStreamWaitEvent(s, EV(1, l + 2), 0));   // du buffer free again
     {
       GemmArgs g = gemm_args(dxT, WT ? WTp(c.L(l, y.fc2_w)) : c.W(c.L(l, y.fc2_w)), du, M, mlp, D, D, WT ? D : mlp, mlp);   // du = (dx W2) * gelu'(u)
-      g.epi = EPI_DGELU; g.aux = ls.u; g.ld_aux = mlp; g.tag = GEMM_TAG_DX;
+      // (tiled stash: the launch fails with a message when the GEMM no longer routes to the 192x384 kernel - never a row-major read)
+      g.epi = EPI_DGELU | (u_tiled ? EPI_PREACT_TILED : 0); g.aux = u_tiled ? ls.u_t : ls.u; g.ld_aux = mlp; g.tag = GEMM_TAG_DX;
       if (dth) { g.epi |= EPI_DROP_BWD; g.drop_seed = rmcl_site_seed(drop_seed, l, DROP_SITE_HIDDEN); g.drop_thresh = dth; g.drop_inv_keep = dinv; }
       RMCL_TRY(gemm(c, g, dt, dt, 1, WT ? 1 : 0));
     }

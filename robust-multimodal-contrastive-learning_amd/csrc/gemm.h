@@ -31,6 +31,14 @@ enum {
   EPI_DUP = 8192,       // skinny fp32 GEMMs: the final value is also stored to C2 (same ld as C) - a second consumer's copy without a memcpy launch
   EPI_ROWSTAT = 4096,   // producer (fp32 output = the residual stream): also store its bf16 copy to C2 and per-row partial
                         // (sum, sum of squares) of this tile's columns to ln_part[m][tile_n * 4 + wave column]
+  // 192x384 kernel (gemm_sw.hip), bf16 output, [rows][K] x [cols][K] only: the pre-activation stash in TILE ORDER.  With EPI_SAVE_PREACT,
+  // C2 is not [M][ldc] but one 192x384 block per output tile, blocks ordered by (row tile, column tile), elements inside a block in the
+  // order the kernel's accumulator fragments hold them (rmcl_preact_tiled_off below); with EPI_DGELU, aux is such a buffer (ld_aux stays
+  // the logical row length: the dropout mask index is the logical element index).  The producer and the consumer are the same kernel
+  // template with the same tile and wave decomposition, so neither converts a layout.  Rows of a block past the tile's live rows hold
+  // anything.  Size: rmcl_preact_tiled_elems(M, N) elements.  No other kernel takes the flag: a GEMM that carries it and does not route to
+  // gemm_sw fails.
+  EPI_PREACT_TILED = 16384,
 };
 
 enum {
@@ -77,6 +85,15 @@ struct GemmArgs {
 };
 
 #ifdef __cplusplus
+// EPI_PREACT_TILED: the ONE place the layout is defined (store: fc1's epilogue, load: fc2-dX's epilogue; gemm_sw.hip).
+// Element offset inside a tile's block of the four bf16 values of accumulator fragment acc[ch * 3 + il][hb * 3 + j] of (wave, lane):
+// a wave's store / load instruction of one fragment covers one contiguous, fully used 512-byte span (8 bytes per lane); the nine
+// fragments of a (row chunk ch, column half hb) group - the unit the epilogue works in - are adjacent.
+constexpr int RMCL_PREACT_TILE_ELEMS = 192 * 384;
+constexpr int rmcl_preact_tiled_off(int wave, int ch, int hb, int il, int j, int lane) {
+  return ((wave * 36 + ((ch * 2 + hb) * 3 + il) * 3 + j) * 64 + lane) * 4;
+}
+constexpr long rmcl_preact_tiled_elems(long M, long N) { return ((M + 191) / 192) * (N / 384) * RMCL_PREACT_TILE_ELEMS; }
 // dt_in / dt_out: RMCL_F32 or RMCL_BF16.  a_kc / b_kc: layout kinds above.
 // exact = 1 forces the f32-MFMA kernel (bf16 inputs are widened to f32 in LDS).
 int rmcl_launch_gemm(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc, int exact, hipStream_t stream);

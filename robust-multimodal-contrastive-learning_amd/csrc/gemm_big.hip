@@ -204,7 +204,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmArgs g, int tiles_
 bool rmcl_gemm_big_supported(const GemmArgs& g, int a_kc, int b_kc) {
   if (g.N % GBN2 != 0 || g.K % GBK2 != 0 || g.K < GBK2) return false;
   if (!a_kc && g.M % GBM2 != 0) return false;
-  if (g.epi & (EPI_DROPOUT | EPI_DROP_BWD)) return false;
+  if (g.epi & (EPI_DROPOUT | EPI_DROP_BWD | EPI_PREACT_TILED)) return false;
   return true;
 }
 

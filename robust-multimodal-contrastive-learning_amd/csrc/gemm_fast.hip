@@ -287,6 +287,7 @@ bool rmcl_gemm_fast_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc
   if (!a_kc && g.M % FBM != 0) return false;                   // m-contiguous A is read in full 256-B rows
   if (g.lda % 8 || g.ldb % 8 || g.ldc % 4 || ((uintptr_t)g.A & 15) || ((uintptr_t)g.B & 15) || ((uintptr_t)g.C & 15)) return false;
   if (g.epi & (EPI_TANH | EPI_ATOMIC)) return false;
+  if ((g.epi & EPI_PREACT_TILED) && dt_out != RMCL_BF16) return false;     // (rmcl_launch_gemm then refuses the GEMM: no exact kernel either)
   if ((g.epi & EPI_ACCUM) && dt_out != RMCL_F32) return false;
   if ((g.epi & (EPI_RESIDUAL | EPI_DGELU)) && (g.ld_aux % 4 || ((uintptr_t)g.aux & 15))) return false;
   if ((g.epi & EPI_SAVE_PREACT) && ((uintptr_t)g.C2 & 15)) return false;
@@ -325,12 +326,14 @@ int rmcl_launch_gemm_big(const GemmArgs& g, int dt_out, int a_kc, int b_kc, hipS
 // LayerNorm-folded epilogues EPI_LNFOLD / EPI_ROWSTAT)
 // Which kernel family rmcl_launch_gemm_fast gives a GEMM to (the ONE place the routing is decided; rmcl_gemm_route in the C ABI
 // reports it so that a parity test can assert which kernels it compared): 0 = 128x128 (gemm_fast), 1 = 192x192 one workgroup per CU
-// (gemm_st), 2 = 192x384 (gemm_sw), 3 = 192x192x32 two workgroups per CU (gemm_dp), 4 = 256x256 ping-pong, 5 = 256x256
+// (gemm_st), 2 = 192x384 (gemm_sw), 3 = 192x192x32 two workgroups per CU (gemm_dp), 4 = 256x256 ping-pong, 5 = 256x256; -1 = no kernel
+// (a GEMM with EPI_PREACT_TILED that gemm_sw does not take)
 int rmcl_gemm_route_code(const GemmArgs& g, int dt_out, int a_kc, int b_kc) {
   if (g_gemm_cfg == 80 && rmcl_gemm_dp_supported(g, a_kc, b_kc) && !((g.epi & EPI_RESIDUAL) && dt_out != RMCL_F32)) return 3;
   // 192x384 tiles where they make exact rounds (N = 3072 at M = 64*185: 496 tiles = 2 x 248)
   if ((g_gemm_cfg == 70 || (g_gemm_cfg < 0 && rmcl_gemm_sw_fill(g, 248 / g_gemm_share) >= 0.95)) && rmcl_gemm_sw_supported(g, a_kc, b_kc) &&
-      !((g.epi & (EPI_DROPOUT | EPI_DROP_BWD)) && dt_out != RMCL_BF16)) return 2;      // (its dropout epilogues write bf16)
+      !((g.epi & (EPI_DROPOUT | EPI_DROP_BWD | EPI_PREACT_TILED)) && dt_out != RMCL_BF16)) return 2;      // (its dropout epilogues and the tiled stash are bf16)
+  if (g.epi & EPI_PREACT_TILED) return -1;                      // the tiled pre-activation stash exists in gemm_sw only: no other kernel may take the GEMM
   // 192x192 ping-pong tiles for the activation GEMMs (M = B*185 rows) whenever they fill the CU rounds
   if ((g_gemm_cfg == 60 || (g_gemm_cfg < 0 && rmcl_gemm_st_fill(g, 256 / g_gemm_share) >= 0.7)) && rmcl_gemm_st_supported(g, a_kc, b_kc)) return 1;
   if (g_gemm_cfg == 50 && rmcl_gemm_pp_supported(g, a_kc, b_kc)) return 4;
@@ -350,6 +353,8 @@ bool rmcl_gemm_routes_to_tile192(const GemmArgs& g, int a_kc, int b_kc) {
 int rmcl_launch_gemm_fast(const GemmArgs& g0, int dt_out, int a_kc, int b_kc, hipStream_t s) {
   GemmArgs g = g0;
   const int route = rmcl_gemm_route_code(g, dt_out, a_kc, b_kc);
+  RMCL_REQUIRE(!(g.epi & EPI_PREACT_TILED) || route == 2,
+               "gemm: the tiled pre-activation stash (EPI_PREACT_TILED) exists in the 192x384 kernel only and this GEMM does not route there");
   RMCL_REQUIRE(!(g.epi & (EPI_LNFOLD | EPI_ROWSTAT)) || (route >= 1 && route <= 3),
                "gemm: the LayerNorm-folded epilogues exist in the 192-row tile kernels only");
   if (route == 3) return rmcl_launch_gemm_dp(g, dt_out, s);

@@ -76,7 +76,9 @@ __device__ __forceinline__ bf16x8 sw_ld(const char* unit, int off, int s) {
   __builtin_amdgcn_s_barrier();                           \
   __builtin_amdgcn_sched_barrier(0)
 
-enum { SW_AUX_NONE = 0, SW_AUX_RES = 1, SW_AUX_DGELU = 2 };
+// (the tiled-stash forms, EPI_PREACT_TILED in gemm.h, are further values of AUX and not a further template parameter: the names of the
+// row-major instantiations stay what they are)
+enum { SW_AUX_NONE = 0, SW_AUX_RES = 1, SW_AUX_DGELU = 2, SW_AUX_DGELU_T = 3, SW_AUX_STASH_T = 4 };
 
 struct SWCtx {
   const bf16_t* A;
@@ -109,8 +111,12 @@ __device__ __forceinline__ void sw_stage_aux(const SWAux& x, int ch, int unit, c
 
 // one k-tile; LAST: no staging (the last k-tile of the output tile).  AUXST (with LAST): the buffer that would take tile
 // t+1 takes chunk 0 of the epilogue's aux operand instead, one unit per phase like the operand staging it replaces.
-template <bool B_KC, bool LAST, bool AUXST = false>
-__device__ __forceinline__ void sw_ktile(f32x4 (&acc)[6][6], const SWCtx& c, const char* cur, char* oth, int t1, const SWAux* ax = nullptr, int lane = 0) {
+// HOOK (with LAST): called once every LDS-DMA of the k-loop has landed - ordinary global loads issued from it (the tiled GELU' operand)
+// have the whole last k-tile to arrive and share the vector-memory counter with nothing.
+struct SWNoHook { __device__ __forceinline__ void operator()() const {} };
+template <bool B_KC, bool LAST, bool AUXST = false, typename HOOK = SWNoHook>
+__device__ __forceinline__ void sw_ktile(f32x4 (&acc)[6][6], const SWCtx& c, const char* cur, char* oth, int t1, const SWAux* ax = nullptr, int lane = 0,
+                                         const HOOK& hook = HOOK()) {
   bf16x8 a[3][2], b[3][2];
   // ---- P1: rows-lo x B0
 #pragma unroll
@@ -121,7 +127,7 @@ __device__ __forceinline__ void sw_ktile(f32x4 (&acc)[6][6], const SWCtx& c, con
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int s = 0; s < 2; ++s) a[i][s] = sw_ld<true>(cur, i * 2048 + c.aoff[s], s);
-  if (!LAST) { sw_stage(c.A, c.oa, (long)t1 * 64, oth, c.wave); sw_wait_vm<3>(); } else { sw_wait_vm<0>(); if (AUXST) sw_stage_aux(*ax, 0, 0, oth, c.wave, lane); }
+  if (!LAST) { sw_stage(c.A, c.oa, (long)t1 * 64, oth, c.wave); sw_wait_vm<3>(); } else { sw_wait_vm<0>(); if (AUXST) sw_stage_aux(*ax, 0, 0, oth, c.wave, lane); hook(); }
   SW_PHASE_BEGIN();
 #pragma unroll
   for (int s = 0; s < 2; ++s)
@@ -317,12 +323,42 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
   // runs) comes through LDS - chunk 0 is fetched by LDS-DMA into the idle buffer DURING the last k-tile, chunk 1 while chunk
   // 0 is converted and stored; whole 768-byte rows instead of the fragment layout's 32-byte pieces.
   constexpr bool AUX_LDS = AUX == SW_AUX_DGELU && sizeof(TO) == 2;
+  // Tiled stash (EPI_PREACT_TILED, bf16 [rows][K] x [cols][K] only): fc1 (TILED_ST) stores the pre-activation straight from the registers
+  // into its tile's block, fc2-dX (TILED_DG) loads it from there into the same registers - no LDS image, no aux DMA, no aux barrier; the
+  // k-loop of both is the plain one.  The block of this tile, this wave, this lane (rmcl_preact_tiled_off: fragments at constant offsets):
+  constexpr bool TILED_DG = AUX == SW_AUX_DGELU_T, TILED_ST = AUX == SW_AUX_STASH_T, DG = AUX == SW_AUX_DGELU || TILED_DG;
+  static_assert(!(TILED_DG || TILED_ST) || (sizeof(TO) == 2 && B_KC), "tiled stash: bf16, [cols][K] weights");
+  // (a uniform base - wave is uniform - and the lane's offset)
+  const size_t tblk = (size_t)(tr * tiles_n + tc) * RMCL_PREACT_TILE_ELEMS + rmcl_preact_tiled_off(wave, 0, 0, 0, 0, 0);
+  const int tlane = rmcl_preact_tiled_off(0, 0, 0, 0, 0, lane);
+  const bf16_t* tl_in = TILED_DG ? reinterpret_cast<const bf16_t*>(g.aux) + tblk : nullptr;
+  // fc2-dX: a register set of the nine fragments of a (chunk, half) group, refilled row by row: group 0 is loaded during the last k-tile,
+  // and as soon as row il of group n has been converted its three registers take row il of group n + 1 - every load is issued two rows
+  // (two thirds of a group's arithmetic) ahead of its use, and the set costs the 18 registers the row-major form's LDS read-back did.
+  // Group 3 has a set of its own (in accumulator registers chunk 0 no longer needs) and is loaded with group 2, BEFORE chunk 0's row
+  // stores: the vector-memory counter retires in issue order, so no wait for a stash load behind those stores waits for them to drain
+  // (the compiler counts the waits; the sched_barriers keep the loads where they are written - unpinned, the scheduler sank every group's
+  // loads to the end of the group before and waited for them at once).
+  uint2 tpre[TILED_DG ? 2 : 1][3][3];
+  auto tiled_load_row = [&](int GRP, int il) {                   // (GRP, il: constants after unrolling)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      tpre[TILED_DG && GRP == 3 ? 1 : 0][il][j] = *reinterpret_cast<const uint2*>(tl_in + tlane + rmcl_preact_tiled_off(0, GRP >> 1, GRP & 1, il, j, 0));
+    __builtin_amdgcn_sched_barrier(0);
+  };
   char* last_cur = (it & 1) ? buf1 : buf0;
   char* aux_area = (it & 1) ? buf0 : buf1;                     // free during the last k-tile
   SWAux ax{reinterpret_cast<const bf16_t*>(g.aux), (long)g.ld_aux, m0, n0, g.M};
   if constexpr (AUX_LDS) {
     sw_ktile<B_KC, true, true>(acc, c, last_cur, aux_area, 0, &ax, lane);
     sw_wait_vm<0>();
+  } else if constexpr (TILED_DG) {
+    auto hook = [&]() {
+#pragma unroll
+      for (int il = 0; il < 3; ++il) tiled_load_row(0, il);
+    };
+    sw_ktile<B_KC, true, false, decltype(hook)>(acc, c, last_cur, nullptr, 0, nullptr, 0, hook);
   } else {
     sw_ktile<B_KC, true>(acc, c, last_cur, nullptr, 0);
   }
@@ -342,6 +378,7 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
   const int epi = g.epi;
   TO* C = reinterpret_cast<TO*>(g.C);
   TO* C2 = reinterpret_cast<TO*>(g.C2);
+  bf16_t* tl_out = TILED_ST ? reinterpret_cast<bf16_t*>(g.C2) + tblk : nullptr;              // (uniform; the lane's offset is tlane)
   const int mb = m0 + wm * 96 + (lane & 15);
   if constexpr (sizeof(TO) == 2) {
     // bf16 outputs go through LDS (all 144 KiB are free now) and leave as whole 768-byte rows, 16 bytes per lane: the
@@ -359,7 +396,7 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
     // (the GELU' form carries no bias - fc2-dX - and has no registers to spare: its zero "bias" stays a constant)
     // (the dropout instantiations keep them per (chunk, half) too: with both halves' vectors live beside the mask state the folded fc1
     // form spilled - 256 VGPRs + scratch - and its epilogue gained nothing from the round-4 rework: 90 us against 76 without dropout)
-    constexpr bool HOIST = AUX != SW_AUX_DGELU && !DROP;
+    constexpr bool HOIST = !DG && !DROP;
     float4 bias2[HOIST ? 2 : 1][3], lns2[HOIST ? 2 : 1][LNF == 1 ? 3 : 1];
     if constexpr (HOIST) {
 #pragma unroll
@@ -430,6 +467,9 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
               if constexpr (LNF == 1) {
                 bias_l[j] = *reinterpret_cast<const float4*>(g.ln_c + nb + j * 16);
                 lns_l[j] = *reinterpret_cast<const float4*>(g.ln_s + nb + j * 16);
+              } else if constexpr (TILED_DG) {
+                bias_l[j] = make_float4(0.f, 0.f, 0.f, 0.f);           // (no bias in this form, not even a conditional load: it would be the youngest
+                                                                        // vector-memory operation ahead of the group's first FMA and its wait would drain the stash prefetch)
               } else {
                 bias_l[j] = (epi & EPI_BIAS) ? *reinterpret_cast<const float4*>(g.bias + nb + j * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
               }
@@ -464,7 +504,8 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
               f32x4 v;
               if constexpr (LNF == 1) v = rstd_m * (av - mean_m * f4v(lns[j])) + bv;
               else v = g.alpha * av + bv;
-              if (AUX == SW_AUX_DGELU) v *= gelu_poly_grad4(bf2f4(pre[il][j]));
+              if constexpr (TILED_DG) v *= gelu_poly_grad4(bf2f4(tpre[TILED_DG && ch * 2 + hb == 3 ? 1 : 0][il][j]));
+              else if (AUX == SW_AUX_DGELU) v *= gelu_poly_grad4(bf2f4(pre[il][j]));
               if constexpr (DROP && (DM & 2) != 0) {
                 if (DM == 2 || (epi & EPI_DROP_BWD)) {                 // mask of the forward's hidden dropout, indexed like the stash
                   const uint32_t di = dbase_aux + (uint32_t)(i * 16) * (uint32_t)g.ld_aux + (uint32_t)(nb + j * 16);
@@ -472,7 +513,8 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
                 }
               }
               const int off = woff[hb][j] + il * 16 * ROWB;
-              if constexpr (STASH) *reinterpret_cast<uint2*>(img + IMG + off) = f2bf4(v);
+              if constexpr (STASH && TILED_ST) *reinterpret_cast<uint2*>(tl_out + tlane + rmcl_preact_tiled_off(0, ch, hb, il, j, 0)) = f2bf4(v);
+              else if constexpr (STASH) *reinterpret_cast<uint2*>(img + IMG + off) = f2bf4(v);
               if constexpr (GELU) v = gelu_poly4(v);
               if constexpr (DROP && (DM & 1) != 0) {
                 if (DM == 1 || (epi & EPI_DROPOUT)) {
@@ -482,6 +524,13 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
               }
               const uint2 pk = f2bf4(v);
               *reinterpret_cast<uint2*>(img + off) = pk;
+            }
+            if constexpr (TILED_DG) {
+              if (ch * 2 + hb < 2) tiled_load_row(ch * 2 + hb + 1, il);
+              if (ch * 2 + hb == 1 && il == 2) {
+#pragma unroll
+                for (int l3 = 0; l3 < 3; ++l3) tiled_load_row(3, l3);
+              }
             }
           }
         }
@@ -497,7 +546,7 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
               if (rb_row[kk] + 16 * t3 < lim) {
                 const size_t dst = (size_t)(cbase + (uint32_t)(16 * t3) * (uint32_t)g.ldc + rb_dst[kk]);
                 *reinterpret_cast<float4*>(C + dst) = *reinterpret_cast<const float4*>(img + rb_lds[kk] + t3 * 16 * ROWB);
-                if constexpr (STASH) *reinterpret_cast<float4*>(C2 + dst) = *reinterpret_cast<const float4*>(img + IMG + rb_lds[kk] + t3 * 16 * ROWB);
+                if constexpr (STASH && !TILED_ST) *reinterpret_cast<float4*>(C2 + dst) = *reinterpret_cast<const float4*>(img + IMG + rb_lds[kk] + t3 * 16 * ROWB);
               }
             }
         }
@@ -521,7 +570,13 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
       using D3 = std::integral_constant<int, 3>;
       const bool gelu = (epi & EPI_GELU) != 0;
       const int dm = DROP ? (((epi & EPI_DROPOUT) ? 1 : 0) | ((epi & EPI_DROP_BWD) ? 2 : 0)) : 0;
-      if constexpr (!DROP) {
+      // (the tiled forms are the step's own combinations and nothing else - rmcl_gemm_sw_supported: the producer is GELU + stash
+      // [+ its own dropout mask], the consumer GELU' [+ the hidden mask])
+      if constexpr (TILED_ST) {
+        if constexpr (DROP) chunk_loop(T1{}, T1{}, D1{}); else chunk_loop(T1{}, T1{}, D0{});
+      } else if constexpr (TILED_DG) {
+        if constexpr (DROP) chunk_loop(T0{}, T0{}, D2{}); else chunk_loop(T0{}, T0{}, D0{});
+      } else if constexpr (!DROP) {
         if constexpr (AUX_LDS) {
           if (gelu) chunk_loop(T1{}, T0{}, D0{}); else chunk_loop(T0{}, T0{}, D0{});
         } else {
@@ -594,8 +649,13 @@ bool rmcl_gemm_sw_supported(const GemmArgs& g, int a_kc, int b_kc) {
   if (g.N % 384 != 0 || g.K % 64 != 0 || g.K < 128) return false;
   if ((long)g.M * g.lda >= (1L << 31) || (long)(b_kc ? g.N : g.K) * g.ldb >= (1L << 31)) return false;
   if ((long)g.M * g.ldc >= (1L << 31)) return false;                          // (the bf16 epilogue's row stores use 32-bit element offsets)
-  if (g.epi & ~(EPI_BIAS | EPI_GELU | EPI_SAVE_PREACT | EPI_DGELU | EPI_LNFOLD | EPI_DROPOUT | EPI_DROP_BWD)) return false;   // (residual epilogue: 72 more live registers spill; N = 768 anyway)
+  if (g.epi & ~(EPI_BIAS | EPI_GELU | EPI_SAVE_PREACT | EPI_DGELU | EPI_LNFOLD | EPI_DROPOUT | EPI_DROP_BWD | EPI_PREACT_TILED)) return false;   // (residual epilogue: 72 more live registers spill; N = 768 anyway)
   if ((g.epi & EPI_DROP_BWD) && !(g.epi & EPI_DGELU)) return false;          // (dropout epilogues: bf16 outputs only - the router checks dt_out)
+  // tiled stash: [cols][K] weights, exactly one of (producer: EPI_SAVE_PREACT -> C2, consumer: EPI_DGELU <- aux); bf16 output - the router checks dt_out
+  if ((g.epi & EPI_PREACT_TILED) && (!b_kc || !(g.epi & EPI_SAVE_PREACT) == !(g.epi & EPI_DGELU))) return false;
+  // (built for the step's own combinations only: producer = GELU + stash [+ EPI_DROPOUT], consumer = GELU' [+ EPI_DROP_BWD], no bias)
+  if ((g.epi & EPI_PREACT_TILED) && (g.epi & EPI_SAVE_PREACT) && !(g.epi & EPI_GELU)) return false;
+  if ((g.epi & EPI_PREACT_TILED) && (g.epi & EPI_DGELU) && (g.epi & (EPI_BIAS | EPI_GELU | EPI_DROPOUT))) return false;
   if (g.epi & EPI_LNFOLD) {
     if (!b_kc || (g.epi & (EPI_BIAS | EPI_DGELU)) || !g.ln_s || !g.ln_c || !g.ln_part || g.ln_nparts % 2 || g.ln_nparts <= 0 || g.ln_cols <= 0) return false;
   }
@@ -629,17 +689,27 @@ static int launch_sw2(const GemmArgs& g, int dt_out, hipStream_t s) {
 
 template <bool B_KC>
 static int launch_sw(const GemmArgs& g, int dt_out, hipStream_t s) {
+  if (g.epi & EPI_PREACT_TILED) {
+    if constexpr (B_KC) {
+      RMCL_REQUIRE(dt_out == RMCL_BF16, "gemm_sw: the tiled pre-activation stash is bf16");
+      const bool drop = (g.epi & (EPI_DROPOUT | EPI_DROP_BWD)) != 0;
+      if (g.epi & EPI_DGELU) return drop ? launch_sw3<true, SW_AUX_DGELU_T, bf16_t, true>(g, s) : launch_sw3<true, SW_AUX_DGELU_T, bf16_t>(g, s);
+      return drop ? launch_sw3<true, SW_AUX_STASH_T, bf16_t, true>(g, s) : launch_sw3<true, SW_AUX_STASH_T, bf16_t>(g, s);
+    } else {
+      RMCL_REQUIRE(false, "gemm_sw: the tiled pre-activation stash needs [cols][K] weights");
+    }
+  }
   if (g.epi & EPI_DGELU) return launch_sw2<B_KC, SW_AUX_DGELU>(g, dt_out, s);
   return launch_sw2<B_KC, SW_AUX_NONE>(g, dt_out, s);
 }
 
-template <bool DROP>
+template <bool DROP, int AUX = SW_AUX_NONE>
 static int launch_sw_lnf(const GemmArgs& g, hipStream_t s) {
   constexpr int LDS = SW_LDS + 2048;
   static RmclLdsOnce once;
-  RMCL_TRY(rmcl_set_max_lds(once, reinterpret_cast<const void*>((gemm_sw_kernel<true, SW_AUX_NONE, bf16_t, 1, DROP>)), LDS));
+  RMCL_TRY(rmcl_set_max_lds(once, reinterpret_cast<const void*>((gemm_sw_kernel<true, AUX, bf16_t, 1, DROP>)), LDS));
   const int tm = cdiv(g.M, 192), tn = g.N / 384, rows = cdiv(g.M, tm);
-  RMCL_LAUNCH((gemm_sw_kernel<true, SW_AUX_NONE, bf16_t, 1, DROP>), dim3(tm * tn), dim3(512), LDS, s, g, tm, tn, rows);
+  RMCL_LAUNCH((gemm_sw_kernel<true, AUX, bf16_t, 1, DROP>), dim3(tm * tn), dim3(512), LDS, s, g, tm, tn, rows);
   RMCL_CHECK_LAUNCH();
   return 0;
 }
@@ -647,6 +717,7 @@ static int launch_sw_lnf(const GemmArgs& g, hipStream_t s) {
 int rmcl_launch_gemm_sw(const GemmArgs& g, int dt_out, int b_kc, hipStream_t s) {
   if (g.epi & EPI_LNFOLD) {
     RMCL_REQUIRE(b_kc && dt_out == RMCL_BF16, "gemm_sw: the LayerNorm-folded form is [rows][K] x [cols][K] with bf16 output");
+    if (g.epi & EPI_PREACT_TILED) return (g.epi & EPI_DROPOUT) ? launch_sw_lnf<true, SW_AUX_STASH_T>(g, s) : launch_sw_lnf<false, SW_AUX_STASH_T>(g, s);
     return (g.epi & EPI_DROPOUT) ? launch_sw_lnf<true>(g, s) : launch_sw_lnf<false>(g, s);
   }
   return b_kc ? launch_sw<true>(g, dt_out, s) : launch_sw<false>(g, dt_out, s);

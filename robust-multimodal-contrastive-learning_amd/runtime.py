@@ -471,6 +471,8 @@ class Engine:
         # transposed bf16 shadows of the layer weights for the data-gradient GEMMs (include/rmcl.h rmcl_weight_transpose_bf16)
         self.q_lpT = z(lay.total, torch.bfloat16) if (self.dtype == L.BF16 and os.environ.get("RMCL_NO_WT", "0") != "1") else None
         self.lpT_stale = True
+        if self.dtype == L.BF16 and self.q_lpT is None:
+            check(lib.rmcl_tune_set(15, 0), "tune_set")    # no transposed shadows: the backward cannot read a tiled pre-activation stash
         self.specs = param_specs(cfg, lay) + self.bt_specs + self.vqa_specs + self.nlvr2_specs + self.mlm_specs + self.mpp_specs
         self._bufs: Dict[tuple, PassBuffers] = {}
         self.lp_stale = True

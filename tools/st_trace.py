@@ -1,5 +1,6 @@
 """Phase timeline of ONE workgroup of gemm_st_kernel (developer build: csrc/build.sh with RMCL_EXTRA_FLAGS=-DST_TRACE).
-Usage: python tools/st_trace.py {proj|fc2|qkv|projdx|fc1|fc2dx|attnbwd|attnfwd|dw}   - launches the step's form of that GEMM 5x and prints the last stamps."""
+Usage: python tools/st_trace.py {proj|fc2|qkv|projdx|fc1|fc2dx|attnbwd|attnfwd|dw}   - launches the step's form of that GEMM 5x and prints the last stamps.
+fc1 / fc2dx: the tiled pre-activation stash (csrc/gemm.h EPI_PREACT_TILED) as the step uses it; ST_TRACE_ROWMAJOR=1 launches the row-major forms."""
 import sys, os, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -51,20 +52,22 @@ elif which == "qkv":
     run = lambda: check(lib.rmcl_linear_lnfold(P(xb), P(W), P(s_), P(c_), P(part), 16, P(out), None, M, N, D, 0, F(1e-6), P(mean), P(rstd), stream()))
 elif which in ("fc1", "fc2dx"):             # the 192x384-tile kernel (gemm_sw.hip): fc1 forward with stash, fc2-dX with GELU'
     H = 3072
+    tiled = not os.environ.get("ST_TRACE_ROWMAJOR")
+    Mu = (M + 191) // 192 * 192 if tiled else M                                          # the tiled stash holds whole 192-row blocks
     if which == "fc1":
         xb = torch.randn(M, D, generator=g).to(DEV).to(torch.bfloat16)
         part = torch.rand(M, 16, 2, generator=g).to(DEV) + 1.0
         mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
         W = (torch.randn(H, D, generator=g) * 0.05).to(DEV).to(torch.bfloat16)
         s_, c_ = torch.randn(H, generator=g).to(DEV), torch.randn(H, generator=g).to(DEV)
-        out, pre = torch.empty(M, H, dtype=torch.bfloat16, device=DEV), torch.empty(M, H, dtype=torch.bfloat16, device=DEV)
-        run = lambda: check(lib.rmcl_linear_lnfold(P(xb), P(W), P(s_), P(c_), P(part), 16, P(out), P(pre), M, H, D, 1, F(1e-6), P(mean), P(rstd), stream()))
+        out, pre = torch.empty(M, H, dtype=torch.bfloat16, device=DEV), torch.empty(Mu, H, dtype=torch.bfloat16, device=DEV)
+        run = lambda: check(lib.rmcl_linear_lnfold(P(xb), P(W), P(s_), P(c_), P(part), 16, P(out), P(pre), M, H, D, 3 if tiled else 1, F(1e-6), P(mean), P(rstd), stream()))
     else:
         dy = torch.randn(M, D, generator=g).to(DEV).to(torch.bfloat16)
         W = (torch.randn(H, D, generator=g) * 0.05).to(DEV).to(torch.bfloat16)          # transposed shadow: [N = 3072][K = 768]
-        u = torch.randn(M, H, generator=g).to(DEV).to(torch.bfloat16)
+        u = torch.randn(Mu, H, generator=g).to(DEV).to(torch.bfloat16)
         out = torch.empty(M, H, dtype=torch.bfloat16, device=DEV)
-        run = lambda: check(lib.rmcl_gemm(P(dy), P(W), P(out), None, None, P(u), M, H, D, I64(D), I64(D), H, H, F(1.0), 16, 1, L.BF16, L.BF16, 1, 1, 0, stream()))
+        run = lambda: check(lib.rmcl_gemm(P(dy), P(W), P(out), None, None, P(u), M, H, D, I64(D), I64(D), H, H, F(1.0), 16 | (16384 if tiled else 0), 1, L.BF16, L.BF16, 1, 1, 0, stream()))
 elif which in ("attnbwd", "attnfwd"):         # fused attention, B = 64, N = 185, 12 heads
     B, N, Hh = 64, 185, 12
     qkv = torch.randn(B * N, 3 * D, generator=g).to(DEV).to(torch.bfloat16)
