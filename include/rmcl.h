@@ -175,12 +175,16 @@ int rmcl_version(void);
  * channel workgroups and small side-stream kernels do not displace GEMM workgroups - at M = 64*185 the 62 x {4,12,16} tiles
  * are whole multiples of a 248-workgroup grid, so this costs nothing).
  * Further keys (csrc/api.cpp rmcl_tune_set has the list): 2 two-kernel attention backward, 3 per-GEMM weight gradients, 4 waves of the attention
- * forward, 5 InfoNCE form, 6 skinny-GEMM form, 7 gemm_dp stagger, 8 / 9 attention-backward experiments, 10 chains sharing the chip (half-batch
+ * forward, 5 InfoNCE form, 6 skinny-GEMM form (below), 7 gemm_dp stagger, 8 / 9 attention-backward experiments, 10 chains sharing the chip (half-batch
  * lanes), 11 (round 4) 0 = the UNCENTRED LayerNorm fold of round 2, 12 / 13 (round 4) stash prefetch of the backward: buffer mask / touch
  * workgroups - measured negative, 0 by default, 14 residual GEMMs: 0 = the fp32 residual through registers only, 15 the MLP pre-activation
  * stash: 1 (default) = in tile order wherever both GEMMs that touch it run on the 192x384 kernel (EPI_PREACT_TILED below), 0 = row-major
  * in every pass (A/B runs, bit-comparison tests).  These are process-global: callers that change one around a region restore it in a finally
- * block (attack/pgd_attack_vilt.py, vilt/modules/objectives.py).                                                                          */
+ * block (attack/pgd_attack_vilt.py, vilt/modules/objectives.py).
+ * key 6, the skinny fp32 GEMMs (M <= 1024 rows, csrc/gemm_exact.hip): 0 = the row-split kernel only; 1 = the k-split kernel wherever
+ * K % 64 == 0 and K >= 128; -1 (default) or 2 = for N < 4096 the STREAMING k-split kernel - the same arithmetic bit for bit, with the weight
+ * loads of a wave's whole K chunk issued before its first MFMA and 1, 2 or 4 row tiles per workgroup, chosen from M and from the share of
+ * key 10 - and the k-split kernel's 32-column form for N >= 4096.  1 is the A/B arm and the bitwise reference of the default.              */
 int rmcl_tune_set(int key, int value);
 
 /* Optional second HIP stream: the weight-gradient GEMMs of rmcl_encoder_backward (mode FULL, bf16) then run
@@ -608,6 +612,14 @@ int rmcl_itm_bwd(const float* dlogits, const float* cls, const float* W, float* 
 int rmcl_gemm(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux, int M, int N, int K,
               int64_t lda, int64_t ldb, int ldc, int ld_aux, float alpha, int epi, int splitk, int dt_in, int dt_out,
               int a_kc, int b_kc, int exact, void* stream);
+/* Skinny fp32 GEMM whose A operand is bf16 rows read in place: C[M, N] = epilogue(A[M, K] W[N, K]^T) with A bf16 at row stride lda (in
+ * bf16 elements, lda % 4 == 0), W / bias / aux / C / C2 fp32, epi of csrc/gemm.h.  Widening bf16 is exact: the result has the bits of
+ * rmcl_rows_gather_f32 followed by rmcl_gemm on the fp32 rows.  Runs on the streaming skinny kernel only (M <= 1024, K % 64 == 0,
+ * 128 <= K < 2048, N < 4096, rmcl_tune_set key 6 at -1 or 2); anything else is an error, never a converted copy.                      */
+int rmcl_gemm_rows_bf16(const void* A, const float* W, float* C, float* C2, const float* bias, const float* aux, int M, int N, int K,
+                        int64_t lda, int ldc, int ld_aux, int epi, void* stream);
+/* out[r, :] = f32(in[(r * stride + off) * D ...]) for r < R: rows of a [., D] tensor of `dtype` gathered at a row stride into compact fp32. */
+int rmcl_rows_gather_f32(const void* in, int dtype, float* out, int R, int D, int64_t stride, int64_t off, void* stream);
 /* Kernel family the bf16 fast path gives a GEMM of this shape / epilogue / layout to under the current tuning: 0 = 128x128 tiles,
  * 1 = 192x192 one workgroup per CU (gemm_st.hip), 2 = 192x384 (gemm_sw.hip), 3 = 192x192x32 two workgroups per CU (gemm_dp.hip),
  * 4 / 5 = 256x256.  Lets a parity test state WHICH kernels it compared with the oracle.                                          */

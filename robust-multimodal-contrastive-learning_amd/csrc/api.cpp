@@ -144,7 +144,7 @@ int rmcl_tune_set(int key, int value) {
   if (key == 10) { g_gemm_share = value < 1 ? 1 : (value > 8 ? 8 : value); return 0; }                 // chains sharing the chip (GEMM routing sizes a launch against CUs / share)
   if (key == 9) { g_attn_bwd_tpw = value; return 0; }                                             // fused attention backward: key tiles per wave (1, 2, 3)
   if (key == 8) { g_attn_bwd_persist = value < 0 ? 0 : value; return 0; }                           // fused attention backward: workgroups (0: one per problem)
-  if (key == 6) { rmcl_gemm_skinny_set_form(value); return 0; }                                   // 0: skinny GEMMs in the row-split form only
+  if (key == 6) { rmcl_gemm_skinny_set_form(value); return 0; }                                   // skinny GEMMs: 0 row-split form only, 1 k-split kernel, -1 / 2 streaming k-split form (gemm_exact.hip)
   if (key == 0) { rmcl_gemm_fast_set_cfg(value); return 0; }
   if (key == 1) { g_st_reserve_cus = value < 0 ? 0 : (value > 128 ? 128 : value); return 0; }   // CUs left free by the activation GEMMs
   if (key == 2) { g_attn_fused_bwd = value != 0; return 0; }                                    // 0: two-kernel attention backward
@@ -453,6 +453,17 @@ int rmcl_gemm(const void* A, const void* B, void* C, void* C2, const float* bias
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ld_aux = ld_aux;
   g.alpha = alpha; g.epi = epi; g.splitk = splitk < 1 ? 1 : splitk; g.nb1 = 1; g.nb2 = 1;
   return rmcl_launch_gemm(g, dt_in, dt_out, a_kc, b_kc, exact, (hipStream_t)stream);
+}
+int rmcl_gemm_rows_bf16(const void* A, const float* W, float* C, float* C2, const float* bias, const float* aux, int M, int N, int K,
+                        int64_t lda, int ldc, int ld_aux, int epi, void* stream) {
+  RMCL_REQUIRE(A && W && C, "gemm_rows_bf16: NULL operand");
+  GemmArgs g = ga(A, W, C, M, N, K, lda, K, ldc);
+  g.C2 = C2; g.bias = bias; g.aux = aux; g.ld_aux = ld_aux; g.epi = epi; g.a_bf16 = 1;
+  return rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, (hipStream_t)stream);
+}
+int rmcl_rows_gather_f32(const void* in, int dtype, float* out, int R, int D, int64_t stride, int64_t off, void* stream) {
+  RMCL_REQUIRE(in && out && R > 0 && D > 0 && stride > 0 && off >= 0, "rows_gather_f32: bad argument");
+  return rmcl_rows_gather_cast(in, dtype, out, R, D, (long)stride, (long)off, (hipStream_t)stream);
 }
 int rmcl_gemm_chain(const rmcl_chain_stage* st, int n, int M, uint32_t* tickets, uint32_t epoch, int flags, int32_t* xcc, int64_t* stamps,
                     int stamp_wg, void* stream) {

@@ -548,12 +548,18 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
       float* u_c = reinterpret_cast<float*>(keep ? ls.u : w.u);
       float* h_c = reinterpret_cast<float*>(full ? ls.h : w.h);
       float* xo_c = keep ? st.x_final : x_out;
-      RMCL_TRY(rmcl_rows_gather_cast(ao, dt, ao_c, B, D, N, 0, s));
       {
-        // residual operand: the cls rows of the dense residual stream, read in place (row b at b * N * D: no gather launch)
-        GemmArgs g = gemm_args(ao_c, c.V(c.L(l, y.proj_w)), x_mid, B, D, D, D, D, D);
+        // residual operand: the cls rows of the dense residual stream, read in place (row b at b * N * D: no gather launch).  The A
+        // operand likewise where the streaming skinny kernel runs the GEMM: the cls rows of the attention output at row stride
+        // N * D, bf16 widened in its registers - the bits of the gather-and-cast launch, which only the other forms still need
+        GemmArgs g = gemm_args(ao, c.V(c.L(l, y.proj_w)), x_mid, B, D, D, (long)N * D, D, D);
         g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, y.proj_b)); g.aux = x; g.ld_aux = N * D;
+        g.a_bf16 = dt == RMCL_BF16;
         with_drop(g, l, DROP_SITE_PROJ, N);
+        if (!rmcl_gemm_skinny_streams(g, 1)) {
+          RMCL_TRY(rmcl_rows_gather_cast(ao, dt, ao_c, B, D, N, 0, s));
+          g.A = ao_c; g.lda = D; g.a_bf16 = 0;
+        }
         RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
       }
       RMCL_TRY(rmcl_ln_fwd(x_mid, D, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), 1e-6f, ln2_c, D, RMCL_F32, m2, r2, B, D, 0, s));

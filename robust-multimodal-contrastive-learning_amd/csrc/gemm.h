@@ -82,6 +82,9 @@ struct GemmArgs {
   float ln_eps;
   int kblk;                          // gemm_dp.hip only: bit 0 / 1 = A / B stored k-blocked [K/32][rows][32] (a k-step of an operand tile is then
                                      // 12 KiB of whole 128-byte lines instead of 192 half lines); bit 2 = the EPI_ROWSTAT producer writes C2 k-blocked
+  int a_bf16;                        // streaming skinny fp32 GEMM only (gemm_exact.hip; rmcl_gemm_skinny_streams says whether it takes the GEMM):
+                                     // A holds bf16, [M][lda] with lda in bf16 elements, widened in registers; B, C and aux stay fp32.  Anything
+                                     // else that is handed the flag fails
 };
 
 #ifdef __cplusplus

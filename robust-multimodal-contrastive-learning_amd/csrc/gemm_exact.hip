@@ -6,8 +6,11 @@
 // 64x64 = 2x2 MFMA tiles of 32x32; LDS images are k-major [16][128+4] f32 so that the one-float
 // A/B fragments (lane l: A[i=l&31][k=l>>5], B[k=l>>5][j=l&31]) are conflict-free ds_read_b32.
 // Register-staged double buffering: tile t+1 is loaded to VGPRs before the MFMAs of tile t.
+#include <type_traits>
+
 #include "rmcl_common.h"
 #include "gemm.h"
+#include "skinny_select.h"
 
 #define GBM 128
 #define GBN 128
@@ -203,7 +206,11 @@ static int launch_layout(const GemmArgs& g, int a_kc, int b_kc, dim3 grid, hipSt
 
 bool rmcl_gemm_skinny_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc);
 int rmcl_launch_gemm_skinny(const GemmArgs& g, int b_kc, hipStream_t s);
-static int g_skinny_form = -1;      // rmcl_tune_set key 6: 0 = the first forms only (row-split skinny kernel, LDS-staged TN kernel)
+bool rmcl_gemm_skinny_streams(const GemmArgs& g, int b_kc);
+extern int g_gemm_share;            // gemm_fast.hip, rmcl_tune_set key 10: chains sharing the chip
+// rmcl_tune_set key 6: 0 = the first forms only (row-split skinny kernel, LDS-staged TN kernel); 1 = the k-split skinny kernel (the
+// streaming form's A/B arm and bitwise reference); -1 (default) or 2 = the streaming k-split form wherever the k-split form ran 16-column tiles
+static int g_skinny_form = -1;
 
 // Outer-product-like fp32 GEMM: C[M, N] (+)= alpha * A^T B with A [K, M], B [K, N] and a SHORT reduction (K = the batch rows:
 // the weight gradients of the heads, of the encoder's cls-only tail and of the Barlow-Twins head, and its cross-correlation
@@ -296,6 +303,8 @@ bool rmcl_gemm_tn_shortk_takes(const GemmArgs& g) {
 }
 
 int rmcl_launch_gemm_exact(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc, hipStream_t s) {
+  RMCL_REQUIRE(!g.a_bf16 || (a_kc && dt_in == RMCL_F32 && dt_out == RMCL_F32 && g.M > 0 && g.N > 0 && rmcl_gemm_skinny_streams(g, b_kc)),
+               "gemm: a bf16 A operand beside fp32 weights is the streaming skinny kernel's alone (rmcl_tune_set key 6; K % 64 == 0, 128 <= K < 2048, N < 4096, weights [N][K])");
   if (g.A && g.B && g.C && g.M > 0 && g.N > 0 && rmcl_gemm_skinny_supported(g, dt_in, dt_out, a_kc)) return rmcl_launch_gemm_skinny(g, b_kc, s);
   if (g.A && g.B && g.C && g.M > 0 && g.N > 0 && !a_kc && !b_kc && dt_in == RMCL_F32 && dt_out == RMCL_F32 && g.K >= 1 && g.K <= 256 &&
       g.splitk <= 1 && g.nb1 * g.nb2 == 1 && (g.epi & ~(EPI_ACCUM | EPI_COLSUM)) == 0 && (!(g.epi & EPI_COLSUM) || g.colsum) && g_skinny_form != 0) {
@@ -528,6 +537,132 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_ksplit_kernel(GemmArgs g)
   }
 }
 
+// Third form: the k-split kernel above with its loads re-timed and its rows cut to what the problem has.  The ARITHMETIC is the
+// k-split kernel's, element for element (same K / NW chunk per wave, same 16-k steps, the same four MFMAs per step in x, y, z, w
+// order on one accumulator, the same LDS sum over waves 0 .. NW-1, the same epilogue expressions), so the two forms agree bit for bit.
+//   * Weights first.  The weights are cold on every pass (26 MB of fp32, evicted by the dense traffic between uses) while the A panel
+//     was written by the previous launch; in the k-split kernel's ring both wait in one queue, 3 steps deep, and a wave's chunk is a
+//     chain of 4 - 8 HBM round trips.  Here a wave issues the weight loads of a whole burst (skinny_select.h: 12 or 24 steps, i.e.
+//     the whole chunk at the step's shapes) before its first MFMA, and only A keeps a ring (rmcl_skinny_a_ring steps).  Every burst
+//     is straight-line code: all register indices and all waits (counted vmcnt) are the compiler's, none depends on a run-time trip.
+//   * RT row tiles of 16 per workgroup instead of always 4: the launcher picks RT so that no workgroup covers a tile that begins
+//     beyond M (the k-split kernel loads and multiplies min(m, M - 1) duplicates there) and so that launches with few column tiles
+//     still fill the chain's part of the chip.  Per-element arithmetic does not depend on RT.
+//   * A16: A holds bf16 (row stride lda in bf16 elements), widened in registers - exact, so the bits are those of a gather-and-cast
+//     launch followed by the fp32 form (the cls-only tail's proj reads the attention output's cls rows in place).
+template <bool B_KC, int NW, int RT, int BS, bool A16>
+__global__ __launch_bounds__(64 * NW) void gemm_skinny_stream_kernel(GemmArgs g) {
+  constexpr int ROWS = 16 * RT, AD = rmcl_skinny_a_ring(B_KC, RT);
+  __shared__ float red[NW][ROWS][17];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c = lane & 15, gq = lane >> 4;
+  const int m0 = blockIdx.y * ROWS, n0 = blockIdx.x * 16;
+  const int kq = g.K / NW, k_lo = wave * kq;                               // kq % 16 == 0 (launcher)
+  const float* Ap[RT];
+  const bf16_t* Ah[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    const long off = (long)min(m0 + rt * 16 + c, g.M - 1) * g.lda + 4 * gq;
+    Ap[rt] = reinterpret_cast<const float*>(g.A) + off;
+    Ah[rt] = reinterpret_cast<const bf16_t*>(g.A) + off;
+  }
+  const int nc = min(n0 + c, g.N - 1);
+  const float* Bp = reinterpret_cast<const float*>(g.B) + (B_KC ? (long)nc * g.ldb + 4 * gq : (long)(4 * gq) * g.ldb + nc);
+  f32x4 acc[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // one burst of n steps from k: every weight load, then AD steps of A, then per step {A of step + AD; the step's MFMAs}
+  auto burst = [&](auto nc_, int k) {
+    constexpr int n = decltype(nc_)::value;
+    float bv[n][4];
+    float4 av[n][RT];
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      if (B_KC) {
+        const float4 t = *reinterpret_cast<const float4*>(Bp + k + 16 * i);
+        bv[i][0] = t.x; bv[i][1] = t.y; bv[i][2] = t.z; bv[i][3] = t.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bv[i][j] = Bp[(long)(k + 16 * i + j) * g.ldb];
+      }
+    }
+    auto load_a = [&](int i) {
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        if (A16) {
+          const f32x4 t = bf2f4(*reinterpret_cast<const uint2*>(Ah[rt] + k + 16 * i));
+          av[i][rt] = make_float4(t.x, t.y, t.z, t.w);
+        } else {
+          av[i][rt] = *reinterpret_cast<const float4*>(Ap[rt] + k + 16 * i);
+        }
+      }
+    };
+#pragma unroll
+    for (int i = 0; i < AD; ++i)
+      if (i < n) load_a(i);
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      if (i + AD < n) load_a(i + AD);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][rt].x, bv[i][0], acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][rt].y, bv[i][1], acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][rt].z, bv[i][2], acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][rt].w, bv[i][3], acc[rt], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  const SkinnyBursts nb = rmcl_skinny_bursts(kq / 16, BS);
+  int k = k_lo;
+  for (int b = 0; b < nb.full; ++b, k += 16 * BS) burst(std::integral_constant<int, BS>{}, k);
+  if constexpr (BS > 12) {
+    if (nb.mid) { burst(std::integral_constant<int, 12>{}, k); k += 16 * 12; }
+  }
+  for (int b = 0; b < nb.quad; ++b, k += 64) burst(std::integral_constant<int, 4>{}, k);
+  for (int b = 0; b < nb.single; ++b, k += 16) burst(std::integral_constant<int, 1>{}, k);
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][rt * 16 + 4 * gq + r][c] = acc[rt][r];
+  __syncthreads();
+  float* C = reinterpret_cast<float*>(g.C);
+  // the k-split kernel's epilogue, expression for expression: ROWS x 16 elements over 64 * NW threads, every global operand loaded
+  // for all of the thread's elements before the first store
+  constexpr int ELEMS = ROWS * 16, THREADS = 64 * NW, ITER = (ELEMS + THREADS - 1) / THREADS;
+  float bia[ITER], aux[ITER], oldc[ITER];
+#pragma unroll
+  for (int it = 0; it < ITER; ++it) {
+    const int i = threadIdx.x + it * THREADS, rl = i / 16, cl = i % 16, row = m0 + rl, n = n0 + cl;
+    const bool live = i < ELEMS && row < g.M && n < g.N;
+    bia[it] = (live && (g.epi & EPI_BIAS)) ? g.bias[n] : 0.f;
+    aux[it] = (live && (g.epi & (EPI_DGELU | EPI_RESIDUAL))) ? reinterpret_cast<const float*>(g.aux)[(long)row * g.ld_aux + n] : 0.f;
+    oldc[it] = (live && (g.epi & EPI_ACCUM)) ? C[(long)row * g.ldc + n] : 0.f;
+  }
+#pragma unroll
+  for (int it = 0; it < ITER; ++it) {
+    const int i = threadIdx.x + it * THREADS, rl = i / 16, cl = i % 16, row = m0 + rl, n = n0 + cl;
+    if (i >= ELEMS || row >= g.M || n >= g.N) continue;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += red[w][rl][cl];                                              // k order: wave 0 .. NW-1
+    v *= g.alpha;
+    if (g.epi & EPI_BIAS) v += bia[it];
+    const long ci = (long)row * g.ldc + n;
+    if (g.epi & EPI_SAVE_PREACT) reinterpret_cast<float*>(g.C2)[ci] = v;
+    if (g.epi & EPI_GELU) v = gelu_erf(v);
+    if (g.epi & EPI_TANH) v = tanhf(v);
+    if (g.epi & EPI_DGELU) v *= gelu_erf_grad(aux[it]);
+    const long drow = (long)row * (g.drop_row_mul > 0 ? g.drop_row_mul : 1);                         // dense row of this compact row (gemm.h)
+    if (g.epi & EPI_DROP_BWD) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ld_aux + n), g.drop_thresh, g.drop_inv_keep);
+    if (g.epi & EPI_DROPOUT) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ldc + n), g.drop_thresh, g.drop_inv_keep);
+    if (g.epi & EPI_RESIDUAL) v += aux[it];
+    if (g.epi & EPI_ACCUM) v += oldc[it];
+    C[ci] = v;
+    if (g.epi & EPI_DUP) reinterpret_cast<float*>(g.C2)[ci] = v;
+  }
+}
+
 bool rmcl_gemm_skinny_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc) {
   return a_kc && dt_in == RMCL_F32 && dt_out == RMCL_F32 && g.M <= 1024 && g.K % 16 == 0 && g.K >= 64 && g.splitk <= 1 &&
          g.nb1 * g.nb2 == 1 && (g.epi & ~(EPI_BIAS | EPI_TANH | EPI_ACCUM | EPI_GELU | EPI_SAVE_PREACT | EPI_DGELU | EPI_RESIDUAL | EPI_DUP | EPI_DROPOUT | EPI_DROP_BWD)) == 0 &&
@@ -539,7 +674,31 @@ bool rmcl_gemm_skinny_supported(const GemmArgs& g, int dt_in, int dt_out, int a_
 
 void rmcl_gemm_skinny_set_form(int v) { g_skinny_form = v; }
 
+// true when rmcl_launch_gemm_exact(g, f32, f32, a_kc = 1, b_kc) runs the streaming form - the only one that takes GemmArgs.a_bf16
+bool rmcl_gemm_skinny_streams(const GemmArgs& g, int b_kc) {
+  return g.A && g.B && g.C && g_skinny_form != 0 && g_skinny_form != 1 && rmcl_gemm_skinny_supported(g, RMCL_F32, RMCL_F32, 1) &&
+         rmcl_skinny_plan(g.M, g.N, g.K, b_kc != 0, g_gemm_share).ok && (!g.a_bf16 || (b_kc && g.K < 2048));
+}
+
+template <bool B_KC, int NW, int BS, bool A16>
+static void launch_skinny_stream(const GemmArgs& g, const SkinnyPlan& p, hipStream_t s) {
+  const dim3 grid(p.grid_x, p.grid_y), block(64 * NW);
+  if (p.rt == 4) RMCL_LAUNCH((gemm_skinny_stream_kernel<B_KC, NW, 4, BS, A16>), grid, block, 0, s, g);
+  else if (p.rt == 2) RMCL_LAUNCH((gemm_skinny_stream_kernel<B_KC, NW, 2, BS, A16>), grid, block, 0, s, g);
+  else RMCL_LAUNCH((gemm_skinny_stream_kernel<B_KC, NW, 1, BS, A16>), grid, block, 0, s, g);
+}
+
 int rmcl_launch_gemm_skinny(const GemmArgs& g, int b_kc, hipStream_t s) {
+  if (rmcl_gemm_skinny_streams(g, b_kc)) {
+    const SkinnyPlan p = rmcl_skinny_plan(g.M, g.N, g.K, b_kc != 0, g_gemm_share);
+    if (g.a_bf16) launch_skinny_stream<true, 4, rmcl_skinny_burst_len(true, 4), true>(g, p, s);
+    else if (b_kc && p.nw == 8) launch_skinny_stream<true, 8, rmcl_skinny_burst_len(true, 8), false>(g, p, s);
+    else if (b_kc) launch_skinny_stream<true, 4, rmcl_skinny_burst_len(true, 4), false>(g, p, s);
+    else if (p.nw == 8) launch_skinny_stream<false, 8, rmcl_skinny_burst_len(false, 8), false>(g, p, s);
+    else launch_skinny_stream<false, 4, rmcl_skinny_burst_len(false, 4), false>(g, p, s);
+    RMCL_CHECK_LAUNCH();
+    return 0;
+  }
   if (g_skinny_form != 0 && g.K % 64 == 0 && g.K >= 128) {
     // 8 waves (K split 8 ways) where the reduction is long and the grid small; 32-column tiles for very wide outputs
     // (round 4: 8 waves from K = 512 on measured -0.05 ms per step over six alternating runs, but the different fp32 summation order moved the

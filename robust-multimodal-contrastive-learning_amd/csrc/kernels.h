@@ -11,7 +11,10 @@ bool rmcl_gemm_fast_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc
 int rmcl_launch_gemm_fast_slab(const GemmArgs& g, float* slab, float* out, hipStream_t s);
 int rmcl_slab_reduce(const float* slab, float* out, long n, int nz, hipStream_t s);
 int rmcl_gemm_fast_get_cfg();
-void rmcl_gemm_skinny_set_form(int v);     // gemm_exact.hip: 0 = row-split skinny kernel only
+void rmcl_gemm_skinny_set_form(int v);     // gemm_exact.hip, rmcl_tune_set key 6: 0 = row-split skinny kernel only; 1 = the k-split kernel (A/B arm and
+                                           // bitwise reference of the streaming form); -1 (default) or 2 = the streaming k-split form (weights of a
+                                           // wave's K chunk fetched in one burst, 1 / 2 / 4 row tiles per workgroup) for K % 64 == 0, K >= 128, N < 4096
+bool rmcl_gemm_skinny_streams(const GemmArgs& g, int b_kc);   // rmcl_launch_gemm_exact(g, f32, f32, 1, b_kc) runs the streaming form (takes GemmArgs.a_bf16)
 bool rmcl_gemm_routes_to_tile192(const GemmArgs& g, int a_kc, int b_kc);
 bool rmcl_lnfold_centred();          // rmcl_tune_set key 11 (api.cpp): the shift-robust form of the LayerNorm fold is on (default)
 int rmcl_gemm_route_code(const GemmArgs& g, int dt_out, int a_kc, int b_kc);   // 0 128x128, 1 gemm_st, 2 gemm_sw, 3 gemm_dp, 4 / 5 256x256
