@@ -545,7 +545,8 @@ int rmcl_infonce_f32(const float* q, const float* k, const float* queue, int B, 
                      float grad_scale, float* dq, float* rows_out, float* loss_sum, void* workspace, void* stream);
 /* The same pass for the bf16 engine: logits and dq on the bf16 matrix cores with SPLIT operands (x = bf16(x) + bf16(x - bf16(x)),
  * three products per pair: 2^-16 relative per product, fp32 softmax / accumulation) - the fp32 queue is read as it is.
- * with_metrics = 0 (the PGD passes consume dq only): rows_out[6..8] (queue-distance means) are written as 0.              */
+ * with_metrics = 0 (the PGD passes consume dq only): rows_out[6..8] (queue-distance means) are written as 0, whichever kernel runs.
+ * At Kq % 256 == 128, and under rmcl_tune_set key 5 = 0, this entry runs the exact-f32 kernel of rmcl_infonce_f32 (no split products). */
 int rmcl_infonce_split_bf16(const float* q, const float* k, const float* queue, int B, int proj, int64_t Kq, float temperature,
                             float grad_scale, float* dq, float* rows_out, float* loss_sum, void* workspace, int with_metrics,
                             void* stream);

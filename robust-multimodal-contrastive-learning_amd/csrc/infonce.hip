@@ -21,7 +21,7 @@
 
 __global__ __launch_bounds__(256) void infonce_partial_kernel(const float* __restrict__ q, const float* __restrict__ queue, long Kq,
                                                               int B, float invT, float* __restrict__ part, float* __restrict__ dq_part,
-                                                              int Bpad) {
+                                                              int Bpad, int metrics) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* Qs = sm;                    // [PD][ILD]   Qs[c][j]
   float* qs = Qs + PD * ILD;         // [RT][ILD]   qs[i][c]
@@ -116,6 +116,7 @@ __global__ __launch_bounds__(256) void infonce_partial_kernel(const float* __res
     if (sub == 0 && r0 + row < B) {
       float* o = part + ((long)slice * Bpad + r0 + row) * NPART;
       o[0] = m; o[1] = z; o[2] = best; o[3] = __int_as_float((int)(j0 + bi));
+      if (!metrics) sd = sc = so = 0.f;                          // (split-bf16 entry with with_metrics = 0 landing here: rows_out[6..8] = 0)
       o[4] = sd; o[5] = sc; o[6] = so; o[7] = 0.f;
     }
   }
@@ -859,7 +860,7 @@ int rmcl_infonce(const float* q, const float* k, const float* queue, int B, int 
     RMCL_TRY(rmcl_set_max_lds(once2, reinterpret_cast<const void*>(infonce_partial2_kernel), (int)lds2));
     RMCL_LAUNCH(infonce_partial2_kernel, dim3(nparts, Bpad / RT), dim3(256), lds2, s, q, queue, Kq, B, 1.0f / T, part, dq_part, Bpad);
   } else {
-    RMCL_LAUNCH(infonce_partial_kernel, dim3(ns, Bpad / RT), dim3(256), lds, s, q, queue, Kq, B, 1.0f / T, part, dq_part, Bpad);
+    RMCL_LAUNCH(infonce_partial_kernel, dim3(ns, Bpad / RT), dim3(256), lds, s, q, queue, Kq, B, 1.0f / T, part, dq_part, Bpad, form != 2);
   }
   RMCL_CHECK_LAUNCH();
   if (g_infonce_fold >= 1)
