@@ -13,6 +13,14 @@
 #pragma once
 #include <stdint.h>
 
+// Epilogue order.  Every family starts with v = alpha * acc (+ bias) and ends with residual, accumulate, store; in between:
+//   skinny fp32 kernels (gemm_exact.hip, skinny_epilogue):   stash to C2, GELU, tanh, * GELU'(aux), * backward mask, * forward mask
+//   128x128 fp32 kernel (gemm_exact.hip, gemm_exact_kernel): * backward mask, * GELU'(aux), stash to C2, GELU, tanh, * forward mask
+//   bf16 4-column kernels (gemm_epi4.h; the 192-row tile kernels keep their own tails - other GELU polynomial, preloaded operands - in
+//   the same order):                                         * backward mask, * GELU'(aux), stash to C2, GELU, * forward mask
+// The two fp32 orders are NOT interchangeable: with d = GELU'(aux) and s = 1 / (1 - p), (v * d) * s and (v * s) * d round differently
+// whenever s is no power of two, and a stash taken after the gradient factors is another value than one taken before them (no caller
+// combines them, the skinny launcher refuses EPI_DUP with EPI_SAVE_PREACT).  Both are on the fp32 parity path, so each keeps its order.
 enum {
   EPI_BIAS = 1,         // + bias[n]
   EPI_GELU = 2,         // exact-erf GELU on the result
@@ -22,9 +30,9 @@ enum {
   EPI_ATOMIC = 32,      // split-K: atomicAdd into fp32 C (C must be fp32, pre-zeroed or accumulating)
   EPI_ACCUM = 64,       // C += result (fp32 or bf16 read-modify-write; not with split-K)
   EPI_TANH = 128,       // tanh on the result
-  EPI_COLSUM = 256,
+  EPI_COLSUM = 256,     // TN only (the short-K fp32 kernel, gemm_exact.hip): also adds the column sums of A over k (= the bias gradient) into colsum[m]
   EPI_DROPOUT = 512,    // dropout on the result (after bias / GELU, before the residual add): mask(drop_seed, m*ldc+n)
-  EPI_DROP_BWD = 1024,  // with EPI_DGELU: also multiply by the forward dropout mask of the hidden activation     // TN only: blocks with blockIdx.y==0 atomically add column sums of A (= bias grad) into bias_grad[m]
+  EPI_DROP_BWD = 1024,  // with EPI_DGELU: also multiply by the forward dropout mask of the hidden activation
   // LayerNorm folded into the GEMM that consumes it (bf16 192x192 / 192x384 kernels only, N_in = ln_cols):
   //   y = LN(x) W^T + b  =  rstd_m * (bf16(x) W'^T - mean_m * s_n) + c_n,  W' = W * gamma (columns), s_n = sum_k W'_nk, c_n = W beta + b
   EPI_LNFOLD = 2048,    // consumer: A = bf16 copy of the residual stream, B = W'; row statistics from ln_part; per-column ln_s / ln_c

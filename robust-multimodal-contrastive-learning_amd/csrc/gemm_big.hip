@@ -11,6 +11,7 @@
 // this tile as well and measured 10-25 % SLOWER than this simple form (GEMM notes).
 #include "rmcl_common.h"
 #include "kernels.h"
+#include "gemm_epi4.h"
 
 #define GBM2 256
 #define GBN2 256
@@ -146,7 +147,6 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmArgs g, int tiles_
     __syncthreads();
   }
 
-  const int epi = g.epi;
   TO* C = reinterpret_cast<TO*>(g.C) + zoff;
   TO* C2 = reinterpret_cast<TO*>(g.C2);
 #pragma unroll
@@ -154,50 +154,7 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmArgs g, int tiles_
     const int m = m0 + wm * 128 + i * 16 + (lane & 15);
     if (m >= g.M) continue;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + 4 * (lane >> 4);
-      float v[4] = {g.alpha * acc[i][j][0], g.alpha * acc[i][j][1], g.alpha * acc[i][j][2], g.alpha * acc[i][j][3]};
-      if (epi & EPI_BIAS) {
-        const float4 b = *reinterpret_cast<const float4*>(g.bias + n);
-        v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-      }
-      if (epi & EPI_DGELU) {
-        const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(g.aux) + (long)m * g.ld_aux + n);
-        v[0] *= gelu_fast_grad(__uint_as_float(u.x << 16)); v[1] *= gelu_fast_grad(__uint_as_float(u.x & 0xffff0000u));
-        v[2] *= gelu_fast_grad(__uint_as_float(u.y << 16)); v[3] *= gelu_fast_grad(__uint_as_float(u.y & 0xffff0000u));
-      }
-      const long ci = (long)m * g.ldc + n;
-      if (epi & EPI_SAVE_PREACT) {
-        if constexpr (sizeof(TO) == 2) {
-          uint2 pk;
-          pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-          pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-          *reinterpret_cast<uint2*>(C2 + ci) = pk;
-        } else {
-          *reinterpret_cast<float4*>(C2 + ci) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-      }
-      if (epi & EPI_GELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = gelu_fast(v[r]);
-      }
-      if (epi & EPI_RESIDUAL) {
-        const float4 r = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(g.aux) + (long)m * g.ld_aux + n);
-        v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
-      }
-      if constexpr (sizeof(TO) == 2) {
-        uint2 pk;
-        pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-        *reinterpret_cast<uint2*>(C + ci) = pk;
-      } else {
-        if (epi & EPI_ACCUM) {
-          const float4 o = *reinterpret_cast<const float4*>(C + ci);
-          v[0] += o.x; v[1] += o.y; v[2] += o.z; v[3] += o.w;
-        }
-        *reinterpret_cast<float4*>(C + ci) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
+    for (int j = 0; j < 4; ++j) epi4<TO, false>(g, g.epi, C, C2, acc[i][j], m, n0 + wn * 64 + j * 16 + 4 * (lane >> 4));
   }
 }
 

@@ -161,6 +161,8 @@ __global__ __launch_bounds__(256) void gemm_exact_kernel(GemmArgs g) {
   }
 
   // epilogue.  C/D map of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+  // Deliberately NOT skinny_epilogue: this kernel applies the backward dropout mask before GELU' and stashes after both (gemm.h,
+  // "Epilogue order"); merging the two orders would change bits of the fp32 parity path.  It also converts types and knows split-K.
   const int epi = g.epi;
   const bool first_slice = (g.splitk <= 1) || (blockIdx.z == 0);
 #pragma unroll
@@ -271,6 +273,7 @@ __global__ __launch_bounds__(256) void gemm_tn_shortk_kernel(GemmArgs g) {
     }
   }
   float* C = reinterpret_cast<float*>(g.C);
+  // The tail is alpha * acc + old C and nothing else (one fma; rmcl_gemm_tn_shortk_takes admits no other flag), so it stays literal.
   // C += : every old value of the tile is loaded BEFORE the first store.  "load, add, store" per element cannot be reordered by the
   // compiler (the stores may alias the next loads for all it knows) and ran as 64 serial round trips per lane (tools/st_trace.py
   // found the same pattern in the weight-gradient launch's epilogue)
@@ -306,8 +309,7 @@ int rmcl_launch_gemm_exact(const GemmArgs& g, int dt_in, int dt_out, int a_kc, i
   RMCL_REQUIRE(!g.a_bf16 || (a_kc && dt_in == RMCL_F32 && dt_out == RMCL_F32 && g.M > 0 && g.N > 0 && rmcl_gemm_skinny_streams(g, b_kc)),
                "gemm: a bf16 A operand beside fp32 weights is the streaming skinny kernel's alone (rmcl_tune_set key 6; K % 64 == 0, 128 <= K < 2048, N < 4096, weights [N][K])");
   if (g.A && g.B && g.C && g.M > 0 && g.N > 0 && rmcl_gemm_skinny_supported(g, dt_in, dt_out, a_kc)) return rmcl_launch_gemm_skinny(g, b_kc, s);
-  if (g.A && g.B && g.C && g.M > 0 && g.N > 0 && !a_kc && !b_kc && dt_in == RMCL_F32 && dt_out == RMCL_F32 && g.K >= 1 && g.K <= 256 &&
-      g.splitk <= 1 && g.nb1 * g.nb2 == 1 && (g.epi & ~(EPI_ACCUM | EPI_COLSUM)) == 0 && (!(g.epi & EPI_COLSUM) || g.colsum) && g_skinny_form != 0) {
+  if (!a_kc && !b_kc && dt_in == RMCL_F32 && dt_out == RMCL_F32 && (!(g.epi & EPI_COLSUM) || g.colsum) && rmcl_gemm_tn_shortk_takes(g)) {
     RMCL_LAUNCH(gemm_tn_shortk_kernel, dim3(cdiv(g.N, 128), cdiv(g.M, 128)), dim3(256), 0, s, g);
     RMCL_CHECK_LAUNCH();
     return 0;
@@ -331,6 +333,77 @@ int rmcl_launch_gemm_exact(const GemmArgs& g, int dt_in, int dt_out, int a_kc, i
   if (dt_in == RMCL_F32 && dt_out == RMCL_BF16) return launch_layout<float, bf16_t>(g, a_kc, b_kc, grid, s);
   rmcl_set_error("gemm: unsupported dtype combination");
   return -1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The element-wise tail of the skinny kernels below, written once (row-split and k-split kernel; the streaming kernel carries a literal
+// copy of it and of skinny_reduce_store, for a measured reason given there).  Order (gemm.h, "Epilogue order"): alpha, bias, stash to C2,
+// GELU, tanh, GELU'(aux), backward dropout mask, forward dropout mask, residual, accumulate, store, second copy.
+// `ops` is the OPERAND SOURCE: bias() / aux() / oldc() of this element.  Where the operands come from is not cosmetic under
+// -ffp-contract=fast: handed preloaded registers, the row-split kernel's `alpha * acc + bias` is if-converted and fused into an fma
+// (other bits); loading at the point of use keeps its branches, and with them its mul and its add.  So the row-split kernel passes
+// SkinnyOpsAtUse and the k-split forms, which must preload (skinny_reduce_store), pass SkinnyOpsLoaded.
+// ---------------------------------------------------------------------------------------------------
+struct SkinnyOpsAtUse {
+  const GemmArgs& g;
+  int row, n;
+  __device__ __forceinline__ float bias() const { return g.bias[n]; }
+  __device__ __forceinline__ float aux() const { return reinterpret_cast<const float*>(g.aux)[(long)row * g.ld_aux + n]; }
+  __device__ __forceinline__ float oldc() const { return reinterpret_cast<const float*>(g.C)[(long)row * g.ldc + n]; }
+};
+struct SkinnyOpsLoaded {
+  float b, a, o;
+  __device__ __forceinline__ float bias() const { return b; }
+  __device__ __forceinline__ float aux() const { return a; }
+  __device__ __forceinline__ float oldc() const { return o; }
+};
+
+// v = the k-sum of element (row, n), row < M and n < N
+template <typename Ops>
+__device__ __forceinline__ void skinny_epilogue(const GemmArgs& g, float v, int row, int n, const Ops& ops) {
+  float* C = reinterpret_cast<float*>(g.C);
+  v *= g.alpha;
+  if (g.epi & EPI_BIAS) v += ops.bias();
+  const long ci = (long)row * g.ldc + n;
+  if (g.epi & EPI_SAVE_PREACT) reinterpret_cast<float*>(g.C2)[ci] = v;
+  if (g.epi & EPI_GELU) v = gelu_erf(v);
+  if (g.epi & EPI_TANH) v = tanhf(v);
+  if (g.epi & EPI_DGELU) v *= gelu_erf_grad(ops.aux());
+  const long drow = (long)row * (g.drop_row_mul > 0 ? g.drop_row_mul : 1);                           // dense row of this compact row (gemm.h)
+  if (g.epi & EPI_DROP_BWD) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ld_aux + n), g.drop_thresh, g.drop_inv_keep);
+  if (g.epi & EPI_DROPOUT) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ldc + n), g.drop_thresh, g.drop_inv_keep);
+  if (g.epi & EPI_RESIDUAL) v += ops.aux();
+  if (g.epi & EPI_ACCUM) v += ops.oldc();
+  C[ci] = v;
+  if (g.epi & EPI_DUP) reinterpret_cast<float*>(g.C2)[ci] = v;
+}
+
+// Second half of the k-split kernel (and, as a literal copy, of the streaming kernel): the NW partial tiles of ROWS x NT elements lie in
+// LDS (after the barrier); every thread sums its elements over the waves in k order and applies the tail.
+template <int NW, int ROWS, int NT>
+__device__ __forceinline__ void skinny_reduce_store(const GemmArgs& g, const float (&red)[NW][ROWS][NT + 1], int m0, int n0) {
+  // every global operand of the epilogue (bias, aux, old C) is loaded for ALL of the thread's elements before the first store: in
+  // "load, compute, store" order per element the loads of element i + 1 cannot pass the store of element i (possible alias)
+  constexpr int ELEMS = ROWS * NT, THREADS = 64 * NW, ITER = (ELEMS + THREADS - 1) / THREADS;
+  constexpr bool FULL = ELEMS % THREADS == 0;                  // no thread runs past the tile: the guard compiles out
+  float bia[ITER], aux[ITER], oldc[ITER];
+#pragma unroll
+  for (int it = 0; it < ITER; ++it) {
+    const int i = threadIdx.x + it * THREADS, rl = i / NT, cl = i % NT, row = m0 + rl, n = n0 + cl;
+    const bool live = (FULL || i < ELEMS) && row < g.M && n < g.N;
+    bia[it] = (live && (g.epi & EPI_BIAS)) ? g.bias[n] : 0.f;
+    aux[it] = (live && (g.epi & (EPI_DGELU | EPI_RESIDUAL))) ? reinterpret_cast<const float*>(g.aux)[(long)row * g.ld_aux + n] : 0.f;
+    oldc[it] = (live && (g.epi & EPI_ACCUM)) ? reinterpret_cast<const float*>(g.C)[(long)row * g.ldc + n] : 0.f;
+  }
+#pragma unroll
+  for (int it = 0; it < ITER; ++it) {
+    const int i = threadIdx.x + it * THREADS, rl = i / NT, cl = i % NT, row = m0 + rl, n = n0 + cl;
+    if ((!FULL && i >= ELEMS) || row >= g.M || n >= g.N) continue;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += red[w][rl][cl];                                              // k order: wave 0 .. NW-1
+    skinny_epilogue(g, v, row, n, SkinnyOpsLoaded{bia[it], aux[it], oldc[it]});
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -397,26 +470,10 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs g) {
   f32x4 acc;
 #pragma unroll
   for (int r = 0; r < 4; ++r) acc[r] = (ac[0][r] + ac[1][r]) + (ac[2][r] + ac[3][r]);
-  float* C = reinterpret_cast<float*>(g.C);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = blockIdx.y * 64 + wave * 16 + 4 * gq + r;
-    if (row < g.M && n < g.N) {
-      float v = g.alpha * acc[r];
-      if (g.epi & EPI_BIAS) v += g.bias[n];
-      const long ci = (long)row * g.ldc + n;
-      if (g.epi & EPI_SAVE_PREACT) reinterpret_cast<float*>(g.C2)[ci] = v;
-      if (g.epi & EPI_GELU) v = gelu_erf(v);
-      if (g.epi & EPI_TANH) v = tanhf(v);
-      if (g.epi & EPI_DGELU) v *= gelu_erf_grad(reinterpret_cast<const float*>(g.aux)[(long)row * g.ld_aux + n]);
-      const long drow = (long)row * (g.drop_row_mul > 0 ? g.drop_row_mul : 1);                       // dense row of this compact row (gemm.h)
-      if (g.epi & EPI_DROP_BWD) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ld_aux + n), g.drop_thresh, g.drop_inv_keep);
-      if (g.epi & EPI_DROPOUT) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ldc + n), g.drop_thresh, g.drop_inv_keep);
-      if (g.epi & EPI_RESIDUAL) v += reinterpret_cast<const float*>(g.aux)[(long)row * g.ld_aux + n];
-      if (g.epi & EPI_ACCUM) v += C[ci];
-      C[ci] = v;
-      if (g.epi & EPI_DUP) reinterpret_cast<float*>(g.C2)[ci] = v;
-    }
+    if (row < g.M && n < g.N) skinny_epilogue(g, acc[r], row, n, SkinnyOpsAtUse{g, row, n});
   }
 }
 
@@ -500,41 +557,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_ksplit_kernel(GemmArgs g)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[wave][rt * 16 + 4 * gq + r][ct * 16 + c] = acc[rt][ct][r];
   __syncthreads();
-  float* C = reinterpret_cast<float*>(g.C);
-  // every global operand of the epilogue (bias, aux, old C) is loaded for ALL of the thread's elements before the first store: in
-  // "load, compute, store" order per element the loads of element i + 1 cannot pass the store of element i (possible alias)
-  constexpr int ITER = NT / NW;                                // 64 * NT elements over 64 * NW threads
-  float bia[ITER], aux[ITER], oldc[ITER];
-#pragma unroll
-  for (int it = 0; it < ITER; ++it) {
-    const int i = threadIdx.x + it * 64 * NW, rl = i / NT, cl = i % NT, row = m0 + rl, n = n0 + cl;
-    const bool live = row < g.M && n < g.N;
-    bia[it] = (live && (g.epi & EPI_BIAS)) ? g.bias[n] : 0.f;
-    aux[it] = (live && (g.epi & (EPI_DGELU | EPI_RESIDUAL))) ? reinterpret_cast<const float*>(g.aux)[(long)row * g.ld_aux + n] : 0.f;
-    oldc[it] = (live && (g.epi & EPI_ACCUM)) ? C[(long)row * g.ldc + n] : 0.f;
-  }
-#pragma unroll
-  for (int it = 0; it < ITER; ++it) {
-    const int i = threadIdx.x + it * 64 * NW, rl = i / NT, cl = i % NT, row = m0 + rl, n = n0 + cl;
-    if (row >= g.M || n >= g.N) continue;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += red[w][rl][cl];                                              // k order: wave 0 .. NW-1
-    v *= g.alpha;
-    if (g.epi & EPI_BIAS) v += bia[it];
-    const long ci = (long)row * g.ldc + n;
-    if (g.epi & EPI_SAVE_PREACT) reinterpret_cast<float*>(g.C2)[ci] = v;
-    if (g.epi & EPI_GELU) v = gelu_erf(v);
-    if (g.epi & EPI_TANH) v = tanhf(v);
-    if (g.epi & EPI_DGELU) v *= gelu_erf_grad(aux[it]);
-    const long drow = (long)row * (g.drop_row_mul > 0 ? g.drop_row_mul : 1);                         // dense row of this compact row (gemm.h)
-    if (g.epi & EPI_DROP_BWD) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ld_aux + n), g.drop_thresh, g.drop_inv_keep);
-    if (g.epi & EPI_DROPOUT) v *= drop_scale(g.drop_seed, (uint32_t)(drow * g.ldc + n), g.drop_thresh, g.drop_inv_keep);
-    if (g.epi & EPI_RESIDUAL) v += aux[it];
-    if (g.epi & EPI_ACCUM) v += oldc[it];
-    C[ci] = v;
-    if (g.epi & EPI_DUP) reinterpret_cast<float*>(g.C2)[ci] = v;
-  }
+  skinny_reduce_store<NW, 64, NT>(g, red, m0, n0);
 }
 
 // Third form: the k-split kernel above with its loads re-timed and its rows cut to what the problem has.  The ARITHMETIC is the
@@ -627,8 +650,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_stream_kernel(GemmArgs g)
     for (int r = 0; r < 4; ++r) red[wave][rt * 16 + 4 * gq + r][c] = acc[rt][r];
   __syncthreads();
   float* C = reinterpret_cast<float*>(g.C);
-  // the k-split kernel's epilogue, expression for expression: ROWS x 16 elements over 64 * NW threads, every global operand loaded
-  // for all of the thread's elements before the first store
+  // skinny_reduce_store + skinny_epilogue, expression for expression, but LITERAL: behind the helper every instantiation kept its
+  // floating-point instructions and gave the same bits, yet the compiler laid the tail's blocks out differently and the [K][N]
+  // instantiations measured 0.1 - 0.3 us (1 - 2 %) slower per launch than the parent's run-to-run spread (DESIGN "GEMM epilogues").  A
+  // change to either copy goes into both; tests/test_gemm_skinny_stream_gpu.py and tests/test_encoder_skinny_stream_gpu.py (dropout
+  // tails) hold them to each other bit for bit.  ROWS x 16 elements over 64 * NW threads, every global operand loaded for all of the
+  // thread's elements before the first store
   constexpr int ELEMS = ROWS * 16, THREADS = 64 * NW, ITER = (ELEMS + THREADS - 1) / THREADS;
   float bia[ITER], aux[ITER], oldc[ITER];
 #pragma unroll
@@ -699,23 +726,18 @@ int rmcl_launch_gemm_skinny(const GemmArgs& g, int b_kc, hipStream_t s) {
     RMCL_CHECK_LAUNCH();
     return 0;
   }
-  if (g_skinny_form != 0 && g.K % 64 == 0 && g.K >= 128) {
-    // 8 waves (K split 8 ways) where the reduction is long and the grid small; 32-column tiles for very wide outputs
-    // (round 4: 8 waves from K = 512 on measured -0.05 ms per step over six alternating runs, but the different fp32 summation order moved the
-    // 4-sample BatchNorm golden of the Barlow-Twins step from 0.9 % to 1.03 % on one gradient norm - bound 1 % - so the threshold stays)
-    const bool w8 = g.K % 128 == 0 && g.K >= 2048 && g.N < 4096;
-    if (g.N >= 4096) {
-      dim3 grid(cdiv(g.N, 32), cdiv(g.M, 64));
-      if (b_kc) RMCL_LAUNCH((gemm_skinny_ksplit_kernel<true, 32, 4>), grid, dim3(256), 0, s, g);
-      else RMCL_LAUNCH((gemm_skinny_ksplit_kernel<false, 32, 4>), grid, dim3(256), 0, s, g);
-    } else if (w8) {
-      dim3 grid(cdiv(g.N, 16), cdiv(g.M, 64));
-      if (b_kc) RMCL_LAUNCH((gemm_skinny_ksplit_kernel<true, 16, 8>), grid, dim3(512), 0, s, g);
-      else RMCL_LAUNCH((gemm_skinny_ksplit_kernel<false, 16, 8>), grid, dim3(512), 0, s, g);
+  const SkinnyKsplitPlan kp = rmcl_skinny_ksplit_plan(g.M, g.N, g.K);
+  if (g_skinny_form != 0 && kp.ok) {
+    const dim3 grid(kp.grid_x, kp.grid_y), block(64 * kp.nw);
+    if (kp.nt == 32) {
+      if (b_kc) RMCL_LAUNCH((gemm_skinny_ksplit_kernel<true, 32, 4>), grid, block, 0, s, g);
+      else RMCL_LAUNCH((gemm_skinny_ksplit_kernel<false, 32, 4>), grid, block, 0, s, g);
+    } else if (kp.nw == 8) {
+      if (b_kc) RMCL_LAUNCH((gemm_skinny_ksplit_kernel<true, 16, 8>), grid, block, 0, s, g);
+      else RMCL_LAUNCH((gemm_skinny_ksplit_kernel<false, 16, 8>), grid, block, 0, s, g);
     } else {
-      dim3 grid(cdiv(g.N, 16), cdiv(g.M, 64));
-      if (b_kc) RMCL_LAUNCH((gemm_skinny_ksplit_kernel<true, 16, 4>), grid, dim3(256), 0, s, g);
-      else RMCL_LAUNCH((gemm_skinny_ksplit_kernel<false, 16, 4>), grid, dim3(256), 0, s, g);
+      if (b_kc) RMCL_LAUNCH((gemm_skinny_ksplit_kernel<true, 16, 4>), grid, block, 0, s, g);
+      else RMCL_LAUNCH((gemm_skinny_ksplit_kernel<false, 16, 4>), grid, block, 0, s, g);
     }
     RMCL_CHECK_LAUNCH();
     return 0;

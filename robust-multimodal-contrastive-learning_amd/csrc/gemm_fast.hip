@@ -22,6 +22,7 @@
 // reproducible, no float atomics).
 #include "rmcl_common.h"
 #include "kernels.h"
+#include "gemm_epi4.h"
 
 #define FBM 128
 #define FBN 128
@@ -180,7 +181,6 @@ __global__ __launch_bounds__(256, 2) void gemm_fast_kernel(GemmArgs g, int tiles
       if (last) {
         // epilogue (registers -> global only, so it overlaps the in-flight prefetch):
         // lane owns row m = ..+(lane&15), columns n..n+3 with n = ..+4*(lane>>4)
-        const int epi = g.epi;
         TO* C = reinterpret_cast<TO*>(g.C) + cur.zoff;
         TO* C2 = reinterpret_cast<TO*>(g.C2);
 #pragma unroll
@@ -189,55 +189,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fast_kernel(GemmArgs g, int tiles
           if (m >= g.M) continue;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const int n = cur.n0 + wn * 64 + j * 16 + 4 * (lane >> 4);
-            float v[4] = {g.alpha * acc[i][j][0], g.alpha * acc[i][j][1], g.alpha * acc[i][j][2], g.alpha * acc[i][j][3]};
-            if (epi & EPI_BIAS) {
-              const float4 b = *reinterpret_cast<const float4*>(g.bias + n);
-              v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-            }
-            if (DROP && (epi & EPI_DROP_BWD)) {
-              const uint32_t di = (uint32_t)((long)m * g.ld_aux + n);
-              drop_scale4(g.drop_seed, di, g.drop_thresh, g.drop_inv_keep, v[0], v[1], v[2], v[3]);
-            }
-            if (epi & EPI_DGELU) {
-              const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(g.aux) + (long)m * g.ld_aux + n);
-              v[0] *= gelu_fast_grad(__uint_as_float(u.x << 16)); v[1] *= gelu_fast_grad(__uint_as_float(u.x & 0xffff0000u));
-              v[2] *= gelu_fast_grad(__uint_as_float(u.y << 16)); v[3] *= gelu_fast_grad(__uint_as_float(u.y & 0xffff0000u));
-            }
-            const long ci = (long)m * g.ldc + n;
-            if (epi & EPI_SAVE_PREACT) {
-              if constexpr (sizeof(TO) == 2) {
-                uint2 pk;
-                pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-                pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-                *reinterpret_cast<uint2*>(C2 + ci) = pk;
-              } else {
-                *reinterpret_cast<float4*>(C2 + ci) = make_float4(v[0], v[1], v[2], v[3]);
-              }
-            }
-            if (epi & EPI_GELU) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) v[r] = gelu_fast(v[r]);
-            }
-            if (DROP && (epi & EPI_DROPOUT)) {
-              drop_scale4(g.drop_seed, (uint32_t)ci, g.drop_thresh, g.drop_inv_keep, v[0], v[1], v[2], v[3]);
-            }
-            if (epi & EPI_RESIDUAL) {
-              const float4 r = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(g.aux) + (long)m * g.ld_aux + n);
-              v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
-            }
-            if constexpr (sizeof(TO) == 2) {
-              uint2 pk;
-              pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-              pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-              *reinterpret_cast<uint2*>(C + ci) = pk;
-            } else {
-              if (epi & EPI_ACCUM) {
-                const float4 o = *reinterpret_cast<const float4*>(C + ci);
-                v[0] += o.x; v[1] += o.y; v[2] += o.z; v[3] += o.w;
-              }
-              *reinterpret_cast<float4*>(C + ci) = make_float4(v[0], v[1], v[2], v[3]);
-            }
+            epi4<TO, DROP>(g, g.epi, C, C2, acc[i][j], m, cur.n0 + wn * 64 + j * 16 + 4 * (lane >> 4));
             // keep the 16 per-tile epilogues from being interleaved: hoisting every tile's bias / residual /
             // aux loads to the top costs > 160 live VGPRs and spills (121 spilled registers measured)
             __builtin_amdgcn_sched_barrier(0);

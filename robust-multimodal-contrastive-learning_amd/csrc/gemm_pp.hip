@@ -210,6 +210,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g, int tiles_m, i
   }
   if (wm == 0) __builtin_amdgcn_s_barrier();
 
+  // bias-only tail, kept literal (not epi4 of gemm_epi4.h): the launcher admits nothing but EPI_BIAS, and the general tail would put dead
+  // branches into a prototype kernel
   const int epi = g.epi;
   TO* C = reinterpret_cast<TO*>(g.C);
 #pragma unroll
@@ -225,14 +227,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g, int tiles_m, i
         v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
       }
       const long ci = (long)m * g.ldc + n;
-      if constexpr (sizeof(TO) == 2) {
-        uint2 pk;
-        pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-        *reinterpret_cast<uint2*>(C + ci) = pk;
-      } else {
-        *reinterpret_cast<float4*>(C + ci) = make_float4(v[0], v[1], v[2], v[3]);
-      }
+      store4<TO>(C + ci, v);
     }
   }
 }

@@ -271,7 +271,7 @@ __device__ __forceinline__ void st_epilogue(const f32x4 (&acc)[6][3], const Gemm
         v[2] *= gelu_poly_grad(__uint_as_float(u.y << 16)); v[3] *= gelu_poly_grad(__uint_as_float(u.y & 0xffff0000u));
       }
       const long ci = (long)m * g.ldc + nb + j * 16;
-      if ((epi & EPI_SAVE_PREACT) && live) st_store4<TO>(C2 + ci, v);
+      if ((epi & EPI_SAVE_PREACT) && live) store4<TO>(C2 + ci, v);
       if (epi & EPI_GELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_poly(v[r]);
@@ -286,7 +286,7 @@ __device__ __forceinline__ void st_epilogue(const f32x4 (&acc)[6][3], const Gemm
           v[0] += o.x; v[1] += o.y; v[2] += o.z; v[3] += o.w;
         }
       }
-      if (live) st_store4<TO>(C + ci, v);
+      if (live) store4<TO>(C + ci, v);
     }
   }
 }

@@ -14,18 +14,6 @@ typedef const __attribute__((address_space(1))) void glb_void;
 #define ST_STAMP(i)
 #endif
 
-template <typename TO>
-__device__ __forceinline__ void st_store4(TO* p, const float (&v)[4]) {
-  if constexpr (sizeof(TO) == 2) {
-    uint2 pk;
-    pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    *reinterpret_cast<uint2*>(p) = pk;
-  } else {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
 enum { ST_AUX_NONE = 0, ST_AUX_RES = 1, ST_AUX_DGELU = 2 };
 
 struct STTile {
@@ -320,7 +308,7 @@ __device__ __forceinline__ void st_epilogue_lds(const f32x4 (&acc)[6][3], const 
           const long ci = (long)m * g.ldc + nb + j * 16;
           if (!PLAIN && (epi & EPI_SAVE_PREACT) && live) {
             const float t[4] = {v.x, v.y, v.z, v.w};
-            st_store4<TO>(C2 + ci, t);
+            store4<TO>(C2 + ci, t);
           }
           if (!PLAIN && (epi & EPI_GELU)) v = gelu_poly4(v);
           if constexpr (DROP && (DM & 1) != 0) {

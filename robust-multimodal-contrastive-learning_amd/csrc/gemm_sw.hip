@@ -182,18 +182,6 @@ __device__ __forceinline__ void sw_ktile(f32x4 (&acc)[6][6], const SWCtx& c, con
   SW_PHASE_END();
 }
 
-template <typename TO>
-__device__ __forceinline__ void sw_store4(TO* p, const float (&v)[4]) {
-  if constexpr (sizeof(TO) == 2) {
-    uint2 pk;
-    pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    *reinterpret_cast<uint2*>(p) = pk;
-  } else {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
 // LNF = 1: LayerNorm folded into this GEMM (EPI_LNFOLD, gemm.h): A = bf16 copy of the residual stream, B = W * gamma;
 // v = rstd_m * (acc - mean_m * s_n) + c_n with the row statistics summed from the producer's partials into LDS.
 // DROP (bf16 outputs only): the dropout epilogues of the training-realistic configuration (drop_rate 0.1, config.py:57) as separate
@@ -627,12 +615,12 @@ __global__ __launch_bounds__(512) void gemm_sw_kernel(GemmArgs g, int tiles_m, i
             v[2] *= gelu_poly_grad(__uint_as_float(u.y << 16)); v[3] *= gelu_poly_grad(__uint_as_float(u.y & 0xffff0000u));
           }
           const long ci = (long)m * g.ldc + nb + j * 16;
-          if ((epi & EPI_SAVE_PREACT) && live) sw_store4<TO>(C2 + ci, v);
+          if ((epi & EPI_SAVE_PREACT) && live) store4<TO>(C2 + ci, v);
           if (epi & EPI_GELU) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = gelu_poly(v[r]);
           }
-          if (live) sw_store4<TO>(C + ci, v);
+          if (live) store4<TO>(C + ci, v);
         }
       }
     }

@@ -1,4 +1,4 @@
-// Stand-alone check of the streaming skinny GEMM's host-side selection (skinny_select.h): every M = 1 .. 1024 at the (N, K) of the
+// Stand-alone check of the k-split skinny GEMMs' host-side selection (skinny_select.h): every M = 1 .. 1024 at the (N, K) of the
 // contrastive step and of the tests, both weight layouts, 1 .. 8 chains sharing the chip.  Built and run under the host sanitizers by
 // tests/test_gemm_skinny_select_cpu.py; needs no GPU.  Exit status 0 = every assertion held.
 #include <cstdio>
@@ -27,6 +27,11 @@ int main() {
           CHECK(p.ok);
           CHECK(p.rt == 1 || p.rt == 2 || p.rt == 4);
           CHECK(p.nw == ((K % 128 == 0 && K >= 2048) ? 8 : 4));                 // the k-split kernel's rule: the K split is arithmetic
+          CHECK(rmcl_skinny_waves(K) == ((K % 128 == 0 && K >= 2048) ? 8 : 4));
+          // both plans apply here: they name the same K split, or the two forms could not agree bit for bit
+          const SkinnyKsplitPlan kp = rmcl_skinny_ksplit_plan(M, N, K);
+          CHECK(kp.ok && kp.nt == 16 && kp.nw == p.nw);
+          CHECK(kp.grid_x == p.grid_x && (long)kp.grid_y * 64 >= M && ((long)kp.grid_y - 1) * 64 < M && K % (16 * kp.nw) == 0);
           CHECK(K % (16 * p.nw) == 0 && p.nsteps * 16 * p.nw == K);
           CHECK(p.grid_x * 16 >= N && (p.grid_x - 1) * 16 < N);
           CHECK(p.grid_y >= 1 && (long)p.grid_y * 16 * p.rt >= M);              // every row is covered
@@ -58,6 +63,16 @@ int main() {
     // shapes the streaming form leaves to the other kernels
     CHECK(!rmcl_skinny_plan(64, 8192, 2048, true, 1).ok && !rmcl_skinny_plan(64, 768, 64, true, 1).ok && !rmcl_skinny_plan(64, 768, 720, true, 1).ok);
     CHECK(!rmcl_skinny_plan(0, 768, 768, true, 1).ok);
+    // the k-split kernel alone: 32-column tiles get 4 waves whatever K says; short or ragged K goes to the row-split kernel
+    for (K = 128; K <= 8192; K += 64)
+      for (M = 1; M <= 1024; M += 33) {
+        N = 8192;
+        const SkinnyKsplitPlan kp = rmcl_skinny_ksplit_plan(M, N, K);
+        CHECK(kp.ok && kp.nt == 32 && kp.nw == 4 && kp.grid_x == 256 && (long)kp.grid_y * 64 >= M && ((long)kp.grid_y - 1) * 64 < M);
+        N = 4095;
+        CHECK(rmcl_skinny_ksplit_plan(M, N, K).nt == 16 && rmcl_skinny_ksplit_plan(M, N, K).nw == ((K % 128 == 0 && K >= 2048) ? 8 : 4));
+      }
+    CHECK(!rmcl_skinny_ksplit_plan(64, 768, 64).ok && !rmcl_skinny_ksplit_plan(64, 768, 720).ok && rmcl_skinny_ksplit_plan(64, 768, 128).ok);
   }
   std::printf("skinny_select_check: %ld plans ok\n", checked);
   return 0;

@@ -2,7 +2,9 @@
 GEMMs of the tail and the heads in the streaming form (rmcl_tune_set key 6 at its default; the tail's proj then reads the cls rows of the
 bf16 attention output in place, no gather launch) against the same pass on the k-split kernel (key 6 = 1).  D = 192, mlp = 768, 3 heads,
 N = 24 + 1 + 48 = 73 tokens: the tail's GEMMs have K = 192 (three single-step bursts: a chunk as long as the A ring) and K = 768 (the
-12-step burst), both weight layouts.  B = 4 and B = 3: one partial row tile either way, an odd row count once.
+12-step burst), both weight layouts.  B = 4 and B = 3: one partial row tile either way, an odd row count once.  Dropout p = 0 and
+p = 0.1 (fixed non-zero seed): at 0.1 the tail's GEMMs run their dropout epilogues (EPI_DROPOUT wherever the encoder's with_drop sets it on the tail's proj /
+fc1 / fc2 launches, EPI_DROP_BWD in fc2's data gradient, both on compact rows through drop_row_mul) - the one place the two forms' dropout tails are compared at all.
 
 The two forms compute the same values in the same order, and nothing in the forward or in the data gradient sums through atomics:
   * x_final (the cls rows of xn), the whole stash - the compact x_mid, u, h, ln2 and the LayerNorm statistics of the tail live in it -,
@@ -48,13 +50,13 @@ class Case:
         self.hstash_bytes = int(lib.rmcl_heads_stash_bytes(C.byref(d)))
         self.ws = torch.empty(int(lib.rmcl_workspace_bytes(C.byref(d))), dtype=torch.uint8, device=DEV)
 
-    def run(self):
+    def run(self, drop_p=0.0, drop_seed=0):
         d, B = self.d, self.B
         stash = torch.zeros(self.stash_bytes, dtype=torch.uint8, device=DEV)     # zeroed: what a pass leaves unwritten compares equal
         hstash = torch.zeros(self.hstash_bytes + 16, dtype=torch.uint8, device=DEV)
         co = torch.zeros(B, N, dtype=torch.int32, device=DEV)
         xn = torch.zeros(B * N, D, device=DEV)
-        seed, p = C.c_uint32(0), C.c_float(0.0)
+        seed, p = C.c_uint32(drop_seed), C.c_float(drop_p)
         check(lib.rmcl_encoder_forward(C.byref(d), L.MODE_FULL | L.MODE_CLS_TAIL, P(self.p32), P(self.plp), P(self.text_ids), P(self.text_mask),
                                        P(self.patches), P(co), P(stash), P(self.ws), P(xn), seed, p, None, None, stream()), "encoder_forward")
         cls, q = torch.zeros(B, D, device=DEV), torch.zeros(B, PROJ, device=DEV)
@@ -87,14 +89,19 @@ def view_bits(t):
     return t.contiguous().view(torch.uint8)
 
 
+DROP_SEED = 20241                                  # any non-zero seed: the masks depend on it, the agreement must not
+
+
 @pytest.mark.parametrize("B", [4, 3])
-def test_tail_and_heads_on_the_streaming_form_have_the_ksplit_bits(B):
+@pytest.mark.parametrize("drop_p", [0.0, 0.1])
+def test_tail_and_heads_on_the_streaming_form_have_the_ksplit_bits(drop_p, B):
     case = Case(B)
+    seed = DROP_SEED if drop_p > 0 else 0
     runs = {}
     for form in (1, -1):
         check(lib.rmcl_tune_set(6, form), "tune_set")
         try:
-            runs[form] = [case.run() for _ in range(3)]
+            runs[form] = [case.run(drop_p, seed) for _ in range(3)]
         finally:
             check(lib.rmcl_tune_set(6, -1), "tune_set")
     old, new = runs[1][0], runs[-1][0]
@@ -102,14 +109,14 @@ def test_tail_and_heads_on_the_streaming_form_have_the_ksplit_bits(B):
         assert bool(torch.isfinite(new[k].float()).all()) and float(new[k].float().abs().max()) > 0, k
     for r in runs[-1]:
         for k in ("x_final", "stash", "q", "cls_feats", "dcls", "dpatches", "dtext"):
-            assert torch.equal(view_bits(r[k]), view_bits(old[k])), (B, k)
+            assert torch.equal(view_bits(r[k]), view_bits(old[k])), (B, drop_p, k)
         for off, n in case.owned():
             assert float(old["G"][off:off + n].abs().max()) > 0, off
-            assert torch.equal(view_bits(r["G"][off:off + n]), view_bits(old["G"][off:off + n])), (B, off)
+            assert torch.equal(view_bits(r["G"][off:off + n]), view_bits(old["G"][off:off + n])), (B, drop_p, off)
     dist = lambda a, b: float((a["G"].double() - b["G"].double()).abs().max())
     spread = max(dist(runs[k][i], runs[k][j]) for k in (1, -1) for i in range(3) for j in range(i))
     cross = [dist(a, b) for a in runs[-1] for b in runs[1]]
-    print(f"B {B} gradient arena: max |d| between forms {min(cross):.3e} .. {max(cross):.3e}, between two runs of one form up to {spread:.3e} "
+    print(f"B {B} p {drop_p} gradient arena: max |d| between forms {min(cross):.3e} .. {max(cross):.3e}, between two runs of one form up to {spread:.3e} "
           f"(max |G| {float(old['G'].abs().max()):.3e})")
     assert all(bool(torch.isfinite(r["G"]).all()) for r in runs[-1])
     assert min(cross) <= spread

@@ -69,16 +69,22 @@ def epilogues(M, N, W_arg, b_kc, X, bias, res, u, base):
     return out
 
 
-@pytest.mark.parametrize("N,K", NKS)
-def test_streaming_form_has_the_ksplit_kernels_bits(N, K):
+def operands(N, K):
+    """Inputs for MMAX rows and the fp64 references of the five launches, computed once and sliced per M."""
     Xall, W, bias = rnd(MMAX, K, seed=1), rnd(N, K, seed=2, scale=0.05), rnd(N, seed=3)
     Wn = W.t().contiguous()                                                      # [K][N]
     res_all = rnd(MMAX, AUX_ROWS, N, seed=7)                                     # row m of the residual: res_all[m, 0]
     u_all, base_all = rnd(MMAX, N, seed=9), rnd(MMAX, N, seed=10)
-    acc64 = Xall.double() @ W.double().t()                                       # computed once, sliced per M
+    acc64 = Xall.double() @ W.double().t()
     pre64 = acc64 + bias.double()
     ref = {"gelu_preact": [gelu(pre64), pre64], "residual_in_place": [pre64 + res_all[:, 0].double()], "dgelu": [acc64 * dgelu(u_all.double())],
            "tanh_dup": [torch.tanh(pre64), torch.tanh(pre64)], "accum": [acc64 + base_all.double()]}
+    return Xall, W, Wn, bias, res_all, u_all, base_all, ref
+
+
+@pytest.mark.parametrize("N,K", NKS)
+def test_streaming_form_has_the_ksplit_kernels_bits(N, K):
+    Xall, W, Wn, bias, res_all, u_all, base_all, ref = operands(N, K)
     worst = 0.0
     for M in MS:
         X, res, u = Xall[:M].contiguous(), res_all[:M].contiguous(), u_all[:M].contiguous()
@@ -97,6 +103,26 @@ def test_streaming_form_has_the_ksplit_kernels_bits(N, K):
     dflt = epilogues(MMAX, N, W, 1, Xall, bias, res_all, u_all, base_all)
     assert all(torch.equal(bits(a), bits(b)) for name in two for a, b in zip(two[name], dflt[name]))
     print(f"N {N} K {K}: largest rel. error against fp64 over all M, layouts and epilogues {worst:.2e}")
+
+
+@pytest.mark.parametrize("N,K", ((16, 128), (40, 256), (128, 768)))
+def test_row_split_kernel_runs_the_same_epilogues_within_the_fp64_bound(N, K):
+    """Key 6 = 0: gemm_skinny_kernel (every wave its own 16 rows, four accumulator chains summed at the end), which shares
+    skinny_epilogue with the k-split kernel but loads the tail's operands at the point of use.  It sums in another order, so no bit
+    equality with the other forms is claimed: the five launches against fp64 with this file's bound."""
+    Xall, W, Wn, bias, res_all, u_all, base_all, ref = operands(N, K)
+    worst = 0.0
+    for M in (1, 17, 64, 70):
+        X, res, u = Xall[:M].contiguous(), res_all[:M].contiguous(), u_all[:M].contiguous()
+        for b_kc, W_arg in ((1, W), (0, Wn)):
+            with Form(0):
+                got = epilogues(M, N, W_arg, b_kc, X, bias, res, u, base_all)
+            for name, outs in got.items():
+                for i, t in enumerate(outs):
+                    e = rel_err(t, ref[name][i][:M])
+                    worst = max(worst, e)
+                    assert e < 2e-5, (M, N, K, b_kc, name, i, e)
+    print(f"row-split N {N} K {K}: largest rel. error against fp64 over all M, layouts and epilogues {worst:.2e}")
 
 
 def rows_bf16(A, Wt, M, N, K, lda, bias=None, aux=None, ld_aux=0, epi=0):
