@@ -245,6 +245,38 @@ int rmcl_image_resize_u8(const uint8_t* src, const int32_t* src_sizes, int B, in
                          const int32_t* hbounds, const int32_t* hk, int ksh, const int32_t* vbounds, const int32_t* vk, int ksv, uint8_t* tmp,
                          uint8_t* dst, void* stream);
 
+/* RandAugment on the device (reference: vilt/transforms/randaug.py RandAugment(2, 9), inserted in front of MinMaxResize by
+ * transforms/pixelbert.py:20-30 and run with PIL in every loader worker).  src: decoded bytes of a batch, uint8 [B, Hs, Ws, 3], every sample
+ * in its top-left corner, sizes [B,2] = (h, w) per sample - the batch rmcl_image_resize_u8 takes, which this call precedes.  Sample b runs
+ * the n_ops operations ops[b, 0 .. n_ops) in turn, each on its own h x w rectangle (histogram, mean, rotation centre, borders); dst: uint8
+ * [B, Hs, Ws, 3], zero outside a sample; tmp: same-sized scratch (the stages ping-pong src -> tmp -> dst); scratch: rmcl_randaug_scratch_bytes
+ * bytes.  The op codes are the positions in the reference's augment_list().  params[b, s, :]: for Rotate, ShearX, ShearY and the translations
+ * the six coefficients (a, b, c, d, e, f) of PIL's affine transform - output (x, y) reads source (a x + b y + c, d x + e y + f); Rotate's as
+ * Image.rotate computes them in Python doubles -, for the other ops params[b, s, 0] = factor / threshold / bits / addition
+ * (vilt/transforms/randaug.py plan_params).  The arithmetic is PIL's (16.16 fixed point, doubles, or unfused C float, as PIL has it): the
+ * output bytes equal PIL's (tests/test_randaug_gpu.py).
+ * ops and params are HOST arrays - the argument check reads the op codes -, copied to the device on `stream`: like every buffer they stay
+ * alive until the stream has drained.  Returns -1 before any launch for a NULL operand, dst or tmp overlapping src (or each other), an op
+ * code outside 0..13 or n_ops outside 1..RMCL_RA_MAX_OPS.                                                                              */
+#define RMCL_RA_AUTOCONTRAST 0
+#define RMCL_RA_EQUALIZE 1
+#define RMCL_RA_ROTATE 2
+#define RMCL_RA_POSTERIZE 3
+#define RMCL_RA_SOLARIZE 4
+#define RMCL_RA_SOLARIZE_ADD 5
+#define RMCL_RA_COLOR 6
+#define RMCL_RA_CONTRAST 7
+#define RMCL_RA_BRIGHTNESS 8
+#define RMCL_RA_SHARPNESS 9
+#define RMCL_RA_SHEAR_X 10
+#define RMCL_RA_SHEAR_Y 11
+#define RMCL_RA_TRANSLATE_X 12
+#define RMCL_RA_TRANSLATE_Y 13
+#define RMCL_RA_MAX_OPS 8
+int64_t rmcl_randaug_scratch_bytes(int B, int n_ops);
+int rmcl_randaug_u8(const uint8_t* src, const int32_t* sizes, int B, int Hs, int Ws, const int32_t* ops, const double* params, int n_ops,
+                    uint8_t* tmp, void* scratch, uint8_t* dst, void* stream);
+
 /* Owner-side sum of a direct reduce-scatter over the xGMI links (replaces the reduction DDP's all-reduce performs inside the
  * collective, run.py:96): pieces [n_pieces][piece_elems] of `dtype` (F32 or BF16), this rank's slice as every rank sent
  * it; out32 = their sum (fp32 accumulation, rank order); out_wire (may be NULL) = the sum rounded to `dtype`, the operand

@@ -345,6 +345,23 @@ int rmcl_image_resize_u8(const uint8_t* src, const int32_t* src_sizes, int B, in
   RMCL_REQUIRE(src && src_sizes && dst_sizes && hbounds && hk && vbounds && vk && tmp && dst, "image_resize_u8: NULL argument");
   return rmcl_resize_u8(src, src_sizes, B, Hs, Ws, dst_sizes, Hd, Wd, hbounds, hk, ksh, vbounds, vk, ksv, tmp, dst, (hipStream_t)stream);
 }
+int64_t rmcl_randaug_scratch_bytes(int B, int n_ops) {
+  return (B > 0 && n_ops >= 1 && n_ops <= RMCL_RA_MAX_OPS) ? (int64_t)rmcl_randaug_scratch(B, n_ops) + 256 : 0;
+}
+int rmcl_randaug_u8(const uint8_t* src, const int32_t* sizes, int B, int Hs, int Ws, const int32_t* ops, const double* params, int n_ops,
+                    uint8_t* tmp, void* scratch, uint8_t* dst, void* stream) {
+  RMCL_REQUIRE(src && sizes && ops && params && tmp && scratch && dst, "randaug: NULL argument");
+  RMCL_REQUIRE(n_ops >= 1 && n_ops <= RMCL_RA_MAX_OPS, "randaug: n_ops must lie in 1..8");
+  RMCL_REQUIRE(B > 0 && Hs > 0 && Ws > 0, "randaug: bad dims");
+  const size_t bytes = (size_t)B * Hs * Ws * 3;
+  auto overlap = [bytes](const uint8_t* p, const uint8_t* q) { return p < q + bytes && q < p + bytes; };
+  RMCL_REQUIRE(!overlap(dst, src) && !overlap(tmp, src) && !overlap(dst, tmp), "randaug: dst and tmp must not alias src or each other");
+  for (long k = 0; k < (long)B * n_ops; ++k)
+    RMCL_REQUIRE(ops[k] >= 0 && ops[k] <= RMCL_RA_TRANSLATE_Y, "randaug: op code outside 0..13");
+  // (the scratch base is rounded up to 16 bytes: rmcl_randaug_scratch_bytes includes the slack)
+  void* aligned = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(scratch) + 15) & ~(uintptr_t)15);
+  return rmcl_randaug(src, sizes, B, Hs, Ws, ops, params, n_ops, tmp, aligned, dst, (hipStream_t)stream);
+}
 int rmcl_shard_sum(const void* pieces, int dtype, int n_pieces, int64_t piece_elems, float* out32, void* out_wire, void* stream) {
   RMCL_REQUIRE(pieces && (out32 || out_wire), "shard_sum: NULL argument");
   RMCL_REQUIRE(dtype == RMCL_F32 || dtype == RMCL_BF16, "shard_sum: dtype");

@@ -759,7 +759,9 @@ class Engine:
 
     def resize_raw(self, raw):
         """``RawUint8Batch`` (decoded bytes at their original sizes) -> ``Uint8Batch`` on the device: MinMaxResize with PIL's integer
-        arithmetic in two kernel passes (include/rmcl.h rmcl_image_resize_u8); the tables come from the host (cached per size pair)."""
+        arithmetic in two kernel passes (include/rmcl.h rmcl_image_resize_u8); the tables come from the host (cached per size pair).
+        A batch that carries RandAugment plans (``raw.aug``, transform key "decode_uint8_randaug") is augmented first, at its original
+        size, by rmcl_randaug_u8."""
         from .vilt.datasets.base_dataset import Uint8Batch
         tgt, hb, hk, vb, vk = raw.tables()
         src = self._h2d(raw.data).contiguous()
@@ -769,12 +771,22 @@ class Engine:
         # pageable memory may still be reading it after the arrays are gone); the image bytes themselves belong to the caller's batch
         dev = lambda t: t.to(self.device, non_blocking=False)
         ssz, dsz, hb_d, hk_d, vb_d, vk_d = dev(raw.sizes.contiguous()), dev(tgt.contiguous()), dev(hb), dev(hk), dev(vb), dev(vk)
+        aug_alive = ()
+        if getattr(raw, "aug", None) is not None:
+            # RandAugment first, at the original size (the reference inserts it in front of MinMaxResize): rmcl_randaug_u8 with PIL's bytes.
+            # The plan stays on the host - the library checks the op codes there and copies it to the device on the stream
+            ops, params = raw.aug
+            n_ops = ops.shape[1]
+            a_tmp, a_dst = torch.empty_like(src), torch.empty_like(src)
+            scratch = torch.empty(int(lib.rmcl_randaug_scratch_bytes(B, n_ops)), dtype=torch.uint8, device=self.device)
+            check(lib.rmcl_randaug_u8(P(src), P(ssz), B, Hs, Ws, P(ops), P(params), n_ops, P(a_tmp), P(scratch), P(a_dst), stream_ptr()), "randaug_u8")
+            aug_alive, src = (src, ops, params, a_tmp, scratch), a_dst
         tmp = torch.empty(B, Hs, Wd, 3, dtype=torch.uint8, device=self.device)
         dst = torch.empty(B, Hd, Wd, 3, dtype=torch.uint8, device=self.device)
         check(lib.rmcl_image_resize_u8(P(src), P(ssz), B, Hs, Ws, P(dsz), Hd, Wd, P(hb_d), P(hk_d), hk.shape[2], P(vb_d), P(vk_d), vk.shape[2],
                                        P(tmp), P(dst), stream_ptr()), "image_resize_u8")
         out = Uint8Batch(dst, tgt)
-        out.keep_alive = (raw.data, src, ssz, dsz, hb_d, hk_d, vb_d, vk_d, tmp)   # until the stream has consumed them
+        out.keep_alive = (raw.data, src, ssz, dsz, hb_d, hk_d, vb_d, vk_d, tmp) + aug_alive   # until the stream has consumed them
         return out
 
     def _bind_uint8(self, text_ids, text_mask, u8, tag, select) -> PassBuffers:

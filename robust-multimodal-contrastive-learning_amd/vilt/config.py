@@ -70,7 +70,7 @@ def task_finetune_vqa(**over):
 
 
 def task_finetune_vqa_randaug(**over):
-    """reference config.py:305-317: as task_finetune_vqa with the RandAugment train transform (the transform itself is the caller's)."""
+    """reference config.py:305-317: as task_finetune_vqa with the RandAugment train transform (vilt/transforms/randaug.py)."""
     cfg = task_finetune_vqa(exp_name="finetune_vqa_randaug", train_transform_keys=["pixelbert_randaug"])
     cfg.update(over)
     return cfg
@@ -105,7 +105,7 @@ def task_finetune_nlvr2(**over):
 
 
 def task_finetune_nlvr2_randaug(**over):
-    """reference config.py:245-256: as task_finetune_nlvr2 with the RandAugment train transform (the transform itself is the caller's)."""
+    """reference config.py:245-256: as task_finetune_nlvr2 with the RandAugment train transform (vilt/transforms/randaug.py)."""
     cfg = task_finetune_nlvr2(exp_name="finetune_nlvr2_randaug", train_transform_keys=["pixelbert_randaug"])
     cfg.update(over)
     return cfg
@@ -140,7 +140,7 @@ def task_finetune_irtr_coco(**over):
 
 
 def task_finetune_irtr_coco_randaug(**over):
-    """reference config.py:363-375 (the RandAugment train transform itself is the caller's)."""
+    """reference config.py:363-375 (the RandAugment train transform: vilt/transforms/randaug.py)."""
     cfg = default_config(
         exp_name="finetune_irtr_coco_randaug", datasets=["coco"], train_transform_keys=["pixelbert_randaug"],
         loss_names=_loss_names({"itm": 0.5, "irtr": 1}), batch_size=128, max_epoch=2, max_steps=None, warmup_steps=0.1,
@@ -161,7 +161,7 @@ def task_finetune_irtr_f30k(**over):
 
 
 def task_finetune_irtr_f30k_randaug(**over):
-    """reference config.py:422-434 (the RandAugment train transform itself is the caller's)."""
+    """reference config.py:422-434 (the RandAugment train transform: vilt/transforms/randaug.py)."""
     cfg = default_config(
         exp_name="finetune_irtr_f30k_randaug", datasets=["f30k"], train_transform_keys=["pixelbert_randaug"],
         loss_names=_loss_names({"itm": 0.5, "irtr": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,
@@ -193,7 +193,7 @@ def task_mlm_itm_mpp(**over):
 
 
 def task_mlm_itm_randaug(**over):
-    """reference config.py:212-220 (the RandAugment train transform itself is the caller's)."""
+    """reference config.py:212-220 (the RandAugment train transform: vilt/transforms/randaug.py)."""
     cfg = default_config(
         exp_name="mlm_itm_randaug", datasets=["coco", "vg", "sbu", "gcc"], train_transform_keys=["pixelbert_randaug"],
         loss_names=_loss_names({"itm": 1, "mlm": 1}), batch_size=4096, max_epoch=10, max_image_len=200,

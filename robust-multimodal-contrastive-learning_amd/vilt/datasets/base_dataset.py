@@ -150,11 +150,14 @@ class Uint8Batch:
 
 class RawView:
     """What the "decode_uint8" transform returns: the DECODED image as uint8 [h, w, 3] at its original size plus the MinMaxResize it still
-    owes (shorter, longer) - a loader worker then only decodes; the bicubic resize runs on the device (``RawUint8Batch``)."""
-    __slots__ = ("pixels", "shorter", "longer")
+    owes (shorter, longer) - a loader worker then only decodes; the bicubic resize runs on the device (``RawUint8Batch``).  ``plan``
+    ("decode_uint8_randaug"): the RandAugment plan [(op code, signed value)] the worker drew for this image (transforms/randaug.py), owed
+    BEFORE the resize."""
+    __slots__ = ("pixels", "shorter", "longer", "plan")
 
-    def __init__(self, pixels: torch.Tensor, shorter: int, longer: int):
+    def __init__(self, pixels: torch.Tensor, shorter: int, longer: int, plan=None):
         self.pixels, self.shorter, self.longer = pixels, int(shorter), int(longer)
+        self.plan = None if plan is None else [(int(c), float(v)) for c, v in plan]
 
     @property
     def shape(self):
@@ -165,11 +168,14 @@ class RawUint8Batch:
     """One view of a collated batch as decoded, NOT yet resized bytes: ``data`` uint8 [B, Hs, Ws, 3] (every sample in its top-left
     corner), ``sizes`` int32 [B, 2] = (h, w) as decoded, and the MinMaxResize parameters.  ``Engine.bind_batch`` resizes it on the device
     with PIL's own integer arithmetic (include/rmcl.h rmcl_image_resize_u8; vilt/transforms/resample.py builds the tables) into the
-    ``Uint8Batch`` the byte path continues from; ``resized_on_host()`` does the same with PIL (callers outside the training step, tests)."""
+    ``Uint8Batch`` the byte path continues from; ``resized_on_host()`` does the same with PIL (callers outside the training step, tests).
+    ``aug``: the RandAugment plans of the samples in the device encoding (transforms/randaug.py plan_params), applied to every sample's own
+    rectangle BEFORE the resize - on the device by rmcl_randaug_u8, in ``resized_on_host()`` by PIL, with the same bytes."""
 
-    def __init__(self, data: torch.Tensor, sizes: torch.Tensor, shorter: int, longer: int, extent=None):
+    def __init__(self, data: torch.Tensor, sizes: torch.Tensor, shorter: int, longer: int, extent=None, aug=None):
         """extent: (Hd, Wd) of the RESIZED batch when it must be larger than this view's own maximum - ``collate`` pads every image key
-        of a batch to ONE extent (base_dataset.py:192-206), e.g. "image" and "false_image_0" of the ITM objective."""
+        of a batch to ONE extent (base_dataset.py:192-206), e.g. "image" and "false_image_0" of the ITM objective.
+        aug: None or (ops int32 [B, n], params float64 [B, n, 6]), 1 <= n <= 8; kept on the host (the library reads the op codes there)."""
         assert data.dtype == torch.uint8 and data.dim() == 4 and data.shape[3] == 3, tuple(data.shape)
         self.data, self.sizes, self.shorter, self.longer = data, torch.as_tensor(sizes).to(torch.int32).cpu(), int(shorter), int(longer)
         self.extent = None if extent is None else (int(extent[0]), int(extent[1]))
@@ -177,6 +183,14 @@ class RawUint8Batch:
         sz = self.sizes
         if tuple(sz.shape) != (B, 2) or bool((sz < 1).any()) or bool((sz[:, 0] > Hs).any()) or bool((sz[:, 1] > Ws).any()):
             raise ValueError(f"RawUint8Batch.sizes must be [B, 2] = (h, w) with 1 <= h <= {Hs}, 1 <= w <= {Ws} (got {sz.tolist()})")
+        self.aug = None
+        if aug is not None:
+            ops, params = torch.as_tensor(aug[0]).to(torch.int32).cpu().contiguous(), torch.as_tensor(aug[1]).to(torch.float64).cpu().contiguous()
+            if ops.dim() != 2 or ops.shape[0] != B or not 1 <= ops.shape[1] <= 8 or tuple(params.shape) != tuple(ops.shape) + (6,) \
+                    or bool((ops < 0).any()) or bool((ops > 13).any()):
+                raise ValueError(f"RawUint8Batch.aug must be (ops [B, n] with codes 0..13, params [B, n, 6]), 1 <= n <= 8 "
+                                 f"(got {tuple(ops.shape)}, {tuple(params.shape)})")
+            self.aug = (ops, params)
 
     @property
     def target_sizes(self) -> torch.Tensor:
@@ -198,10 +212,10 @@ class RawUint8Batch:
         return (self.data.shape[0], 3) + self.out_hw()
 
     def to(self, device, non_blocking: bool = True) -> "RawUint8Batch":
-        return RawUint8Batch(self.data.to(device, non_blocking=non_blocking), self.sizes, self.shorter, self.longer, self.extent)
+        return RawUint8Batch(self.data.to(device, non_blocking=non_blocking), self.sizes, self.shorter, self.longer, self.extent, self.aug)
 
     def pin_memory(self) -> "RawUint8Batch":
-        return RawUint8Batch(self.data.pin_memory(), self.sizes, self.shorter, self.longer, self.extent)
+        return RawUint8Batch(self.data.pin_memory(), self.sizes, self.shorter, self.longer, self.extent, self.aug)
 
     def tables(self):
         """PIL's integer resampling tables of every sample, packed for the device: (target sizes [B,2], hbounds [B,Wd,2], hk [B,Wd,ksh],
@@ -226,7 +240,11 @@ class RawUint8Batch:
         out = torch.zeros((self.data.shape[0],) + self.out_hw(tgt) + (3,), dtype=torch.uint8)
         src = self.data.cpu().numpy()
         for b, ((h, w), (th, tw)) in enumerate(zip(self.sizes.tolist(), tgt.tolist())):
-            img = Image.fromarray(src[b, :h, :w]).resize((tw, th), resample=Image.BICUBIC)
+            img = Image.fromarray(src[b, :h, :w])
+            if self.aug is not None:
+                from ..transforms.randaug import apply_params_pil
+                img = apply_params_pil(img, self.aug[0][b].tolist(), self.aug[1][b].numpy())
+            img = img.resize((tw, th), resample=Image.BICUBIC)
             out[b, :th, :tw] = torch.from_numpy(np.asarray(img).copy())
         return Uint8Batch(out, tgt)
 
@@ -289,9 +307,22 @@ def collate_uint8(samples: List[dict], mlm_collator: Optional[Callable] = None) 
     return batch
 
 
+def _pack_plans(views: list):
+    """the plans of one view of every sample -> (ops [B, n], params [B, n, 6]) or None"""
+    planned = [rv.plan is not None for rv in views]
+    if not any(planned):
+        return None
+    if not all(planned) or len({len(rv.plan) for rv in views}) != 1:
+        raise AssertionError("Collate error, the RandAugment plans of a view must be given for all of its samples or none, with one length")
+    from ..transforms.randaug import plan_params
+    packed = [plan_params(rv.plan, rv.shape[1], rv.shape[0]) for rv in views]
+    return torch.from_numpy(np.stack([o for o, _ in packed])), torch.from_numpy(np.stack([p for _, p in packed]))
+
+
 def collate_raw_uint8(samples: List[dict], mlm_collator: Optional[Callable] = None) -> Dict[str, object]:
     """``collate`` for samples whose image views are ``RawView`` (transform key "decode_uint8"): every image key becomes a list of
-    ``RawUint8Batch`` - decoded bytes at their ORIGINAL sizes, one maximum extent over all image keys - for the device-side resize."""
+    ``RawUint8Batch`` - decoded bytes at their ORIGINAL sizes, one maximum extent over all image keys - for the device-side resize.  Views
+    that carry a RandAugment plan ("decode_uint8_randaug") give the batch its ``aug``: all samples of a view or none, one plan length per view."""
     names = {k for smp in samples for k in smp}
     image_keys = [k for k in names if "image" in k]
     stripped = [{k: v for k, v in smp.items() if k not in image_keys} for smp in samples]
@@ -315,7 +346,7 @@ def collate_raw_uint8(samples: List[dict], mlm_collator: Optional[Callable] = No
                     px = vs[v].pixels
                     data[b, : px.shape[0], : px.shape[1]] = px
                     sizes[b, 0], sizes[b, 1] = px.shape[0], px.shape[1]
-                out.append(RawUint8Batch(data, sizes, per_sample[0][v].shorter, per_sample[0][v].longer, extent))
+                out.append(RawUint8Batch(data, sizes, per_sample[0][v].shorter, per_sample[0][v].longer, extent, _pack_plans([vs[v] for vs in per_sample])))
             batch[k] = out
     return batch
 
@@ -337,7 +368,8 @@ class BaseDataset(torch.utils.data.Dataset):
 
     ``transform_keys``: "pixelbert" (float CHW views, the reference's), "pixelbert_uint8" (byte HWC views for the device-side
     normalisation, collate with ``collate_uint8``) or "decode_uint8" (decoded bytes at the original size: MinMaxResize too runs on the
-    device, collate with ``collate_raw_uint8``).  Differences kept on purpose: the tables stay memory-mapped and the caption
+    device, collate with ``collate_raw_uint8``); "pixelbert_randaug" (the reference's training transform of the ``_randaug`` configs:
+    RandAugment(2, 9) in front of "pixelbert") and "decode_uint8_randaug" ("decode_uint8" plus the drawn plan: RandAugment runs on the device).  Differences kept on purpose: the tables stay memory-mapped and the caption
     column is read once with ``to_pylist`` (no pandas round trip); de-duplication keeps first-seen order (the reference's
     ``list(set(texts))`` order depends on the hash seed)."""
 

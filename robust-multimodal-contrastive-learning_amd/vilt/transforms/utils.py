@@ -68,8 +68,29 @@ def decode_uint8_transform(size=800):
     return lambda img: RawView(torch.from_numpy(np.array(img.convert("RGB"), dtype=np.uint8)), size, longer)
 
 
-# (the RandAugment variant is a training-time augmentation, out of scope)
-_transforms = {"pixelbert": pixelbert_transform, "pixelbert_uint8": pixelbert_uint8_transform, "decode_uint8": decode_uint8_transform}
+RANDAUG_N, RANDAUG_M = 2, 9          # transforms/pixelbert.py:29: RandAugment(2, 9)
+
+
+def pixelbert_randaug_transform(size=800):
+    """The reference's training transform of the ``_randaug`` task configs (transforms/pixelbert.py:20-30): RandAugment(2, 9) at position 0 -
+    on the decoded image at its original size -, then MinMaxResize and the float conversion of ``pixelbert``."""
+    from .randaug import RandAugment
+    augment, resize = RandAugment(RANDAUG_N, RANDAUG_M), MinMaxResize(shorter=size, longer=int((1333 / 800) * size))
+    return lambda img: to_normalized_tensor(resize(augment(img)))
+
+
+def decode_uint8_randaug_transform(size=800):
+    """``decode_uint8`` for the ``_randaug`` configs: the worker decodes and DRAWS the RandAugment plan (the same draws from ``random`` as the
+    reference's transform makes), nothing else; the ``RawView`` carries the plan and the device applies it in front of its resize
+    (rmcl_randaug_u8, Engine.resize_raw) with PIL's bytes as the result."""
+    from ..datasets.base_dataset import RawView
+    from .randaug import draw_plan
+    longer = int((1333 / 800) * size)
+    return lambda img: RawView(torch.from_numpy(np.array(img.convert("RGB"), dtype=np.uint8)), size, longer, plan=draw_plan(RANDAUG_N, RANDAUG_M))
+
+
+_transforms = {"pixelbert": pixelbert_transform, "pixelbert_uint8": pixelbert_uint8_transform, "decode_uint8": decode_uint8_transform,
+               "pixelbert_randaug": pixelbert_randaug_transform, "decode_uint8_randaug": decode_uint8_randaug_transform}
 
 
 def keys_to_transforms(keys: list, size=224):
