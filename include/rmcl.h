@@ -612,6 +612,40 @@ int rmcl_adamw_f32(float* p, const float* g, float* m, float* v, void* p_lp, con
                    const float* seg_lr_mult, const float* seg_wd, int nseg, float lr, float beta1, float beta2,
                    float eps, int step, float grad_scale, int64_t n, void* stream);
 
+/* Guarded optimizer step (Lightning's precision=16 GradScaler skip and gradient_clip_val, run.py:92-112): the decision to skip or
+ * clip a step is taken on the device and handed to the AdamW through this block of DEVICE memory, so a step costs no host round
+ * trip.  48 bytes, 8-byte aligned; the host reads it only when asked (counters, norm).  Zero-fill it before the first step.
+ *   offset  0  double  sumsq       sum of g^2 over the FINITE elements of the last statistics pass (unscaled gradient)
+ *   offset  8  int64   nonfinite   elements of that pass whose exponent bits are all ones (NaN, +inf, -inf)
+ *   offset 16  float   norm        (float)(grad_scale * sqrt(sumsq))
+ *   offset 20  float   clip_coef   max_norm > 0 ? min(1, max_norm / (norm + 1e-6f)) : 1      (torch.nn.utils.clip_grad_norm_)
+ *   offset 24  int32   skip        nonfinite > 0: the guarded AdamW that follows writes nothing
+ *   offset 28  int32   applied     AdamW steps actually applied so far (the step number of the bias corrections)
+ *   offset 32  int32   skipped     steps dropped so far
+ *   offset 36  float   bc1         1 - beta1^applied          (double arithmetic, rounded once)
+ *   offset 40  float   bc2s        sqrt(1 - beta2^applied)
+ *   offset 44  int32   reserved                                                                                          */
+typedef struct rmcl_step_ctl {
+  double sumsq;
+  int64_t nonfinite;
+  float norm, clip_coef;
+  int32_t skip, applied, skipped;
+  float bc1, bc2s;
+  int32_t reserved;
+} rmcl_step_ctl;
+/* One pass over the n fp32 gradients (n > 0, n % 4 == 0): per-block (sum of squares in double, non-finite count) pairs into `ws`
+ * (rmcl_grad_stats_ws_bytes(n) bytes, every byte of it written), then one block adds them in a fixed order and writes the decision
+ * into ctl: sumsq, nonfinite, norm, clip_coef, skip; not skipping, applied += 1 and bc1 / bc2s of that step; skipping, skipped += 1.
+ * No atomics: the same input gives the same bytes of ws and ctl on every call.                                           */
+int64_t rmcl_grad_stats_ws_bytes(int64_t n);
+int rmcl_grad_stats_f32(const float* g, int64_t n, float grad_scale, float max_norm, float beta1, float beta2, void* ws,
+                        rmcl_step_ctl* ctl, void* stream);
+/* rmcl_adamw_f32 with skip, clip_coef, bc1 and bc2s read from ctl on the device: skip set, no byte of p, m, v or p_lp is written;
+ * otherwise the gradient is g * grad_scale * clip_coef and the rest (segments, weight decay, bf16 shadow) is rmcl_adamw_f32's.   */
+int rmcl_adamw_guarded_f32(float* p, const float* g, float* m, float* v, void* p_lp, const int64_t* seg_end,
+                           const float* seg_lr_mult, const float* seg_wd, int nseg, float lr, float beta1, float beta2,
+                           float eps, float grad_scale, const rmcl_step_ctl* ctl, int64_t n, void* stream);
+
 /* ITM + word-patch alignment (objectives.py:24-76,714-787).  cost / dsim are [B, Lt, ld] f32 with
  * ld >= Li a multiple of 4 (GEMM operand pitch); T is [B, Li, Lt] like the reference's ipot().      */
 int rmcl_gemm_batched(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int ldc, float alpha,

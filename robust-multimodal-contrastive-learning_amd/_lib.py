@@ -77,6 +77,21 @@ class RankSrc(C.Structure):
     _fields_ = [("embeds", C.c_void_p), ("masks", C.c_void_p), ("img_of", C.c_void_p), ("n_img", C.c_int32), ("ld_tok", C.c_int32)]
 
 
+class StepCtl(C.Structure):
+    """include/rmcl.h rmcl_step_ctl: the guarded optimizer step's decision block (device memory, 48 bytes)."""
+    _fields_ = [("sumsq", C.c_double), ("nonfinite", C.c_int64), ("norm", C.c_float), ("clip_coef", C.c_float),
+                ("skip", C.c_int32), ("applied", C.c_int32), ("skipped", C.c_int32), ("bc1", C.c_float), ("bc2s", C.c_float),
+                ("reserved", C.c_int32)]
+
+    @classmethod
+    def from_tensor(cls, t):
+        """Host copy of a 48-byte uint8 tensor (this read synchronises when the tensor is on the device)."""
+        return cls.from_buffer_copy(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes())
+
+    def to_tensor(self, device):
+        return torch.frombuffer(bytearray(bytes(self)), dtype=torch.uint8).clone().to(device)
+
+
 class RmclError(RuntimeError):
     pass
 
@@ -90,8 +105,9 @@ def _load():
     lib.rmcl_last_error.restype = C.c_char_p
     for name in ("rmcl_stash_bytes", "rmcl_workspace_bytes", "rmcl_heads_stash_bytes", "rmcl_infonce_ws_bytes",
                  "rmcl_attention_scratch_elems", "rmcl_attention_stream_stat_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats",
-                 "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats", "rmcl_mpp_ws_floats", "rmcl_randaug_scratch_bytes"):
+                 "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats", "rmcl_mpp_ws_floats", "rmcl_randaug_scratch_bytes", "rmcl_grad_stats_ws_bytes"):
         getattr(lib, name).restype = C.c_int64
+    lib.rmcl_grad_stats_ws_bytes.argtypes = [C.c_int64]
     lib.rmcl_randaug_scratch_bytes.argtypes = [C.c_int, C.c_int]
     lib.rmcl_randaug_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
@@ -104,7 +120,7 @@ EXPORTS = (
     "rmcl_last_error", "rmcl_version", "rmcl_prof_begin", "rmcl_prof_end", "rmcl_tune_set", "rmcl_grad_ready_wait", "rmcl_set_side_stream", "rmcl_set_prefetch_stream", "rmcl_dropout_mask_apply", "rmcl_param_layout", "rmcl_ln_fold_elems", "rmcl_ln_fold", "rmcl_linear_rowstat", "rmcl_linear_lnfold", "rmcl_linear_rowstat_c", "rmcl_linear_lnfold_c", "rmcl_weight_transpose_bf16", "rmcl_stash_bytes", "rmcl_workspace_bytes",
     "rmcl_heads_stash_bytes", "rmcl_im2patch_f32", "rmcl_patch_select", "rmcl_im2patch_sel", "rmcl_image_u8_to_patches", "rmcl_image_resize_u8", "rmcl_randaug_scratch_bytes", "rmcl_randaug_u8", "rmcl_add_cast_f32", "rmcl_shard_sum", "rmcl_encoder_forward", "rmcl_encoder_backward",
     "rmcl_heads_forward", "rmcl_heads_forward2", "rmcl_heads_backward", "rmcl_infonce_ws_bytes", "rmcl_infonce_f32", "rmcl_infonce_split_bf16", "rmcl_pgd_step", "rmcl_pgd_step_fused",
-    "rmcl_delta_channel_norm", "rmcl_ema_f32", "rmcl_enqueue_f32", "rmcl_cast_f32", "rmcl_adamw_f32", "rmcl_ipot_f32", "rmcl_gemm_batched", "rmcl_l2norm_rows_fwd", "rmcl_l2norm_rows_bwd",
+    "rmcl_delta_channel_norm", "rmcl_ema_f32", "rmcl_enqueue_f32", "rmcl_cast_f32", "rmcl_adamw_f32", "rmcl_grad_stats_ws_bytes", "rmcl_grad_stats_f32", "rmcl_adamw_guarded_f32", "rmcl_ipot_f32", "rmcl_gemm_batched", "rmcl_l2norm_rows_fwd", "rmcl_l2norm_rows_bwd",
     "rmcl_wpa_cost_finish", "rmcl_wpa_distance", "rmcl_itm_fwd", "rmcl_itm_bwd",
     "rmcl_gemm", "rmcl_gemm_rows_bf16", "rmcl_rows_gather_f32", "rmcl_gemm_chain", "rmcl_l2_prefetch_experiment", "rmcl_gemm_route", "rmcl_gemm_kblk", "rmcl_layernorm_fwd", "rmcl_layernorm_bwd", "rmcl_attention_scratch_elems", "rmcl_attention_fwd",
     "rmcl_attention_bwd", "rmcl_attention_stream_stat_elems", "rmcl_attention_stream_fwd", "rmcl_attention_stream_bwd",

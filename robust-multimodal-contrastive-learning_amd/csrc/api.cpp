@@ -417,6 +417,19 @@ int rmcl_adamw_f32(float* p, const float* g, float* m, float* v, void* p_lp, con
   return rmcl_adamw(p, g, m, v, p_lp, (const long*)seg_end, seg_lr_mult, seg_wd, nseg, lr, beta1, beta2, eps, step, grad_scale, n,
                     (hipStream_t)stream);
 }
+int64_t rmcl_grad_stats_ws_bytes(int64_t n) { return rmcl_grad_stats_workspace_bytes(n); }
+int rmcl_grad_stats_f32(const float* g, int64_t n, float grad_scale, float max_norm, float beta1, float beta2, void* ws,
+                        rmcl_step_ctl* ctl, void* stream) {
+  RMCL_REQUIRE(g && ws && ctl, "grad_stats: NULL argument");
+  return rmcl_grad_stats(g, n, grad_scale, max_norm, beta1, beta2, ws, ctl, (hipStream_t)stream);
+}
+int rmcl_adamw_guarded_f32(float* p, const float* g, float* m, float* v, void* p_lp, const int64_t* seg_end, const float* seg_lr_mult,
+                           const float* seg_wd, int nseg, float lr, float beta1, float beta2, float eps, float grad_scale,
+                           const rmcl_step_ctl* ctl, int64_t n, void* stream) {
+  RMCL_REQUIRE(p && g && m && v && seg_end && seg_lr_mult && seg_wd && ctl, "adamw_guarded: NULL argument");
+  return rmcl_adamw_guarded(p, g, m, v, p_lp, (const long*)seg_end, seg_lr_mult, seg_wd, nseg, lr, beta1, beta2, eps, grad_scale, ctl, n,
+                            (hipStream_t)stream);
+}
 int rmcl_ipot_f32(const float* cost, const int32_t* txt_valid, const int32_t* img_valid, float* T, int B, int Lt, int Li,
                   int ld, float beta, int iters, void* stream) {
   RMCL_REQUIRE(cost && txt_valid && img_valid && T, "ipot: NULL argument");

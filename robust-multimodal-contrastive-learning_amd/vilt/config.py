@@ -22,6 +22,10 @@ def default_config(**over):
         get_recall_metric=False, resume_from="", fast_dev_run=False, val_check_interval=1.0, test_only=False,
         data_root="", log_dir="result", per_gpu_batchsize=0, num_gpus=1, num_nodes=1, load_path="",
         num_workers=8, precision=16,
+        # not reference keys.  skip_nonfinite_steps: drop an optimizer step whose gradient holds a NaN / inf (what the GradScaler of the
+        # reference's precision=16 does); gradient_clip_val: Lightning's Trainer argument of that name (its default 0 = off; run.py does
+        # not set it).  Either one switches FusedAdamW to the guarded step (DESIGN.md "Guarded step and resumable state")
+        skip_nonfinite_steps=False, gradient_clip_val=0.0,
     )
     cfg.update(over)
     return cfg

@@ -323,6 +323,44 @@ class ViLTransformerSS(nn.Module):
         if hasattr(self, "proj_queue_ptr"):
             self._queue_ptr_host = None
 
+    # ---- resumable state ---------------------------------------------------------------------
+    def training_state(self):
+        """Everything OUTSIDE state_dict() that the next step depends on (tensors, numbers, lists and dicts only): the dropout seed
+        position (Engine.pass_counter / seed_base), the host copy of the queue pointer, the metric accumulators epoch_wrapup would read,
+        and the RNG states - torch CPU and device, and Python's `random` (the RandAugment plan and the collators draw from it).  The
+        queue, its pointer, the momentum copies and the Barlow-Twins running statistics are buffers / parameters: state_dict() has them."""
+        import random
+        e = self.engine
+        version, internal, gauss = random.getstate()
+        logged = {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in self.logged.items()
+                  if torch.is_tensor(v) or isinstance(v, (int, float))}
+        st = {"pass_counter": int(e.pass_counter), "seed_base": int(e.seed_base),
+              "queue_ptr": int(self.queue_ptr) if hasattr(self, "proj_queue_ptr") else None,
+              "logged": logged,
+              "mlm_epoch_counts": {k: v.detach().cpu() for k, v in getattr(self, "mlm_epoch_counts", {}).items()},
+              "mpp_epoch_counts": {k: v.detach().cpu() for k, v in getattr(self, "mpp_epoch_counts", {}).items()},
+              "torch_rng": torch.get_rng_state(),
+              "python_rng": [int(version), [int(x) for x in internal], gauss]}
+        if e.q32.is_cuda:
+            st["device_rng"] = torch.cuda.get_rng_state(e.q32.device)
+        return st
+
+    def load_training_state(self, state):
+        import random
+        e = self.engine
+        e.pass_counter, e.seed_base = int(state["pass_counter"]), int(state["seed_base"])
+        if hasattr(self, "proj_queue_ptr") and state.get("queue_ptr") is not None:
+            self._queue_ptr_host = int(state["queue_ptr"])        # (the device copy is a buffer of state_dict())
+        self.logged = {k: (v.to(e.device) if torch.is_tensor(v) else v) for k, v in state.get("logged", {}).items()}
+        for name in ("mlm_epoch_counts", "mpp_epoch_counts"):
+            if state.get(name):
+                setattr(self, name, {k: v.to(e.device) for k, v in state[name].items()})
+        torch.set_rng_state(state["torch_rng"].cpu().to(torch.uint8))
+        if "device_rng" in state and e.q32.is_cuda:
+            torch.cuda.set_rng_state(state["device_rng"].cpu().to(torch.uint8), e.q32.device)
+        version, internal, gauss = state["python_rng"]
+        random.setstate((int(version), tuple(int(x) for x in internal), gauss))
+
     # ---- Lightning shims -------------------------------------------------------------------
     @property
     def device(self):

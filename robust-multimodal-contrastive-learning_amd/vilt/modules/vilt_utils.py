@@ -77,9 +77,16 @@ def adamw_segments(specs, total, wd, lr_mult, irtr=False):
 
 
 class FusedAdamW:
-    """optimizer-like object (``step`` / ``zero_grad`` / ``param_groups``) over the engine's arenas."""
+    """optimizer-like object (``step`` / ``zero_grad`` / ``param_groups`` / ``state_dict``) over the engine's arenas.
 
-    def __init__(self, pl_module, lr, wd, lr_mult, betas=(0.9, 0.98), eps=1e-8):
+    skip_nonfinite / clip_val (config ``skip_nonfinite_steps`` / ``gradient_clip_val``, both off by default): with either set, ``step``
+    is the GUARDED step - a statistics pass over the gradient arena takes the decision on the device (rmcl_step_ctl: a non-finite
+    gradient drops the step, as the GradScaler of the reference's precision=16 does; clip_val > 0 scales the gradient like
+    clip_grad_norm_) and the AdamW reads it there.  No device-to-host copy, no synchronisation: ``t`` counts ATTEMPTED steps on the
+    host, the applied / skipped counts live in ``ctl`` and are read by ``counters()`` / ``grad_norm()`` only.  With N > 1 every rank
+    sees the same reduced gradient, so every rank takes the same decision without a collective."""
+
+    def __init__(self, pl_module, lr, wd, lr_mult, betas=(0.9, 0.98), eps=1e-8, skip_nonfinite=False, clip_val=0.0):
         eng = pl_module.engine
         self.eng = eng
         self.module = pl_module
@@ -94,6 +101,11 @@ class FusedAdamW:
         self.seg_wd = torch.tensor(wds, dtype=torch.float32, device=dev)
         self.param_groups = [{"lr": lr, "initial_lr": lr}]
         self.grad_scale = 1.0
+        self.clip_val = float(clip_val or 0.0)
+        self.guarded = bool(skip_nonfinite) or self.clip_val > 0
+        if self.guarded:
+            self.ctl = torch.zeros(C.sizeof(L.StepCtl), dtype=torch.uint8, device=dev)
+            self.stats_ws = torch.zeros(int(lib.rmcl_grad_stats_ws_bytes(I64(eng.q32.numel()))), dtype=torch.uint8, device=dev)
 
     def zero_grad(self, set_to_none: bool = False):
         self.eng.zero_grads()
@@ -102,13 +114,65 @@ class FusedAdamW:
         self.t += 1
         e = self.eng
         self.module.wait_grad_sync()                       # overlapped data-parallel all-reduces (N > 1)
-        check(lib.rmcl_adamw_f32(P(e.q32), P(e.g32), P(self.m), P(self.v), P(e.q_lp), P(self.seg_end), P(self.seg_mult),
-                                 P(self.seg_wd), int(self.seg_end.numel()), F(self.param_groups[0]["lr"]), F(self.betas[0]),
-                                 F(self.betas[1]), F(self.eps), self.t, F(self.grad_scale), I64(e.q32.numel()), stream_ptr()),
-              "adamw")
-        e.fold_stale["q"] = True
+        if self.guarded:
+            n = I64(e.q32.numel())
+            check(lib.rmcl_grad_stats_f32(P(e.g32), n, F(self.grad_scale), F(self.clip_val), F(self.betas[0]), F(self.betas[1]),
+                                          P(self.stats_ws), P(self.ctl), stream_ptr()), "grad_stats")
+            check(lib.rmcl_adamw_guarded_f32(P(e.q32), P(e.g32), P(self.m), P(self.v), P(e.q_lp), P(self.seg_end), P(self.seg_mult),
+                                             P(self.seg_wd), int(self.seg_end.numel()), F(self.param_groups[0]["lr"]), F(self.betas[0]),
+                                             F(self.betas[1]), F(self.eps), F(self.grad_scale), P(self.ctl), n, stream_ptr()),
+                  "adamw_guarded")
+        else:
+            check(lib.rmcl_adamw_f32(P(e.q32), P(e.g32), P(self.m), P(self.v), P(e.q_lp), P(self.seg_end), P(self.seg_mult),
+                                     P(self.seg_wd), int(self.seg_end.numel()), F(self.param_groups[0]["lr"]), F(self.betas[0]),
+                                     F(self.betas[1]), F(self.eps), self.t, F(self.grad_scale), I64(e.q32.numel()), stream_ptr()),
+                  "adamw")
+        e.fold_stale["q"] = True                            # (after a skipped step too: refreshing a shadow that did not move is harmless)
         e.lpT_stale = True
         e.mlm_wt_stale = True
+
+    def read_ctl(self):
+        """Host copy of the decision block (synchronises); None on an unguarded optimizer."""
+        return L.StepCtl.from_tensor(self.ctl) if self.guarded else None
+
+    def counters(self):
+        """(applied, skipped) optimizer steps.  Reads ``ctl``: this call synchronises."""
+        if not self.guarded:
+            return self.t, 0
+        c = self.read_ctl()
+        return int(c.applied), int(c.skipped)
+
+    def grad_norm(self):
+        """grad_scale * |g| of the last step's FINITE gradient elements, before clipping.  Reads ``ctl``: this call synchronises."""
+        if not self.guarded:
+            raise RuntimeError("grad_norm(): the gradient statistics run only in the guarded step "
+                               "(config skip_nonfinite_steps=True or gradient_clip_val > 0)")
+        return float(self.read_ctl().norm)
+
+    def state_dict(self):
+        """m, v, the step counts and the hyper-parameters (tensors, numbers, lists and dicts only: torch.load(weights_only=True) reads
+        it).  The segment tables follow from the model and are rebuilt, not stored."""
+        applied, skipped = self.counters()
+        return {"state": {"m": self.m.detach().cpu(), "v": self.v.detach().cpu()}, "t": int(self.t), "applied": applied, "skipped": skipped,
+                "betas": [float(b) for b in self.betas], "eps": float(self.eps), "grad_scale": float(self.grad_scale),
+                "param_groups": [dict(g) for g in self.param_groups], "arena_numel": int(self.m.numel())}
+
+    def load_state_dict(self, sd):
+        have, want = int(sd["state"]["m"].numel()), int(self.m.numel())
+        if have != want or int(sd["state"]["v"].numel()) != want:
+            raise ValueError(f"FusedAdamW.load_state_dict: the checkpoint's optimizer state has {have} elements, this model's parameter "
+                             f"arena has {want} (another architecture or head set)")
+        self.m.copy_(sd["state"]["m"])
+        self.v.copy_(sd["state"]["v"])
+        self.t = int(sd["t"])
+        self.betas, self.eps = tuple(float(b) for b in sd["betas"]), float(sd["eps"])
+        self.grad_scale = float(sd["grad_scale"])
+        self.param_groups = [dict(g) for g in sd["param_groups"]]
+        if self.guarded:
+            c = L.StepCtl(applied=int(sd["applied"]), skipped=int(sd["skipped"]), clip_coef=1.0)
+            self.ctl.copy_(c.to_tensor(self.ctl.device))
+        else:
+            self.t = int(sd["applied"])                    # the unguarded kernel's bias corrections follow t: only applied steps count
 
 
 class PolySchedule:
@@ -127,7 +191,15 @@ class PolySchedule:
         self.opt.param_groups[0]["lr"] = self.lr_at(self.n)
 
     def step(self):
+        """Once per ATTEMPTED optimizer step: like Lightning's, the schedule also advances on a step the guard dropped."""
         self.n += 1
+        self._apply()
+
+    def state_dict(self):
+        return {"n": int(self.n), "lr": float(self.opt.param_groups[0]["lr"])}
+
+    def load_state_dict(self, sd):
+        self.n = int(sd["n"])
         self._apply()
 
 
@@ -142,11 +214,12 @@ def set_schedule(pl_module):
     cfg = pl_module.hparams.config
     if cfg["optim_type"] != "adamw":
         raise NotImplementedError("only optim_type='adamw' (the reference default) is built")
-    opt = FusedAdamW(pl_module, cfg["learning_rate"], cfg["weight_decay"], cfg["lr_mult"])
+    opt = FusedAdamW(pl_module, cfg["learning_rate"], cfg["weight_decay"], cfg["lr_mult"],
+                     skip_nonfinite=cfg.get("skip_nonfinite_steps", False), clip_val=cfg.get("gradient_clip_val", 0.0))
     max_steps = cfg["max_steps"]
     if max_steps is None:
-        # the reference derives it from the Lightning trainer's dataloader (vilt_utils.py:404-411); there is no
-        # trainer here, so the caller states it
+        # the reference derives it from the Lightning trainer's dataloader (vilt_utils.py:404-411); rmcl_amd.trainer.Trainer.fit does
+        # the same before it calls configure_optimizers(), any other caller states it
         raise ValueError("set_schedule: config['max_steps'] is None - set it to the number of optimizer steps "
                          "(the reference computes it from len(train_dataloader) * max_epoch // accumulate_grad_batches)")
     warmup = cfg["warmup_steps"]
