@@ -422,6 +422,13 @@ int64_t rmcl_mpp_ws_floats(const rmcl_mpp_head* h, int rows);
  * sel[b, j], every other slot gets -100 in all three channels.                                                                   */
 int rmcl_mpp_labels(const float* img, int B, int H, int W, const int32_t* sel, const int32_t* counts, int sel_ld, int gw, int P,
                     int32_t* labels, void* stream);
+/* The same labels from the byte feed: img uint8 [B, Hmax, Wmax, 3] (HWC, every sample in its top-left corner), sizes [B, 2] = (h, w),
+ * multiples of 32, lut [256] = normalize_lut() - exactly the batch rmcl_image_u8_to_patches takes.  sel / counts / sel_ld / gw / P and the
+ * layout of labels as in rmcl_mpp_labels (dense form: sel = NULL, P = (Hmax / 32) (Wmax / 32)).  The labels equal, integer for integer,
+ * what rmcl_mpp_labels writes for the float batch of the same bytes (Uint8Batch.float_image()): a pixel outside its sample counts as
+ * that batch's zero, 0 * 0.5 + 0.5 (not lut[0]), so a fully padded patch of the dense form has the label 127.  img 4-byte aligned. */
+int rmcl_mpp_labels_u8(const uint8_t* img, const int32_t* sizes, int B, int Hmax, int Wmax, const float* lut, const int32_t* sel,
+                       const int32_t* counts, int sel_ld, int gw, int P, int32_t* labels, void* stream);
 /* labels [B, P, 3], masked [B, P] int32 -> idx [cap]: row b * N + L + 1 + j of xn [B N, D] for every masked valid slot (ascending) whose
  * three labels lie in [0, 256); lab [cap, 3] its labels; count [2]: count[0] = n, count[1] = the label entries outside [0, 256) of masked
  * valid slots (such a slot is skipped; callers turn a non-zero count[1] into an error).  A masked pad slot (labels -100) is ignored.

@@ -110,6 +110,8 @@ def _load():
     lib.rmcl_grad_stats_ws_bytes.argtypes = [C.c_int64]
     lib.rmcl_randaug_scratch_bytes.argtypes = [C.c_int, C.c_int]
     lib.rmcl_randaug_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rmcl_mpp_labels_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -130,7 +132,7 @@ EXPORTS = (
     "rmcl_nlvr2_ce",
     "rmcl_visual_embed", "rmcl_encoder_forward_rank", "rmcl_irtr_score", "rmcl_irtr_ce", "rmcl_irtr_bwd",
     "rmcl_mlm_ws_floats", "rmcl_mlm_compact", "rmcl_mlm_weight_transpose", "rmcl_mlm_forward", "rmcl_mlm_backward", "rmcl_mlm_logits",
-    "rmcl_mpp_ws_floats", "rmcl_mpp_labels", "rmcl_mpp_compact", "rmcl_mpp_forward", "rmcl_mpp_backward", "rmcl_mpp_logits",
+    "rmcl_mpp_ws_floats", "rmcl_mpp_labels", "rmcl_mpp_labels_u8", "rmcl_mpp_compact", "rmcl_mpp_forward", "rmcl_mpp_backward", "rmcl_mpp_logits",
     "rmcl_encoder_forward_mpp", "rmcl_encoder_backward_mpp", "rmcl_visual_embed_mpp",
     "rmcl_word_saliency",
 )

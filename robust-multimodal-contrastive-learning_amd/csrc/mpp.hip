@@ -62,6 +62,69 @@ __global__ __launch_bounds__(256) void mpp_labels_kernel(const float* __restrict
   }
 }
 
+// The same labels from the byte feed: img uint8 [B, Hmax, Wmax, 3] (HWC, every sample in its top-left corner), sizes [B, 2] = (h, w), lut =
+// the 256 values of ToTensor + Normalize(0.5, 0.5) - the batch u8_to_patches_kernel takes.  The labels equal, integer for integer, those of
+// mpp_labels_kernel on Uint8Batch.float_image() of the same bytes, because the arithmetic and its order are that kernel's: the pixel is
+// lut[byte] * 0.5f + 0.5f (x * 0.5f is exact, so the contraction into an FMA cannot change a bit), a pixel outside its sample is the
+// collate zero of the float batch, 0 * 0.5f + 0.5f (NOT lut[0]: a fully padded patch of the dense form has the label 127), lane l takes
+// pixel group i = l + 64 k of patch line i >> 3, columns (i & 7) * 4 .. + 3, k ascending, pairwise inside the group, then the DPP wave sum.
+// In HWC a lane's four pixels of all three channels are 12 contiguous bytes: three dwords per k give the three channel sums in ONE pass
+// over the patch (the float kernel makes three passes over four times the bytes).
+__global__ __launch_bounds__(256) void mpp_labels_u8_kernel(const unsigned char* __restrict__ img, const int* __restrict__ sizes, int B, int Hmax,
+                                                            int Wmax, const float* __restrict__ lut, const int* __restrict__ sel,
+                                                            const int* __restrict__ counts, int sel_ld, int gw, int P, int* __restrict__ labels) {
+  __shared__ float tab[256];
+  tab[threadIdx.x] = lut[threadIdx.x];
+  __syncthreads();
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (slot >= B * P) return;
+  const int b = slot / P, j = slot - b * P, gh = Hmax / 32;
+  int patch = j;
+  bool valid = true;
+  if (sel) {
+    valid = j < counts[b] && j < sel_ld;
+    patch = valid ? sel[(long)b * sel_ld + j] : 0;
+  }
+  valid = valid && patch >= 0 && patch < gh * gw;
+  int* out = labels + (long)slot * 3;
+  if (!valid) {                                              // (wave-uniform)
+    if (lane < 3) out[lane] = -100;
+    return;
+  }
+  const int py = patch / gw, px = patch - py * gw;
+  // extents clamped to the padded batch, like u8_to_patches_kernel: no read leaves [Hmax, Wmax] whatever `sizes` holds
+  const int hb = min(sizes[2 * b], Hmax), wb = min(sizes[2 * b + 1], Wmax);
+  float s[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k, y = py * 32 + (i >> 3), x = px * 32 + (i & 7) * 4;
+    float u[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) u[c][q] = 0.f * 0.5f + 0.5f;
+    if (y < hb && x < wb) {                                  // (x + 3 < Wmax: the 12 bytes lie inside the row of the padded batch)
+      const uint3 w = *reinterpret_cast<const uint3*>(img + (((long)b * Hmax + y) * Wmax + x) * 3);
+      const unsigned wd[3] = {w.x, w.y, w.z};
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int byte = q * 3 + c;
+          if (x + q < wb) u[c][q] = tab[(wd[byte >> 2] >> ((byte & 3) * 8)) & 0xff] * 0.5f + 0.5f;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s[c] += sum4_pairwise(make_float4(u[c][0], u[c][1], u[c][2], u[c][3]));
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float t = wave_sum_dpp(s[c]);
+    const float val = (t * (1.0f / 1024.0f)) * 255.0f;
+    if (lane == 0) out[c] = (int)val;                        // truncation, like .long()
+  }
+}
+
 // ---- compaction -----------------------------------------------------------------------------------------------------------------------
 // labels [B, P, 3], masked [B, P].  A slot is LISTED when it is masked, valid (its labels are not the pad's -100) and all three labels lie
 // in [0, 256); a masked valid slot with a label outside adds its out-of-range entries to count[1] and is skipped.  idx[r] = the row
@@ -458,6 +521,20 @@ int rmcl_mpp_labels(const float* img, int B, int H, int W, const int32_t* sel, c
                "mpp_labels: images must be [B, 3, H, W] with H, W multiples of the 32-pixel patch");
   RMCL_REQUIRE(sel ? (gw == W / 32 && sel_ld >= 1) : P == (H / 32) * (W / 32), "mpp_labels: the dense form covers the whole grid (P = H/32 x W/32); gw = W/32");
   RMCL_LAUNCH(mpp_labels_kernel, dim3(cdiv((long)B * P, 4)), dim3(256), 0, (hipStream_t)stream, img, B, H, W, sel, counts, sel_ld, W / 32, P, labels);
+  RMCL_CHECK_LAUNCH();
+  return 0;
+}
+
+int rmcl_mpp_labels_u8(const uint8_t* img, const int32_t* sizes, int B, int Hmax, int Wmax, const float* lut, const int32_t* sel,
+                       const int32_t* counts, int sel_ld, int gw, int P, int32_t* labels, void* stream) {
+  RMCL_REQUIRE(img && sizes && lut && labels && (!sel || counts), "mpp_labels_u8: NULL argument");
+  RMCL_REQUIRE(B >= 1 && Hmax >= 32 && Wmax >= 32 && Hmax % 32 == 0 && Wmax % 32 == 0 && P >= 1 && (long)B * P <= (1L << 24),
+               "mpp_labels_u8: images must be [B, Hmax, Wmax, 3] with Hmax, Wmax multiples of the 32-pixel patch");
+  RMCL_REQUIRE(sel ? (gw == Wmax / 32 && sel_ld >= 1) : P == (Hmax / 32) * (Wmax / 32),
+               "mpp_labels_u8: the dense form covers the whole grid (P = Hmax/32 x Wmax/32); gw = Wmax/32");
+  RMCL_REQUIRE(((uintptr_t)img & 3) == 0, "mpp_labels_u8: img must be 4-byte aligned (the pixels are read as dwords)");
+  RMCL_LAUNCH(mpp_labels_u8_kernel, dim3(cdiv((long)B * P, 4)), dim3(256), 0, (hipStream_t)stream, img, sizes, B, Hmax, Wmax, lut, sel, counts, sel_ld,
+              Wmax / 32, P, labels);
   RMCL_CHECK_LAUNCH();
   return 0;
 }

@@ -789,10 +789,23 @@ class Engine:
         out.keep_alive = (raw.data, src, ssz, dsz, hb_d, hk_d, vb_d, vk_d, tmp) + aug_alive   # until the stream has consumed them
         return out
 
-    def _bind_uint8(self, text_ids, text_mask, u8, tag, select) -> PassBuffers:
-        from .vilt.datasets.base_dataset import select_from_sizes
-        from .vilt.transforms import normalize_lut
-        ps, S = self.cfg["patch_size"], self.cfg["image_size"]
+    def u8_on_device(self, image):
+        """``Uint8Batch`` / ``RawUint8Batch`` -> the ``Uint8Batch`` whose bytes lie on the device, its ``sizes`` validated on the host (the
+        byte kernels address the batch from them); a raw batch is resized first (``resize_raw``).  A batch that is already there comes
+        back as it is, so ``bind_batch`` and ``mpp_bind`` of one pass share ONE copy of the bytes."""
+        from .vilt.datasets.base_dataset import Uint8Batch
+        if hasattr(image, "tables"):
+            image = self.resize_raw(image)
+        data, _ = self._u8_ingest(image)
+        if data is image.data:
+            return image
+        out = Uint8Batch(data, image.sizes)
+        out.keep_alive = (image, getattr(image, "keep_alive", None))
+        return out
+
+    def _u8_ingest(self, u8):
+        """the bytes of a Uint8Batch on the device and its sizes [B, 2] on the host, checked against the padded batch"""
+        ps = self.cfg["patch_size"]
         data = self._h2d(u8.data).contiguous()
         B, Hh, Ww, _ = data.shape
         sz = torch.as_tensor(u8.sizes)
@@ -804,22 +817,39 @@ class Engine:
             # the ingest kernel addresses img + ((b * Hmax + y) * Wmax + x) * 3 from these extents: an extent outside the padded
             # batch (a hand-built batch, swapped (w, h)) would read past the sample
             raise ValueError(f"Uint8Batch.sizes must satisfy 1 <= h <= {Hh}, 1 <= w <= {Ww} (got {sz.tolist()})")
-        gh, gw = Hh // ps, Ww // ps
-        if gh * gw > 1024:
-            raise ValueError(f"at most 1024 patches per image ({gh}x{gw} given)")
+        if (Hh // ps) * (Ww // ps) > 1024:
+            raise ValueError(f"at most 1024 patches per image ({Hh // ps}x{Ww // ps} given)")
         if self._lut is None:
+            from .vilt.transforms import normalize_lut
             self._lut = normalize_lut().to(self.device)
-        full = Hh == S and Ww == S and select is None and bool((u8.sizes == S).all())
-        geom = None
-        if not full:
-            sel, counts, hw = select_from_sizes(u8.sizes, gh, gw, ps)
-            sel, counts, n = self._cap_selection(sel, counts, counts, select)   # on the host; to the device only afterwards
-            geom = RaggedGeometry(sel.to(self.device), counts.to(self.device), hw.to(self.device), n, gh, gw, (B, 3, Hh, Ww))
+        return data, sz.to(torch.int32).cpu()
+
+    def _u8_geometry(self, sz: torch.Tensor, Hh: int, Ww: int, select, max_image_len=None, check_tokens: bool = True):
+        """``patch_geometry`` of a byte batch, from its known extents `sz` (host): no selection launch, no read of the counts"""
+        from .vilt.datasets.base_dataset import select_from_sizes
+        ps, S = self.cfg["patch_size"], self.cfg["image_size"]
+        if Hh == S and Ww == S and select is None and bool((sz == S).all()):
+            return None
+        gh, gw = Hh // ps, Ww // ps
+        sel, counts, hw = select_from_sizes(sz, gh, gw, ps)
+        sel, counts, n = self._cap_selection(sel, counts, counts, select, max_image_len, check_tokens)   # on the host; to the device only afterwards
+        return RaggedGeometry(sel.to(self.device), counts.to(self.device), hw.to(self.device), n, gh, gw, (sz.shape[0], 3, Hh, Ww))
+
+    def _u8_patches(self, data: torch.Tensor, sizes: torch.Tensor, geom, pat: torch.Tensor):
+        """bytes [B, Hh, Ww, 3] and sizes [B, 2], both on the device -> the normalised patch rows `pat` (whole grid, or geom's selection)"""
+        B, Hh, Ww, _ = data.shape
+        ps = self.cfg["patch_size"]
+        check(lib.rmcl_image_u8_to_patches(P(data), P(sizes), P(geom.sel) if geom else None, P(geom.counts) if geom else None,
+                                           geom.sel.shape[1] if geom else 0, B, geom.n if geom else (Hh // ps) * (Ww // ps), Hh, Ww, ps, P(self._lut),
+                                           P(pat), stream_ptr()), "image_u8_to_patches")
+
+    def _bind_uint8(self, text_ids, text_mask, u8, tag, select) -> PassBuffers:
+        data, sz = self._u8_ingest(u8)
+        B, Hh, Ww, _ = data.shape
+        geom = self._u8_geometry(sz, Hh, Ww, select)
         pb = self._bind(text_ids, text_mask, geom, B, tag)
         sizes = self._h2d(u8.sizes)
-        check(lib.rmcl_image_u8_to_patches(P(data), P(sizes), P(geom.sel) if geom else None, P(geom.counts) if geom else None,
-                                           geom.sel.shape[1] if geom else 0, B, geom.n if geom else gh * gw, Hh, Ww, ps, P(self._lut),
-                                           P(pb.patches32), stream_ptr()), "image_u8_to_patches")
+        self._u8_patches(data, sizes, geom, pb.patches32)
         pb.keep_alive = (data, sizes, u8, getattr(u8, "keep_alive", None))      # until the stream has consumed them
         return pb
 
@@ -1197,7 +1227,15 @@ class Engine:
         """Labels of the batch's image slots from the float image `img` [B, 3, H, W] (on the device), the two full-grid masks [B, G]
         gathered through `pb`'s patch selection into [B, P] (pad slots: 0), and the compaction of the masked valid slots.  The launch
         extent comes from the host-known number of masked patches; n stays on the device.  A pixel mean outside [0, 1] (pixels outside
-        [-1, 1]) is a ValueError, like the reference's cross_entropy raising on a label outside 0..255."""
+        [-1, 1]) is a ValueError, like the reference's cross_entropy raising on a label outside 0..255.
+        `img` may be a ``Uint8Batch`` / ``RawUint8Batch`` instead: the labels then come from the bytes (rmcl_mpp_labels_u8: the same
+        integers as from ``float_image()``, which is never built), G from the batch's ``shape``."""
+        u8 = None
+        if not torch.is_tensor(img):
+            u8 = self.u8_on_device(img)
+            u8_sizes = self._h2d(u8.sizes)
+            mp.keep_alive = (u8, u8_sizes)                                    # until the stream has consumed them
+            img = u8
         B, _, Hh, Ww = img.shape
         ps = int(self.cfg["patch_size"])
         if ps != 32:
@@ -1210,12 +1248,18 @@ class Engine:
         n_host = int(masked.sum()) if masked.device.type == "cpu" else B * Pn
         mk = masked.to(self.device).to(torch.int32)
         rp = (replaced.to(self.device) & masked.to(self.device)).to(torch.int32) if replaced.dtype == torch.bool else replaced.to(self.device, torch.int32) * mk
-        if geom is None:
+        if u8 is not None:
+            check(lib.rmcl_mpp_labels_u8(P(u8.data), P(u8_sizes), B, Hh, Ww, P(self._lut), P(geom.sel) if geom else None,
+                                         P(geom.counts) if geom else None, geom.sel.shape[1] if geom else 0, Ww // ps, Pn, P(mp.labels),
+                                         stream_ptr()), "mpp_labels_u8")
+        elif geom is None:
             check(lib.rmcl_mpp_labels(P(img), B, Hh, Ww, None, None, 0, Ww // ps, Pn, P(mp.labels), stream_ptr()), "mpp_labels")
-            mp.masked, mp.replaced = mk.contiguous(), rp.contiguous()
         else:
             check(lib.rmcl_mpp_labels(P(img), B, Hh, Ww, P(geom.sel), P(geom.counts), geom.sel.shape[1], geom.gw, Pn, P(mp.labels), stream_ptr()),
                   "mpp_labels")
+        if geom is None:
+            mp.masked, mp.replaced = mk.contiguous(), rp.contiguous()
+        else:
             sel = geom.sel[:, :Pn].to(torch.int64).clamp_(0, G - 1)
             valid = (torch.arange(Pn, device=self.device)[None, :] < geom.counts[:, None]).to(torch.int32)
             mp.masked = (torch.gather(mk, 1, sel) * valid).contiguous()
@@ -1316,10 +1360,16 @@ class Engine:
         Runs once per image, so its buffers are allocated per call (the caching allocator hands the same blocks back)."""
         if self.lp_stale:
             self.refresh_shadows()
-        img = images.to(self.device, torch.float32).contiguous()
-        B, _, Hh, Ww = img.shape
         ps = self.cfg["patch_size"]
-        geom = self.patch_geometry(img, select, max_image_len=max_image_len, check_tokens=False)
+        u8 = None
+        if torch.is_tensor(images):
+            img = images.to(self.device, torch.float32).contiguous()
+            B, _, Hh, Ww = img.shape
+            geom = self.patch_geometry(img, select, max_image_len=max_image_len, check_tokens=False)
+        else:                                                          # Uint8Batch / RawUint8Batch: geometry from the extents, rows from the bytes
+            img = u8 = self.u8_on_device(images)
+            B, _, Hh, Ww = u8.shape
+            geom = self._u8_geometry(self._u8_ingest(u8)[1], Hh, Ww, select, max_image_len=max_image_len, check_tokens=False)
         g = self.cfg["image_size"] // ps
         n = g * g if geom is None else geom.n
         if self.long_sequences and n + 1 + int(self.cfg["max_text_len"]) > self.token_cap:
@@ -1331,7 +1381,10 @@ class Engine:
         pat32 = torch.empty(B * n, d.patch_k, dtype=torch.float32, device=self.device)
         op = pat32 if self.dtype == L.F32 else torch.empty(B * n, d.patch_k, dtype=torch.bfloat16, device=self.device)
         rg = None
-        self._im2patch(img, pat32, geom, B, Hh, Ww)
+        if u8 is None:
+            self._im2patch(img, pat32, geom, B, Hh, Ww)
+        else:
+            self._u8_patches(u8.data, self._h2d(u8.sizes), geom, pat32)
         if geom is None:
             ii, jj = torch.meshgrid(torch.arange(g), torch.arange(g), indexing="ij")
             patch_index = torch.stack([ii, jj], dim=-1).reshape(1, g * g, 2).expand(B, -1, -1)

@@ -28,6 +28,10 @@ class Nlvr2Pass:
         img0, img1 = batch["image_0"][0], batch["image_1"][0]
         B = int(img0.shape[0])
         if pl_module.hparams.config.get("nlvr2_pair_pass", True):
+            if not torch.is_tensor(img0) or not torch.is_tensor(img1):
+                # byte feeds: the pair pass interleaves the two images pixel by pixel (Engine.bind_pair), which needs float pixels
+                from .attack.pgd_attack_vilt import device_image
+                img0, img1 = device_image(eng, img0), device_image(eng, img1)
             return cls(eng, [eng.bind_pair(batch["text_ids"], batch["text_masks"], img0, img1, tag=tag)], B, True)
         views = []
         for t, img in ((1, img0), (2, img1)):                  # geometry drawn in the reference's order: image_0, then image_1

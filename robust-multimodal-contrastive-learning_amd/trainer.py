@@ -3,6 +3,7 @@ resume and the ``test_only`` switch around ``ViLTransformerSS.training_step`` an
 
     trainer = Trainer(config)
     trainer.fit(model, train_loader, val_loader)       # or trainer.run(model, train_loader, val_loader, test_loader)
+    trainer.run(model)                                 # no loaders: MTDataModule(config) builds them from config["data_root"]
 
 What it takes from ``run.py``: ``accumulate_grad_batches`` (:86-88, :105), ``max_steps`` / ``max_epochs`` (:90-100), ``val_check_interval``
 (:111), a ModelCheckpoint with ``save_last`` and ``save_top_k=1`` on ``val/the_metric``, mode max (:46-52), ``resume_from_checkpoint`` (:108),
@@ -130,6 +131,22 @@ class Trainer:
         self.best_metric = None
         self.validations = 0
         self.optimizer = self.scheduler = None
+        self.datamodule = None
+
+    def attach_datamodule(self, model):
+        """run.py:40 for the calls that bring no loader: ``MTDataModule(config, dist=<a process group is initialised>)``, set up once and
+        kept as ``self.datamodule``.  ``model.trainer = self`` is what ``compute_irtr_recall`` (get_recall_metric) reads its validation
+        datasets through; a VQA datamodule hands the model its ``id2answer``."""
+        if self.datamodule is None:
+            from .vilt.datamodules import MTDataModule
+            dist = torch.distributed.is_available() and torch.distributed.is_initialized()
+            self.datamodule = MTDataModule(self.config, dist=dist)
+            self.datamodule.setup("fit")
+        model.trainer = self
+        vqa = self.datamodule.dm_dicts.get("vqa")
+        if vqa is not None:
+            model.id2answer = vqa.id2answer
+        return self.datamodule
 
     # run.py:114-118
     def run(self, model, train_loader=None, val_loader=None, test_loader=None):
@@ -149,9 +166,9 @@ class Trainer:
         model.train(was_training)
         return getattr(model, "last_epoch_metrics", {})
 
-    def test(self, model, loader):
-        if loader is None:
-            raise ValueError("Trainer.test: no loader")
+    def test(self, model, loader=None):
+        if loader is None:                                   # no loader: the config's datamodule (config["datasets"], config["data_root"])
+            loader = self.attach_datamodule(model).test_dataloader()
         return self._eval_loop(model, loader, model.test_step, model.test_epoch_end)
 
     def validate(self, model, loader):
@@ -174,10 +191,14 @@ class Trainer:
             self._save(BEST, model, n_batches)
         self._save(LAST, model, n_batches)
 
-    def fit(self, model, train_loader, val_loader=None):
+    def fit(self, model, train_loader=None, val_loader=None):
         cfg = self.config
         if cfg.get("test_only", False):
             return self.test(model, val_loader)
+        if train_loader is None:                             # no loader: the config's datamodule, its validation loader included
+            dm = self.attach_datamodule(model)
+            train_loader = dm.train_dataloader()
+            val_loader = dm.val_dataloader() if val_loader is None else val_loader
         fast = bool(cfg.get("fast_dev_run", False))
         n_batches = len(train_loader)
         max_epochs = 1000                                    # run.py:99

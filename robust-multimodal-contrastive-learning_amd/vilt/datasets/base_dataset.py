@@ -34,18 +34,54 @@ def default_collator(max_text_len: int = 40, pad_id: int = 0) -> Callable:
 
 
 def masking_collator(mask_id: int, vocab_size: int, special_ids=(), mlm_prob: float = 0.15, max_text_len: int = 40, pad_id: int = 0,
-                     generator: Optional[torch.Generator] = None, whole_word_masking: bool = False) -> Callable:
+                     generator: Optional[torch.Generator] = None, whole_word_masking: bool = False, continuation_ids=None) -> Callable:
     """The masked-LM collator of the reference's datamodule (datamodule_base.py:57-65: HF ``DataCollatorForLanguageModeling``, BERT
     rule): every token that is neither special (``special_ids``: [CLS], [SEP], ...) nor padding is chosen with probability
     ``mlm_prob``; of the chosen, 80 % become ``mask_id``, 10 % a uniformly random id of [0, vocab_size), 10 % stay; ``labels`` hold the
     original id on the chosen positions and -100 everywhere else.  ``generator`` makes the draw reproducible (the random stream is
-    this function's own, not HF's).  Whole-word masking is not built."""
-    if whole_word_masking:
-        raise NotImplementedError("whole_word_masking=True (DataCollatorForWholeWordMask) is not built")
+    this function's own, not HF's).
+
+    ``whole_word_masking`` (HF ``DataCollatorForWholeWordMask``'s rule, per sentence): a word is a piece and the ``##`` pieces that
+    follow it (``continuation_ids``: the ids of the vocabulary's ``##`` tokens); special and padding tokens are never candidates and end
+    a word.  The words are visited in a random order; with n_tokens the sentence's tokens (specials included, padding not) the budget is
+    num_to_predict = min(512, max(1, round(n_tokens * mlm_prob))): a word that would take the chosen set past it is skipped, and the
+    visit ends once the budget is reached.  The chosen tokens then take the 80 / 10 / 10 rule above.  Without ``continuation_ids`` words
+    cannot be told from pieces: that call is refused as before."""
+    if whole_word_masking and continuation_ids is None:
+        raise NotImplementedError("whole_word_masking=True (DataCollatorForWholeWordMask) is not built without continuation_ids, the ids of "
+                                  "the vocabulary's ## tokens (the datamodule computes them from its tokenizer)")
     if not 0.0 <= mlm_prob <= 1.0:
         raise ValueError(f"mlm_prob must lie in [0, 1] (got {mlm_prob})")
     special = torch.tensor(sorted({int(pad_id), *[int(i) for i in special_ids]}), dtype=torch.int64)
+    continuation = torch.tensor(sorted({int(i) for i in continuation_ids or ()}), dtype=torch.int64)
     pad = default_collator(max_text_len, pad_id)
+
+    def whole_words(ids: torch.Tensor, valid: torch.Tensor, free: torch.Tensor) -> torch.Tensor:
+        chosen = torch.zeros_like(free)
+        cont = torch.isin(ids, continuation)
+        for b in range(ids.shape[0]):
+            words: List[List[int]] = []
+            open_word = False                                  # a ## piece joins the word before it only when nothing special lies between
+            for t in range(ids.shape[1]):
+                if not bool(free[b, t]):
+                    open_word = False
+                    continue
+                if open_word and bool(cont[b, t]):
+                    words[-1].append(t)
+                else:
+                    words.append([t])
+                open_word = True
+            n_tokens = int((valid[b] & (ids[b] != pad_id)).sum())
+            budget = min(512, max(1, int(round(n_tokens * mlm_prob))))
+            n = 0
+            for w in torch.randperm(len(words), generator=generator).tolist():
+                if n >= budget:
+                    break
+                if n + len(words[w]) > budget:
+                    continue
+                chosen[b, words[w]] = True
+                n += len(words[w])
+        return chosen
 
     def mask(encodings: List[dict]) -> Dict[str, torch.Tensor]:
         ids = pad(encodings)["input_ids"]
@@ -53,8 +89,11 @@ def masking_collator(mask_id: int, vocab_size: int, special_ids=(), mlm_prob: fl
         for row, enc in zip(valid, encodings):
             row[: min(len(enc["input_ids"]), max_text_len)] = True
         free = valid & ~torch.isin(ids, special)
-        u = torch.rand(ids.shape, generator=generator)
-        chosen = free & (u < mlm_prob)
+        if whole_word_masking:
+            chosen = whole_words(ids, valid, free)
+        else:
+            u = torch.rand(ids.shape, generator=generator)
+            chosen = free & (u < mlm_prob)
         kind = torch.rand(ids.shape, generator=generator)
         rand_ids = torch.randint(0, vocab_size, ids.shape, generator=generator, dtype=torch.int64)
         labels = torch.where(chosen, ids, torch.full_like(ids, -100))

@@ -245,7 +245,8 @@ def compute_mlm(pl_module, batch):
 
 
 def _mpp_pass(pl_module, batch, text_ids, tag, mode):
-    """The masked-image encoder pass shared by compute_mpp and infer(mask_image=True): the float image on the device, the two mask draws
+    """The masked-image encoder pass shared by compute_mpp and infer(mask_image=True): the image on the device (float, or the bytes of a
+    Uint8Batch / RawUint8Batch), the two mask draws
     (batch["mpp_masked"] / ["mpp_replaced"] [B, G] bool replace them) BEFORE the patch selection's own draws - the reference's order
     (vision_transformer.py:602-603 before :632-645) -, the labels and the compaction, then the encoder forward with the mask-token
     substitution.  Returns (pb, mp, op, img)."""
@@ -255,9 +256,12 @@ def _mpp_pass(pl_module, batch, text_ids, tag, mode):
         raise NotImplementedError("MPP masking (mask_image=True / compute_mpp) needs a model built with loss_names['mpp'] > 0 "
                                   "(transformer.mask_token and the mpp_score head)")
     image = batch["image"][0]
-    if not torch.is_tensor(image):
-        raise NotImplementedError("the MPP pass reads its labels from the float image: Uint8Batch / RawUint8Batch feeds are not built for it")
-    img = image.to(eng.device, torch.float32).contiguous()
+    if torch.is_tensor(image):
+        img = image.to(eng.device, torch.float32).contiguous()
+    else:
+        # byte feeds (Uint8Batch; a RawUint8Batch is resized on the device first): the patch rows AND the labels come from the bytes
+        # (rmcl_image_u8_to_patches, rmcl_mpp_labels_u8) - no float image exists on this path
+        img = eng.u8_on_device(image)
     B, _, Hh, Ww = img.shape
     ps = int(pl_module.hparams.config["patch_size"])
     G = (Hh // ps) * (Ww // ps)

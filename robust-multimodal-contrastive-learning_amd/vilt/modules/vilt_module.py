@@ -571,7 +571,7 @@ class ViLTransformerSS(nn.Module):
         fourth value.  Labels and masks take the path of compute_mpp (Engine.mpp_bind)."""
         from ...runtime import mpp_draw_masks
         eng, ps = self.engine, self.config["patch_size"]
-        img = images.to(eng.device, torch.float32).contiguous()
+        img = images.to(eng.device, torch.float32).contiguous() if torch.is_tensor(images) else eng.u8_on_device(images)   # (byte feeds stay bytes)
         B, _, Hh, Ww = img.shape
         masks = mpp_masks if mpp_masks is not None else mpp_draw_masks(B, (Hh // ps) * (Ww // ps))
         emb, msk, patch_index, mp = eng.visual_embed(img, max_image_len=max_image_len, select=select, mpp_masks=masks)

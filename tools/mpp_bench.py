@@ -7,7 +7,13 @@ events, medians; (c) the head alone at the same shape: the compacted path (gathe
 backward with all weight gradients, scatter; the bind - labels, mask gather, compaction - is timed apart) against the reference's
 schedule - the same head on ALL B (1 + P) image rows in torch (bf16 autocast linear layers, fp32 cross_entropy with ignore_index over
 [B (1 + P) 3, 256], autograd backward) - and, forward only, against this library's own all-rows listing (the dense-logits pass).  The
-variants alternate inside one process; medians.  Nothing here is a pass criterion: the comparison figure is the all-rows baseline of the same run."""
+variants alternate inside one process; medians.  Nothing here is a pass criterion: the comparison figure is the all-rows baseline of the same run.
+
+  python tools/mpp_bench.py --u8 [--bs 64] [--steps 20] [--head-iters 20] [--out profiles/mpp_u8_bench.json]
+
+The byte feed: (d) stream time of rmcl_mpp_labels_u8 on a Uint8Batch against rmcl_mpp_labels on its float image (B x 384 x 384, dense
+form), alternating in one process, medians; (e) the `mpp` and `mlm + itm + mpp` steps fed the Uint8Batch against the same steps of the same
+model fed the float batch, alternating step by step.  One JSON object, written to --out."""
 import argparse
 import json
 import os
@@ -105,6 +111,62 @@ def head_alone(m, cfg, batch, a, dev):
             "all_rows": B * (P + 1)}
 
 
+def byte_feed(a, dev):
+    from rmcl_amd._lib import lib, check, P
+    from rmcl_amd.runtime import stream_ptr
+    from rmcl_amd.vilt.datasets import Uint8Batch
+    from rmcl_amd.vilt.transforms import normalize_lut
+    B, S = a.bs, 384
+    g = torch.Generator().manual_seed(1)
+    u8 = Uint8Batch(torch.randint(0, 256, (B, S, S, 3), generator=g, dtype=torch.uint8).to(dev), torch.full((B, 2), S, dtype=torch.int32))
+    img = u8.float_image().contiguous()
+    sizes, lut = u8.sizes.to(dev), normalize_lut().to(dev)
+    Pn = (S // 32) ** 2
+    lab_f = torch.empty(B, Pn, 3, dtype=torch.int32, device=dev)
+    lab_b = torch.empty_like(lab_f)
+    fns = {"labels_f32": lambda: check(lib.rmcl_mpp_labels(P(img), B, S, S, None, None, 0, S // 32, Pn, P(lab_f), stream_ptr())),
+           "labels_u8": lambda: check(lib.rmcl_mpp_labels_u8(P(u8.data), P(sizes), B, S, S, P(lut), None, None, 0, S // 32, Pn, P(lab_b), stream_ptr()))}
+    t = {k: [] for k in fns}
+    for i in range(a.head_iters + 5):
+        ev = {}
+        for k, fn in fns.items():
+            ev[k] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[k][0].record(); fn(); ev[k][1].record()
+        torch.cuda.synchronize()
+        if i >= 5:
+            for k in t:
+                t[k].append(ev[k][0].elapsed_time(ev[k][1]))
+    out = {"labels_equal": bool(torch.equal(lab_f, lab_b)), "labels_repeats": a.head_iters,
+           "labels_f32_ms": round(median(t["labels_f32"]), 4), "labels_f32_ms_min": round(min(t["labels_f32"]), 4),
+           "labels_u8_ms": round(median(t["labels_u8"]), 4), "labels_u8_ms_min": round(min(t["labels_u8"]), 4)}
+    for name, tasks in (("mpp", {"mpp": 1}), ("mlm+itm+mpp", {"mlm": 1, "itm": 1, "mpp": 1})):
+        cfg = task_mlm_itm_mpp(num_layers=a.layers, per_gpu_batchsize=B, max_steps=10 ** 6, warmup_steps=0, loss_names=_loss_names(tasks))
+        m = ViLTransformerSS(cfg, device=dev, compute_dtype=a.dtype)
+        (opt,), _ = m.configure_optimizers()
+        m.train()
+        base = batch_of(B, cfg, dev)
+        u8f = Uint8Batch(torch.roll(u8.data, 1, 0).contiguous(), u8.sizes)
+        feeds = {"float": dict(base, image=[img], false_image_0=[u8f.float_image().contiguous()]), "bytes": dict(base, image=[u8], false_image_0=[u8f])}
+        ms = {k: [] for k in feeds}
+        for i in range(a.warmup + a.steps):
+            for k, batch in feeds.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                m.zero_grad()
+                loss = m.training_step(dict(batch), i)
+                loss.backward()
+                opt.step()
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= a.warmup:
+                    ms[k].append(e0.elapsed_time(e1))
+        out[name] = {"steps": a.steps, "float_ms_per_step": round(median(ms["float"]), 3), "float_ms_min": round(min(ms["float"]), 3),
+                     "bytes_ms_per_step": round(median(ms["bytes"]), 3), "bytes_ms_min": round(min(ms["bytes"]), 3)}
+        del m, opt
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bs", type=int, default=64)
@@ -113,13 +175,22 @@ def main():
     ap.add_argument("--head-iters", type=int, default=20)
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mpp_bench.jsonl"))
+    ap.add_argument("--out", default=None, help="default: profiles/mpp_bench.jsonl (appended), with --u8 profiles/mpp_u8_bench.json (written)")
     ap.add_argument("--commit", default="unknown")
+    ap.add_argument("--u8", action="store_true", help="the byte feed against the float feed (labels kernel and steps); one JSON object to --out")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "mpp_u8_bench.json" if a.u8 else "mpp_bench.jsonl")
     dev = "cuda:0"
     prop = torch.cuda.get_device_properties(0)
     env = {"box": socket.gethostname(), "device": prop.name, "clocks": clocks(), "cus": prop.multi_processor_count,
            "commit": a.commit, "bs": a.bs, "layers": a.layers, "dtype": a.dtype, "text_len": 40, "image": 384, "mask_prob": 0.15}
+    if a.u8:
+        rec = dict(env, metric="mpp_u8_feed", **byte_feed(a, dev))
+        print(json.dumps(rec))
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(rec, indent=1) + "\n")
+        return
     lines = []
     m, cfg, batch, med, lo, hi, loss, n = time_steps({"mpp": 1}, a, dev)
     lines.append(dict(env, metric="mpp_step_ms", task="mpp", ms_per_step=round(med, 3), ms_min=round(lo, 3), ms_max=round(hi, 3),
