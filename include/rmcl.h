@@ -653,6 +653,30 @@ int rmcl_adamw_guarded_f32(float* p, const float* g, float* m, float* v, void* p
                            const float* seg_lr_mult, const float* seg_wd, int nseg, float lr, float beta1, float beta2,
                            float eps, float grad_scale, const rmcl_step_ctl* ctl, int64_t n, void* stream);
 
+/* Adam and SGD over the same flat arenas (vilt/modules/vilt_utils.py:399-402: torch.optim.Adam(groups, lr) and
+ * torch.optim.SGD(groups, lr, momentum=0.9)), with rmcl_adamw_f32's segment tables, grad_scale and optional bf16 shadow p_lp.
+ * All arithmetic in fp32, per element, in this order (slr = lr * seg_lr_mult[s], wd = seg_wd[s] of the element's segment s):
+ *   gj = g * grad_scale                      guarded form: gj = (g * grad_scale) * clip_coef
+ *   if wd > 0: gj = gj + wd * p              torch's coupled L2 decay, on the OLD p
+ *   RMCL_OPTIM_ADAM  (torch.optim.Adam, amsgrad off; the reference's defaults: betas (0.9, 0.999), eps 1e-8)
+ *     m = b1 * m + (1 - b1) * gj
+ *     v = b2 * v + (1 - b2) * gj * gj
+ *     p = p - ((slr / bc1) * m) / (sqrt(v) / bc2s + eps)        bc1 = 1 - b1^t, bc2s = sqrt(1 - b2^t), each computed in double and
+ *                                                               rounded once; eps is added AFTER the division by bc2s (rmcl_adamw_f32,
+ *                                                               HF AdamW, adds it before)
+ *   RMCL_OPTIM_SGD   (torch.optim.SGD with momentum, dampening 0, nesterov off; beta1 IS the momentum, beta2 and eps are ignored)
+ *     m = b1 * m + gj                                           (m zero-filled before the first step gives torch's buf = gj)
+ *     p = p - slr * m
+ *     v must be NULL: SGD keeps no second moment.
+ * ctl == NULL: the plain form, t = step (>= 1).  ctl != NULL: the guarded form, `step` is ignored; ctl->skip set, no byte of p, m, v
+ * or p_lp is written; otherwise clip_coef and, for Adam, bc1 / bc2s are read from ctl as rmcl_grad_stats_f32 (called with Adam's betas)
+ * left them.  With clip_coef == 1 the guarded form gives the plain form's bits.  n > 0, n % 4 == 0, nseg > 0.              */
+#define RMCL_OPTIM_ADAM 1
+#define RMCL_OPTIM_SGD 2
+int rmcl_optim_step_f32(int rule, float* p, const float* g, float* m, float* v, void* p_lp, const int64_t* seg_end,
+                        const float* seg_lr_mult, const float* seg_wd, int nseg, float lr, float beta1, float beta2, float eps,
+                        int step, float grad_scale, const rmcl_step_ctl* ctl, int64_t n, void* stream);
+
 /* ITM + word-patch alignment (objectives.py:24-76,714-787).  cost / dsim are [B, Lt, ld] f32 with
  * ld >= Li a multiple of 4 (GEMM operand pitch); T is [B, Li, Lt] like the reference's ipot().      */
 int rmcl_gemm_batched(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int ldc, float alpha,

@@ -17,6 +17,7 @@ MODE_CLS_TAIL = 16        # include/rmcl.h RMCL_MODE_CLS_TAIL
 MODE_STREAM_ATTN = 32     # include/rmcl.h RMCL_MODE_STREAM_ATTN
 PGD_DELTA_ZERO, PGD_SUM_PREV = 1, 2   # include/rmcl.h RMCL_PGD_*
 HEADS_NO_WGRAD = 1                    # include/rmcl.h RMCL_HEADS_NO_WGRAD
+OPTIM_ADAM, OPTIM_SGD = 1, 2          # include/rmcl.h RMCL_OPTIM_*
 EPI_BIAS, EPI_GELU, EPI_SAVE_PREACT, EPI_RESIDUAL, EPI_DGELU, EPI_ATOMIC, EPI_ACCUM, EPI_TANH = 1, 2, 4, 8, 16, 32, 64, 128
 EPI_LNFOLD, EPI_ROWSTAT = 2048, 4096
 
@@ -122,7 +123,7 @@ EXPORTS = (
     "rmcl_last_error", "rmcl_version", "rmcl_prof_begin", "rmcl_prof_end", "rmcl_tune_set", "rmcl_grad_ready_wait", "rmcl_set_side_stream", "rmcl_set_prefetch_stream", "rmcl_dropout_mask_apply", "rmcl_param_layout", "rmcl_ln_fold_elems", "rmcl_ln_fold", "rmcl_linear_rowstat", "rmcl_linear_lnfold", "rmcl_linear_rowstat_c", "rmcl_linear_lnfold_c", "rmcl_weight_transpose_bf16", "rmcl_stash_bytes", "rmcl_workspace_bytes",
     "rmcl_heads_stash_bytes", "rmcl_im2patch_f32", "rmcl_patch_select", "rmcl_im2patch_sel", "rmcl_image_u8_to_patches", "rmcl_image_resize_u8", "rmcl_randaug_scratch_bytes", "rmcl_randaug_u8", "rmcl_add_cast_f32", "rmcl_shard_sum", "rmcl_encoder_forward", "rmcl_encoder_backward",
     "rmcl_heads_forward", "rmcl_heads_forward2", "rmcl_heads_backward", "rmcl_infonce_ws_bytes", "rmcl_infonce_f32", "rmcl_infonce_split_bf16", "rmcl_pgd_step", "rmcl_pgd_step_fused",
-    "rmcl_delta_channel_norm", "rmcl_ema_f32", "rmcl_enqueue_f32", "rmcl_cast_f32", "rmcl_adamw_f32", "rmcl_grad_stats_ws_bytes", "rmcl_grad_stats_f32", "rmcl_adamw_guarded_f32", "rmcl_ipot_f32", "rmcl_gemm_batched", "rmcl_l2norm_rows_fwd", "rmcl_l2norm_rows_bwd",
+    "rmcl_delta_channel_norm", "rmcl_ema_f32", "rmcl_enqueue_f32", "rmcl_cast_f32", "rmcl_adamw_f32", "rmcl_grad_stats_ws_bytes", "rmcl_grad_stats_f32", "rmcl_adamw_guarded_f32", "rmcl_optim_step_f32", "rmcl_ipot_f32", "rmcl_gemm_batched", "rmcl_l2norm_rows_fwd", "rmcl_l2norm_rows_bwd",
     "rmcl_wpa_cost_finish", "rmcl_wpa_distance", "rmcl_itm_fwd", "rmcl_itm_bwd",
     "rmcl_gemm", "rmcl_gemm_rows_bf16", "rmcl_rows_gather_f32", "rmcl_gemm_chain", "rmcl_l2_prefetch_experiment", "rmcl_gemm_route", "rmcl_gemm_kblk", "rmcl_layernorm_fwd", "rmcl_layernorm_bwd", "rmcl_attention_scratch_elems", "rmcl_attention_fwd",
     "rmcl_attention_bwd", "rmcl_attention_stream_stat_elems", "rmcl_attention_stream_fwd", "rmcl_attention_stream_bwd",

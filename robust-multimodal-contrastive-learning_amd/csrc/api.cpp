@@ -430,6 +430,13 @@ int rmcl_adamw_guarded_f32(float* p, const float* g, float* m, float* v, void* p
   return rmcl_adamw_guarded(p, g, m, v, p_lp, (const long*)seg_end, seg_lr_mult, seg_wd, nseg, lr, beta1, beta2, eps, grad_scale, ctl, n,
                             (hipStream_t)stream);
 }
+int rmcl_optim_step_f32(int rule, float* p, const float* g, float* m, float* v, void* p_lp, const int64_t* seg_end,
+                        const float* seg_lr_mult, const float* seg_wd, int nseg, float lr, float beta1, float beta2, float eps, int step,
+                        float grad_scale, const rmcl_step_ctl* ctl, int64_t n, void* stream) {
+  RMCL_REQUIRE(p && g && m && seg_end && seg_lr_mult && seg_wd, "optim_step: NULL argument");
+  return rmcl_optim_step(rule, p, g, m, v, p_lp, (const long*)seg_end, seg_lr_mult, seg_wd, nseg, lr, beta1, beta2, eps, step, grad_scale,
+                         ctl, n, (hipStream_t)stream);
+}
 int rmcl_ipot_f32(const float* cost, const int32_t* txt_valid, const int32_t* img_valid, float* T, int B, int Lt, int Li,
                   int ld, float beta, int iters, void* stream) {
   RMCL_REQUIRE(cost && txt_valid && img_valid && T, "ipot: NULL argument");

@@ -162,6 +162,10 @@ int rmcl_grad_stats(const float* g, long n, float grad_scale, float max_norm, fl
 int rmcl_adamw_guarded(float* p, const float* g, float* m, float* v, void* p_lp, const long* seg_end, const float* seg_lr_mult,
                        const float* seg_wd, int nseg, float lr, float b1, float b2, float eps, float grad_scale, const rmcl_step_ctl* ctl,
                        long n, hipStream_t s);
+// optim.hip: Adam / SGD sweep (rule: RMCL_OPTIM_*, include/rmcl.h); ctl NULL = plain form (reads step), ctl given = guarded form
+int rmcl_optim_step(int rule, float* p, const float* g, float* m, float* v, void* p_lp, const long* seg_end, const float* seg_lr_mult,
+                    const float* seg_wd, int nseg, float lr, float b1, float b2, float eps, int step, float grad_scale,
+                    const rmcl_step_ctl* ctl, long n, hipStream_t s);
 
 long rmcl_infonce_workspace_bytes(int B, long Kq);
 // form 0: exact-f32 matrix cores (the fp32 parity engine); 1: split-bf16 matrix cores (x = hi + lo, three products: 2^-16 relative);

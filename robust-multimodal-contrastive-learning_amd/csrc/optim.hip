@@ -1,6 +1,7 @@
 // Guarded optimizer step: one statistics pass over the fp32 gradient arena that takes the skip / clip decision ON THE DEVICE
 // (rmcl_step_ctl, include/rmcl.h), and the AdamW of embed_misc.hip reading that decision.  Both are pure streaming passes (4 B per
-// element read; 16 B read + 14 B written): 16-byte loads, grids sized to the CUs, grid-stride loops.
+// element read; 16 B read + 14 B written): 16-byte loads, grids sized to the CUs, grid-stride loops.  Below them, the Adam and SGD
+// sweeps (optim_rule_kernel), plain and guarded.
 #include "rmcl_common.h"
 #include "kernels.h"
 #include "../../include/rmcl.h"
@@ -162,6 +163,95 @@ int rmcl_adamw_guarded(float* p, const float* g, float* m, float* v, void* p_lp,
   RMCL_REQUIRE(n > 0 && n % 4 == 0 && nseg > 0, "adamw_guarded: bad args");
   RMCL_LAUNCH(adamw_guarded_kernel, dim3(std::min<long>(cdiv(n / 4, 256), 2048)), dim3(256), 0, s, p, g, m, v, (bf16_t*)p_lp, seg_end,
               seg_lr_mult, seg_wd, nseg, lr, b1, b2, eps, ctl, n / 4, grad_scale);
+  RMCL_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adam and SGD (the other two optim_type values of vilt_utils.set_schedule :399-402) over the same arenas, segment tables and bf16
+// shadow as adamw_kernel: one float4 per thread and trip, the segment looked up per float4, 16-byte loads and stores, no atomics, no
+// scratch.  gj = g * grad_scale (* clip_coef, guarded); both rules use torch's COUPLED L2 decay, gj += wd * p where the segment's wd > 0.
+//   Adam (torch.optim.Adam, single tensor, amsgrad off):
+//     m = b1 m + (1 - b1) gj;  v = b2 v + (1 - b2) gj^2;  p = p - ((slr / bc1) * m) / (sqrt(v) / bc2s + eps)
+//     eps is added AFTER the division by bc2s = sqrt(1 - b2^t); adamw_kernel (HF AdamW) adds it before.
+//   SGD (torch.optim.SGD, momentum b1, dampening 0, nesterov off):
+//     m = b1 m + gj;  p = p - slr * m
+//     torch's first step sets the buffer to gj, which is this update on a zero buffer: no first-step arm.  v is neither read nor written.
+// GUARDED: skip set -> return before the first store; otherwise clip_coef (and, for Adam, bc1 / bc2s) come from ctl.  The product with
+// clip_coef == 1 is exact, so the unclipped guarded form gives the plain form's bits.
+// Bytes per element: Adam 16 read + 12 written, SGD 12 + 8; + 2 written with the shadow.
+// ---------------------------------------------------------------------------------------------
+template <int RULE, bool GUARDED>
+__global__ __launch_bounds__(256) void optim_rule_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, bf16_t* __restrict__ p_lp, const long* __restrict__ seg_end,
+                                                         const float* __restrict__ seg_lr_mult, const float* __restrict__ seg_wd, int nseg,
+                                                         float lr, float b1, float b2, float eps, float bc1, float bc2s,
+                                                         const rmcl_step_ctl* __restrict__ ctl, long n4, float grad_scale) {
+  float clip_coef = 1.0f;
+  if (GUARDED) {
+    if (ctl->skip) return;
+    clip_coef = ctl->clip_coef;
+    if (RULE == RMCL_OPTIM_ADAM) { bc1 = ctl->bc1; bc2s = ctl->bc2s; }
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const long e = i * 4;
+    int lo = 0, hi = nseg - 1;  // first segment with seg_end > e
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (seg_end[mid] > e) hi = mid; else lo = mid + 1; }
+    const float slr = lr * seg_lr_mult[lo], wd = seg_wd[lo];
+    float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i], mm = reinterpret_cast<float4*>(m)[i];
+    float P[4] = {pp.x, pp.y, pp.z, pp.w}, G[4] = {gg.x, gg.y, gg.z, gg.w}, Mo[4] = {mm.x, mm.y, mm.z, mm.w};
+    if (RULE == RMCL_OPTIM_ADAM) {
+      const float step = slr / bc1;
+      float4 vv = reinterpret_cast<float4*>(v)[i];
+      float V[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float gj = G[j] * grad_scale;
+        if (GUARDED) gj = gj * clip_coef;
+        if (wd > 0.f) gj = gj + wd * P[j];
+        Mo[j] = Mo[j] * b1 + gj * (1.0f - b1);
+        V[j] = V[j] * b2 + gj * gj * (1.0f - b2);
+        P[j] = P[j] - (step * Mo[j]) / (sqrtf(V[j]) / bc2s + eps);
+      }
+      reinterpret_cast<float4*>(v)[i] = make_float4(V[0], V[1], V[2], V[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float gj = G[j] * grad_scale;
+        if (GUARDED) gj = gj * clip_coef;
+        if (wd > 0.f) gj = gj + wd * P[j];
+        Mo[j] = Mo[j] * b1 + gj;
+        P[j] = P[j] - slr * Mo[j];
+      }
+    }
+    reinterpret_cast<float4*>(p)[i] = make_float4(P[0], P[1], P[2], P[3]);
+    reinterpret_cast<float4*>(m)[i] = make_float4(Mo[0], Mo[1], Mo[2], Mo[3]);
+    if (p_lp) {
+      uint2 pk;
+      pk.x = (uint32_t)f2bf(P[0]) | ((uint32_t)f2bf(P[1]) << 16);
+      pk.y = (uint32_t)f2bf(P[2]) | ((uint32_t)f2bf(P[3]) << 16);
+      reinterpret_cast<uint2*>(p_lp)[i] = pk;
+    }
+  }
+}
+
+// ctl NULL: the plain form, bias corrections of `step` computed here like rmcl_adamw's; ctl given: the guarded form, `step` unused
+int rmcl_optim_step(int rule, float* p, const float* g, float* m, float* v, void* p_lp, const long* seg_end, const float* seg_lr_mult,
+                    const float* seg_wd, int nseg, float lr, float b1, float b2, float eps, int step, float grad_scale,
+                    const rmcl_step_ctl* ctl, long n, hipStream_t s) {
+  RMCL_REQUIRE(rule == RMCL_OPTIM_ADAM || rule == RMCL_OPTIM_SGD, "optim_step: unknown rule");
+  RMCL_REQUIRE(n > 0 && n % 4 == 0 && nseg > 0, "optim_step: bad args (n must be a positive multiple of 4, nseg > 0)");
+  RMCL_REQUIRE(rule == RMCL_OPTIM_ADAM ? v != nullptr : v == nullptr, "optim_step: Adam needs v, SGD keeps none (v must be NULL)");
+  RMCL_REQUIRE(ctl || step >= 1, "optim_step: the plain form needs step >= 1");
+  float bc1 = 1.0f, bc2s = 1.0f;
+  if (!ctl && rule == RMCL_OPTIM_ADAM) {
+    bc1 = (float)(1.0 - pow((double)b1, (double)step));
+    bc2s = (float)sqrt(1.0 - pow((double)b2, (double)step));
+  }
+  auto kernel = rule == RMCL_OPTIM_ADAM ? (ctl ? optim_rule_kernel<RMCL_OPTIM_ADAM, true> : optim_rule_kernel<RMCL_OPTIM_ADAM, false>)
+                                        : (ctl ? optim_rule_kernel<RMCL_OPTIM_SGD, true> : optim_rule_kernel<RMCL_OPTIM_SGD, false>);
+  RMCL_LAUNCH(kernel, dim3(std::min<long>(cdiv(n / 4, 256), 4096)), dim3(256), 0, s, p, g, m, v, (bf16_t*)p_lp, seg_end, seg_lr_mult,
+              seg_wd, nseg, lr, b1, b2, eps, bc1, bc2s, ctl, n / 4, grad_scale);
   RMCL_CHECK_LAUNCH();
   return 0;
 }

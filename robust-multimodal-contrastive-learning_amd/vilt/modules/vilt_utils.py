@@ -1,6 +1,7 @@
 """Training utilities on the hot path's edge: ``set_task`` (vilt/modules/vilt_utils.py:325-329) and
 ``set_schedule`` (:331-437) = HF AdamW (beta (0.9,0.98), eps 1e-8, 4 parameter groups) + polynomial
-decay with warm-up, restated as ONE fused multi-tensor kernel over the flat parameter arena."""
+decay with warm-up, restated as ONE fused multi-tensor kernel over the flat parameter arena.  ``optim_type`` "adam" and "sgd"
+(:399-402) are the same object over another update rule: FusedAdam, FusedSGD."""
 from __future__ import annotations
 
 import ctypes as C
@@ -82,9 +83,14 @@ class FusedAdamW:
     skip_nonfinite / clip_val (config ``skip_nonfinite_steps`` / ``gradient_clip_val``, both off by default): with either set, ``step``
     is the GUARDED step - a statistics pass over the gradient arena takes the decision on the device (rmcl_step_ctl: a non-finite
     gradient drops the step, as the GradScaler of the reference's precision=16 does; clip_val > 0 scales the gradient like
-    clip_grad_norm_) and the AdamW reads it there.  No device-to-host copy, no synchronisation: ``t`` counts ATTEMPTED steps on the
+    clip_grad_norm_) and the update kernel reads it there.  No device-to-host copy, no synchronisation: ``t`` counts ATTEMPTED steps on the
     host, the applied / skipped counts live in ``ctl`` and are read by ``counters()`` / ``grad_norm()`` only.  With N > 1 every rank
-    sees the same reduced gradient, so every rank takes the same decision without a collective."""
+    sees the same reduced gradient, so every rank takes the same decision without a collective.
+
+    FusedAdam and FusedSGD below are this object with another ``rule``: they replace ``_sweep`` (the update kernel) and nothing else."""
+
+    rule = "adamw"              # recorded by state_dict(); load_state_dict() refuses another rule's state
+    has_v = True                # a second-moment arena is kept
 
     def __init__(self, pl_module, lr, wd, lr_mult, betas=(0.9, 0.98), eps=1e-8, skip_nonfinite=False, clip_val=0.0):
         eng = pl_module.engine
@@ -92,7 +98,7 @@ class FusedAdamW:
         self.module = pl_module
         self.betas, self.eps = betas, eps
         self.m = torch.zeros_like(eng.q32)
-        self.v = torch.zeros_like(eng.q32)
+        self.v = torch.zeros_like(eng.q32) if self.has_v else None
         self.t = 0
         ends, mults, wds = adamw_segments(eng.specs, eng.total, wd, lr_mult, eng.irtr)
         dev = eng.device
@@ -115,9 +121,18 @@ class FusedAdamW:
         e = self.eng
         self.module.wait_grad_sync()                       # overlapped data-parallel all-reduces (N > 1)
         if self.guarded:
-            n = I64(e.q32.numel())
-            check(lib.rmcl_grad_stats_f32(P(e.g32), n, F(self.grad_scale), F(self.clip_val), F(self.betas[0]), F(self.betas[1]),
-                                          P(self.stats_ws), P(self.ctl), stream_ptr()), "grad_stats")
+            check(lib.rmcl_grad_stats_f32(P(e.g32), I64(e.q32.numel()), F(self.grad_scale), F(self.clip_val), F(self.betas[0]),
+                                          F(self.betas[1]), P(self.stats_ws), P(self.ctl), stream_ptr()), "grad_stats")
+        self._sweep()
+        e.fold_stale["q"] = True                            # (after a skipped step too: refreshing a shadow that did not move is harmless)
+        e.lpT_stale = True
+        e.mlm_wt_stale = True
+
+    def _sweep(self):
+        """The update kernel over the arenas; guarded, it reads the decision the statistics pass just left in ``ctl``."""
+        e = self.eng
+        n = I64(e.q32.numel())
+        if self.guarded:
             check(lib.rmcl_adamw_guarded_f32(P(e.q32), P(e.g32), P(self.m), P(self.v), P(e.q_lp), P(self.seg_end), P(self.seg_mult),
                                              P(self.seg_wd), int(self.seg_end.numel()), F(self.param_groups[0]["lr"]), F(self.betas[0]),
                                              F(self.betas[1]), F(self.eps), F(self.grad_scale), P(self.ctl), n, stream_ptr()),
@@ -125,11 +140,8 @@ class FusedAdamW:
         else:
             check(lib.rmcl_adamw_f32(P(e.q32), P(e.g32), P(self.m), P(self.v), P(e.q_lp), P(self.seg_end), P(self.seg_mult),
                                      P(self.seg_wd), int(self.seg_end.numel()), F(self.param_groups[0]["lr"]), F(self.betas[0]),
-                                     F(self.betas[1]), F(self.eps), self.t, F(self.grad_scale), I64(e.q32.numel()), stream_ptr()),
+                                     F(self.betas[1]), F(self.eps), self.t, F(self.grad_scale), n, stream_ptr()),
                   "adamw")
-        e.fold_stale["q"] = True                            # (after a skipped step too: refreshing a shadow that did not move is harmless)
-        e.lpT_stale = True
-        e.mlm_wt_stale = True
 
     def read_ctl(self):
         """Host copy of the decision block (synchronises); None on an unguarded optimizer."""
@@ -150,20 +162,29 @@ class FusedAdamW:
         return float(self.read_ctl().norm)
 
     def state_dict(self):
-        """m, v, the step counts and the hyper-parameters (tensors, numbers, lists and dicts only: torch.load(weights_only=True) reads
-        it).  The segment tables follow from the model and are rebuilt, not stored."""
+        """m, v (where the rule keeps one), the step counts, the rule and the hyper-parameters (tensors, numbers, strings, lists and dicts
+        only: torch.load(weights_only=True) reads it).  The segment tables follow from the model and are rebuilt, not stored."""
         applied, skipped = self.counters()
-        return {"state": {"m": self.m.detach().cpu(), "v": self.v.detach().cpu()}, "t": int(self.t), "applied": applied, "skipped": skipped,
+        state = {"m": self.m.detach().cpu()}
+        if self.has_v:
+            state["v"] = self.v.detach().cpu()
+        return {"state": state, "rule": self.rule, "t": int(self.t), "applied": applied, "skipped": skipped,
                 "betas": [float(b) for b in self.betas], "eps": float(self.eps), "grad_scale": float(self.grad_scale),
                 "param_groups": [dict(g) for g in self.param_groups], "arena_numel": int(self.m.numel())}
 
     def load_state_dict(self, sd):
+        who = type(self).__name__
+        rule = sd.get("rule", "adamw")                     # files written before the rule was recorded are AdamW's
+        if rule != self.rule:
+            raise ValueError(f"{who}.load_state_dict: the checkpoint's optimizer state was written by optim_type={rule!r}, "
+                             f"this optimizer is optim_type={self.rule!r}")
         have, want = int(sd["state"]["m"].numel()), int(self.m.numel())
-        if have != want or int(sd["state"]["v"].numel()) != want:
-            raise ValueError(f"FusedAdamW.load_state_dict: the checkpoint's optimizer state has {have} elements, this model's parameter "
+        if have != want or (self.has_v and int(sd["state"]["v"].numel()) != want):
+            raise ValueError(f"{who}.load_state_dict: the checkpoint's optimizer state has {have} elements, this model's parameter "
                              f"arena has {want} (another architecture or head set)")
         self.m.copy_(sd["state"]["m"])
-        self.v.copy_(sd["state"]["v"])
+        if self.has_v:
+            self.v.copy_(sd["state"]["v"])
         self.t = int(sd["t"])
         self.betas, self.eps = tuple(float(b) for b in sd["betas"]), float(sd["eps"])
         self.grad_scale = float(sd["grad_scale"])
@@ -173,6 +194,40 @@ class FusedAdamW:
             self.ctl.copy_(c.to_tensor(self.ctl.device))
         else:
             self.t = int(sd["applied"])                    # the unguarded kernel's bias corrections follow t: only applied steps count
+
+
+class FusedAdam(FusedAdamW):
+    """``torch.optim.Adam(groups, lr=lr)`` (vilt_utils.py:399-400) over the arenas: betas (0.9, 0.999), eps 1e-8 added AFTER the division
+    by sqrt(1 - beta2^t), weight decay coupled into the gradient (include/rmcl.h rmcl_optim_step_f32, RMCL_OPTIM_ADAM)."""
+
+    rule = "adam"
+    code = L.OPTIM_ADAM
+
+    def __init__(self, pl_module, lr, wd, lr_mult, betas=(0.9, 0.999), eps=1e-8, skip_nonfinite=False, clip_val=0.0):
+        super().__init__(pl_module, lr, wd, lr_mult, betas=betas, eps=eps, skip_nonfinite=skip_nonfinite, clip_val=clip_val)
+
+    def _sweep(self):
+        e = self.eng
+        check(lib.rmcl_optim_step_f32(self.code, P(e.q32), P(e.g32), P(self.m), P(self.v), P(e.q_lp), P(self.seg_end), P(self.seg_mult),
+                                      P(self.seg_wd), int(self.seg_end.numel()), F(self.param_groups[0]["lr"]), F(self.betas[0]),
+                                      F(self.betas[1]), F(self.eps), self.t, F(self.grad_scale), P(self.ctl if self.guarded else None),
+                                      I64(e.q32.numel()), stream_ptr()), "optim_step")
+
+
+class FusedSGD(FusedAdam):
+    """``torch.optim.SGD(groups, lr=lr, momentum=0.9)`` (vilt_utils.py:401-402): ``m`` is the momentum buffer, there is no ``v`` arena
+    (4 bytes of state less per parameter than Adam).  ``betas`` = (momentum, 0) and ``eps`` = 0 keep the surface; the kernel reads only
+    betas[0], and the statistics pass of the guarded step writes bias corrections nobody reads."""
+
+    rule = "sgd"
+    code = L.OPTIM_SGD
+    has_v = False
+
+    def __init__(self, pl_module, lr, wd, lr_mult, momentum=0.9, skip_nonfinite=False, clip_val=0.0):
+        super().__init__(pl_module, lr, wd, lr_mult, betas=(momentum, 0.0), eps=0.0, skip_nonfinite=skip_nonfinite, clip_val=clip_val)
+
+
+OPTIMIZERS = {"adamw": FusedAdamW, "adam": FusedAdam, "sgd": FusedSGD}        # the reference's three optim_type values
 
 
 class PolySchedule:
@@ -212,10 +267,10 @@ class CosineSchedule(PolySchedule):
 
 def set_schedule(pl_module):
     cfg = pl_module.hparams.config
-    if cfg["optim_type"] != "adamw":
-        raise NotImplementedError("only optim_type='adamw' (the reference default) is built")
-    opt = FusedAdamW(pl_module, cfg["learning_rate"], cfg["weight_decay"], cfg["lr_mult"],
-                     skip_nonfinite=cfg.get("skip_nonfinite_steps", False), clip_val=cfg.get("gradient_clip_val", 0.0))
+    if cfg["optim_type"] not in OPTIMIZERS:
+        raise ValueError(f"set_schedule: optim_type={cfg['optim_type']!r} is none of {sorted(OPTIMIZERS)} (vilt_utils.py:395-402)")
+    opt = OPTIMIZERS[cfg["optim_type"]](pl_module, cfg["learning_rate"], cfg["weight_decay"], cfg["lr_mult"],
+                                        skip_nonfinite=cfg.get("skip_nonfinite_steps", False), clip_val=cfg.get("gradient_clip_val", 0.0))
     max_steps = cfg["max_steps"]
     if max_steps is None:
         # the reference derives it from the Lightning trainer's dataloader (vilt_utils.py:404-411); rmcl_amd.trainer.Trainer.fit does

@@ -7,11 +7,15 @@ that ALTERNATE four windows of ITERS calls each, timed with device events -
     guarded        rmcl_grad_stats_f32 + rmcl_adamw_guarded_f32   (what FusedAdamW.step() enqueues with the guard on)
     stats          rmcl_grad_stats_f32 alone
     guarded_adamw  rmcl_adamw_guarded_f32 alone (on the last decision)
-and reports the median and the spread of the per-call time over the rounds, the bytes each call must move (AdamW: 16 B read + 12 B
-written per element, + 2 B with the shadow; statistics: 4 B read) and the rate that gives.  `added_over_plain` is the measured
-(guarded - plain) / plain; `bytes_estimate` is 4 / (28 or 30), what the statistics pass adds by byte count.
+and, in the same rounds, the other two update rules (rmcl_optim_step_f32), each as FusedAdam / FusedSGD enqueue them -
+    adam_plain, sgd_plain        the plain form
+    adam_guarded, sgd_guarded    rmcl_grad_stats_f32 + the guarded form
+and reports the median and the spread of the per-call time over the rounds, the bytes each call must move (AdamW and Adam: 16 B read +
+12 B written per element, SGD: 12 B + 8 B, each + 2 B with the shadow; statistics: 4 B read) and the rate that gives.
+`added_over_plain` is the measured (guarded - plain) / plain; `bytes_estimate` is 4 / (28 or 30), what the statistics pass adds by byte
+count.  `vs_adamw` holds, per new arm, its time over rmcl_adamw_f32's next to the ratio of the bytes.
 
-  python tools/optim_bench.py --out profiles/guarded_step_bench.json"""
+  python tools/optim_bench.py --out profiles/optim_rules_bench.json        (profiles/guarded_step_bench.json: the first four arms, 10 rounds)"""
 import argparse
 import ctypes as C
 import json
@@ -23,7 +27,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ITERS, ROUNDS, WARMUP = 50, 10, 5
+ITERS, ROUNDS, WARMUP = 50, 20, 5
 LEG_TIMEOUT = 240
 
 
@@ -77,7 +81,21 @@ def leg(shadow: bool) -> dict:
         check(lib.rmcl_adamw_guarded_f32(P(p), P(g), P(m), P(v), P(lp), P(seg_end), P(mult), P(wd), nseg, *hyper, F(1.0), P(ctl), I64(n), s),
               "adamw_guarded")
 
-    arms = {"plain": plain, "guarded": guarded, "stats": stats, "guarded_adamw": guarded_adamw}
+    adam_hyper = (F(1e-4), F(0.9), F(0.999), F(1e-8))
+    sgd_hyper = (F(1e-4), F(0.9), F(0.0), F(0.0))
+
+    def rule(code, vv, hp, with_ctl):                       # the arenas are shared between the arms: only the time is read
+        def call():
+            t[0] += 1
+            if with_ctl:
+                check(lib.rmcl_grad_stats_f32(P(g), I64(n), F(1.0), F(1.0), hp[1], hp[2], P(ws), P(ctl), s), "grad_stats")
+            check(lib.rmcl_optim_step_f32(code, P(p), P(g), P(m), P(vv), P(lp), P(seg_end), P(mult), P(wd), nseg, *hp, t[0], F(1.0),
+                                          P(ctl if with_ctl else None), I64(n), s), "optim_step")
+        return call
+
+    arms = {"plain": plain, "guarded": guarded, "stats": stats, "guarded_adamw": guarded_adamw,
+            "adam_plain": rule(L.OPTIM_ADAM, v, adam_hyper, False), "adam_guarded": rule(L.OPTIM_ADAM, v, adam_hyper, True),
+            "sgd_plain": rule(L.OPTIM_SGD, None, sgd_hyper, False), "sgd_guarded": rule(L.OPTIM_SGD, None, sgd_hyper, True)}
     for fn in arms.values():
         for _ in range(WARMUP):
             fn()
@@ -90,11 +108,15 @@ def leg(shadow: bool) -> dict:
     assert c.skip == 0 and c.nonfinite == 0 and bool(torch.isfinite(p).all())
     adam_bytes, stat_bytes = n * (30 if shadow else 28), n * 4
     out = {"shadow": shadow, "elements": n, "segments": nseg, "iters_per_window": ITERS, "rounds": ROUNDS}
-    for k, b in (("plain", adam_bytes), ("guarded", adam_bytes + stat_bytes), ("stats", stat_bytes), ("guarded_adamw", adam_bytes)):
+    sgd_bytes = n * (22 if shadow else 20)
+    new_arms = (("adam_plain", adam_bytes), ("adam_guarded", adam_bytes + stat_bytes), ("sgd_plain", sgd_bytes), ("sgd_guarded", sgd_bytes + stat_bytes))
+    for k, b in (("plain", adam_bytes), ("guarded", adam_bytes + stat_bytes), ("stats", stat_bytes), ("guarded_adamw", adam_bytes)) + new_arms:
         med = statistics.median(ms[k])
         out[k] = {"ms_median": med, "ms_min": min(ms[k]), "ms_max": max(ms[k]), "bytes": b, "TB_per_s": b / (med * 1e-3) / 1e12}
     out["added_over_plain"] = (out["guarded"]["ms_median"] - out["plain"]["ms_median"]) / out["plain"]["ms_median"]
     out["bytes_estimate"] = stat_bytes / adam_bytes
+    out["vs_adamw"] = {k: {"time_ratio": out[k]["ms_median"] / out["plain" if k.endswith("plain") else "guarded"]["ms_median"],
+                           "bytes_ratio": b / (adam_bytes if k.endswith("plain") else adam_bytes + stat_bytes)} for k, b in new_arms}
     return out
 
 
@@ -113,7 +135,8 @@ def main():
             sys.stderr.write(r.stderr[-4000:])
             return r.returncode
         legs.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
-    rec = {"what": "rmcl_adamw_f32 against rmcl_grad_stats_f32 + rmcl_adamw_guarded_f32, ViLT-B/32 arena", "legs": legs}
+    rec = {"what": "rmcl_adamw_f32 against rmcl_grad_stats_f32 + rmcl_adamw_guarded_f32, and rmcl_optim_step_f32 (Adam, SGD) plain and "
+                   "guarded beside them, ViLT-B/32 arena", "legs": legs}
     text = json.dumps(rec, indent=1)
     print(text)
     if a.out:
