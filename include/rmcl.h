@@ -677,6 +677,55 @@ int rmcl_optim_step_f32(int rule, float* p, const float* g, float* m, float* v, 
                         const float* seg_lr_mult, const float* seg_wd, int nseg, float lr, float beta1, float beta2, float eps,
                         int step, float grad_scale, const rmcl_step_ctl* ctl, int64_t n, void* stream);
 
+/* Epoch metrics on the device (vilt/gadgets/my_metrics.py: Accuracy, VQAScore, Scalar, change_rate - each a (sum, count) pair that is
+ * divided at the end of the epoch).  `table` is double[n_slots][2], slot s = (table[2 s], table[2 s + 1]) = (sum, count).  One call adds up
+ * to RMCL_METRIC_MAX_OPS ops, carried BY VALUE in the kernel arguments (nothing is uploaded); one workgroup of 256 threads per op, the
+ * workgroups of a call run concurrently, so the slot ranges of a call's ops must not overlap.  Stream order serialises calls.
+ *
+ * A row kind reads `rows` rows and takes an optional `group` table, int32 [rows]: row r belongs to group group[r] when that lies in
+ * [0, n_groups), and is left out otherwise; without a table every row is in group 0.  Group g adds into slot `slot + g`; an op owns the
+ * slots [slot, slot + n_groups), 1 <= n_groups <= 4 (SCALAR and PAIR use `slot` alone).  n_g = rows of group g.
+ *   SCALAR        sum += scale * x,  x = ((const float*)a)[0] or `imm` when a is NULL;  count += 1                   (Scalar.update)
+ *                 optional gate b: nothing when ((const float*)b)[0] == 0 (the loss of a batch without a labelled row, which is NaN)
+ *   PAIR          sum += ((const float*)a)[0], count += ((const float*)b)[0];  nothing when that count is 0         (MLM / MPP stats[1], [2])
+ *   ROWSUM        sum += sum_{r in g} x[r * stride], count += n_g;  nothing when n_g == 0;  x = (const float*)a      (VQAScore.update)
+ *   ROWMEAN       sum += (sum_{r in g} x[r * stride]) / n_g, count += 1;  nothing when n_g == 0                      (Scalar of a split's mean loss)
+ *   MATCH         a, b int32 [rows]; over the rows of g with b[r] != ignore_index: sum += #(a[r] == b[r]), count += #rows; nothing when no
+ *                 row qualifies.  RMCL_METRIC_INVERT: sum += #(a[r] != b[r]) over ALL rows of g, ignore_index is not read
+ *                                                                                                                 (Accuracy.update, change_rate.update)
+ *   ARGMAX_MATCH  MATCH with a[r] = index of the FIRST maximum of row r of the fp32 logits a = [rows, pitch], columns 0 .. ncols - 1
+ *                 (1 <= ncols <= pitch; the pad columns are not read); one wave per row; a row of -inf gives index 0.
+ * Counts stay integers until the one addition into the table; sums are in double in a fixed order (a thread's strided partial, a butterfly
+ * over the wave, the four waves in wave order), no float or double atomics: from the same table bytes and the same inputs a call leaves the
+ * same bytes.  rows == 0 is legal and writes nothing.  Inputs are finite: a NaN among the logits or the addends is the caller's problem, as
+ * for the heads' own argmax.  Returns -1, with nothing launched and the table untouched, for: n_ops outside 1 .. 8, a NULL table or required
+ * pointer, an unknown kind or flag, n_groups outside 1 .. 4, a slot range outside [0, n_slots), rows < 0, stride < 1, ncols < 1 or
+ * ncols > pitch, or two ops of the call whose slot ranges overlap.                                                                      */
+#define RMCL_METRIC_SCALAR 0
+#define RMCL_METRIC_PAIR 1
+#define RMCL_METRIC_ROWSUM 2
+#define RMCL_METRIC_ROWMEAN 3
+#define RMCL_METRIC_MATCH 4
+#define RMCL_METRIC_ARGMAX_MATCH 5
+#define RMCL_METRIC_INVERT 1
+#define RMCL_METRIC_MAX_OPS 8
+#define RMCL_METRIC_MAX_GROUPS 4
+typedef struct {
+  int32_t kind, slot, n_groups, flags;
+  int32_t rows, stride, ncols, pitch;
+  int32_t ignore_index;
+  float scale, imm;
+  int32_t reserved;
+  const void* a;
+  const void* b;
+  const int32_t* group;
+} rmcl_metric_op;
+typedef struct {
+  int32_t n_ops, reserved;
+  rmcl_metric_op op[RMCL_METRIC_MAX_OPS];
+} rmcl_metric_ops;
+int rmcl_metrics_update(double* table, int n_slots, const rmcl_metric_ops* ops, void* stream);
+
 /* ITM + word-patch alignment (objectives.py:24-76,714-787).  cost / dsim are [B, Lt, ld] f32 with
  * ld >= Li a multiple of 4 (GEMM operand pitch); T is [B, Li, Lt] like the reference's ipot().      */
 int rmcl_gemm_batched(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int ldc, float alpha,

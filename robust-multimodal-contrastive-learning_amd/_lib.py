@@ -93,6 +93,23 @@ class StepCtl(C.Structure):
         return torch.frombuffer(bytearray(bytes(self)), dtype=torch.uint8).clone().to(device)
 
 
+METRIC_SCALAR, METRIC_PAIR, METRIC_ROWSUM, METRIC_ROWMEAN, METRIC_MATCH, METRIC_ARGMAX_MATCH = range(6)   # include/rmcl.h RMCL_METRIC_*
+METRIC_INVERT, METRIC_MAX_OPS, METRIC_MAX_GROUPS = 1, 8, 4
+
+
+class MetricOp(C.Structure):
+    """include/rmcl.h rmcl_metric_op: one addition into the epoch-metric table (a, b, group: device pointers)."""
+    _fields_ = [("kind", C.c_int32), ("slot", C.c_int32), ("n_groups", C.c_int32), ("flags", C.c_int32),
+                ("rows", C.c_int32), ("stride", C.c_int32), ("ncols", C.c_int32), ("pitch", C.c_int32),
+                ("ignore_index", C.c_int32), ("scale", C.c_float), ("imm", C.c_float), ("reserved", C.c_int32),
+                ("a", C.c_void_p), ("b", C.c_void_p), ("group", C.c_void_p)]
+
+
+class MetricOps(C.Structure):
+    """include/rmcl.h rmcl_metric_ops: the ops of one rmcl_metrics_update call, passed by value into the kernel arguments."""
+    _fields_ = [("n_ops", C.c_int32), ("reserved", C.c_int32), ("op", MetricOp * METRIC_MAX_OPS)]
+
+
 class RmclError(RuntimeError):
     pass
 
@@ -113,6 +130,7 @@ def _load():
     lib.rmcl_randaug_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rmcl_mpp_labels_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]
+    lib.rmcl_metrics_update.argtypes = [C.c_void_p, C.c_int, C.POINTER(MetricOps), C.c_void_p]
     return lib
 
 
@@ -136,6 +154,7 @@ EXPORTS = (
     "rmcl_mpp_ws_floats", "rmcl_mpp_labels", "rmcl_mpp_labels_u8", "rmcl_mpp_compact", "rmcl_mpp_forward", "rmcl_mpp_backward", "rmcl_mpp_logits",
     "rmcl_encoder_forward_mpp", "rmcl_encoder_backward_mpp", "rmcl_visual_embed_mpp",
     "rmcl_word_saliency",
+    "rmcl_metrics_update",
 )
 
 

@@ -414,6 +414,11 @@ class Engine:
         # of refusing them; every encoder pass of more than 256 tokens then carries the mode bit (stream_bit).
         self.long_sequences = bool(cfg.get("long_sequences", False)) and self.dtype == L.BF16
         self.token_cap = 512 if self.long_sequences else 256       # tokens per sequence on the bf16 path
+        # A model that went out of use is freed by the CYCLE collector only (the deferred-backward closures and the optimizer tie module,
+        # engine and pass buffers into cycles), and Python runs that collector by object counts, not by device bytes: a process that builds
+        # model after model (a test session) was seen holding 130 - 280 GB of dead arenas.  Collect before this engine allocates its own.
+        import gc
+        gc.collect()
         d0 = self.dims(1)
         self.layout = L.Layout()
         lib.rmcl_param_layout(C.byref(d0), C.byref(self.layout))

@@ -154,7 +154,15 @@ class Trainer:
             return self.test(model, test_loader if test_loader is not None else val_loader)
         return self.fit(model, train_loader, val_loader)
 
+    def _metrics(self, model):
+        """vilt_module.py:253 calls set_metrics in every model's constructor; here the trainer does, once, unless config["epoch_metrics"]
+        is false - a model stepped without a trainer launches nothing for metrics"""
+        if getattr(model, "epoch_metrics", None) is None and self.config.get("epoch_metrics", True):
+            from .vilt.modules import vilt_utils
+            vilt_utils.set_metrics(model)
+
     def _eval_loop(self, model, loader, step, end):
+        self._metrics(model)
         was_training = model.training
         model.eval()
         with torch.no_grad():
@@ -199,6 +207,7 @@ class Trainer:
             dm = self.attach_datamodule(model)
             train_loader = dm.train_dataloader()
             val_loader = dm.val_dataloader() if val_loader is None else val_loader
+        self._metrics(model)
         fast = bool(cfg.get("fast_dev_run", False))
         n_batches = len(train_loader)
         max_epochs = 1000                                    # run.py:99

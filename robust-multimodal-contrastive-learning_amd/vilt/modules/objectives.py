@@ -57,6 +57,29 @@ def _loss_view(pl_module, loss, view, op, **hooks):
     return _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
 
 
+def _em(pl_module):
+    """pl_module.epoch_metrics (vilt_utils.set_metrics): None on a model no trainer has taken - the objectives then queue nothing"""
+    return getattr(pl_module, "epoch_metrics", None)
+
+
+def _metric(pl_module, name):
+    """The epoch-metric handle `name`, or None on a module without epoch metrics / without that attribute."""
+    return getattr(pl_module, name, None) if _em(pl_module) is not None else None
+
+
+def _feed_scalars(pl_module, phase, **values):
+    """Scalar.update at the reference's call sites: `{phase}_{name}` <- value (a device scalar, or a host number as an immediate), then
+    ONE rmcl_metrics_update for everything the objective queued."""
+    em = _em(pl_module)
+    if em is None:
+        return
+    for name, v in values.items():
+        h = _metric(pl_module, f"{phase}_{name}")
+        if h is not None:
+            h.update(v)
+    em.flush()
+
+
 def _log_delta(pl_module, pb, task, phase):
     """compute_pgd's delta log (:184) of a single-image objective, from the patch-layout delta the attack left in `pb`"""
     pl_module.engine.delta_channel_norm(pb)
@@ -84,6 +107,7 @@ def compute_geometric(pl_module, batch, loss_name, k_modality=None):
     phase = "train" if pl_module.training else "val"
     pl_module.log(f"{loss_name}_attack/{phase}/num_changes", attack_words["num_changes"])
     pl_module.log(f"{loss_name}_attack/{phase}/change_rate", attack_words["change_rate"])
+    batch["txt_attack_stats"] = (attack_words["num_changes"], attack_words["change_rate"])     # (host numbers: the epoch metrics' immediates)
     return batch
 
 
@@ -194,6 +218,9 @@ def compute_itm_wpa(pl_module, batch):
     pl_module.log(f"itm/{phase}/loss", ret["itm_loss"].detach())
     pl_module.log(f"itm/{phase}/wpa_loss", ret["itm_wpa_loss"].detach())
     pl_module.log(f"itm/{phase}/accuracy", (logits.argmax(-1) == itm_labels.long()).float().mean())
+    if _em(pl_module) is not None:
+        _metric(pl_module, f"{phase}_itm_accuracy").update(logits, labels_i)
+        _feed_scalars(pl_module, phase, itm_loss=value[0].detach(), itm_wpa_loss=value[1].detach())
     return ret
 
 
@@ -241,6 +268,11 @@ def compute_mlm(pl_module, batch):
     acc[phase] += stats[1:3]
     pl_module.log(f"mlm/{phase}/loss", value.detach())
     pl_module.log(f"mlm/{phase}/accuracy", stats[1] / stats[2])
+    if _em(pl_module) is not None:
+        # (a batch without a labelled row has a NaN loss, here as in the reference; gated on the row count it leaves the epoch loss alone)
+        _metric(pl_module, f"{phase}_mlm_accuracy").update_counts(stats[1:2], stats[2:3])
+        _metric(pl_module, f"{phase}_mlm_loss").update(value.detach(), gate=stats[2:3])
+        _em(pl_module).flush()
     return ret
 
 
@@ -328,6 +360,10 @@ def compute_mpp(pl_module, batch):
     acc[phase] += stats[1:3]
     pl_module.log(f"mpp/{phase}/loss", value.detach())
     pl_module.log(f"mpp/{phase}/accuracy", stats[1] / stats[2])
+    if _em(pl_module) is not None:
+        _metric(pl_module, f"{phase}_mpp_accuracy").update_counts(stats[1:2], stats[2:3])
+        _metric(pl_module, f"{phase}_mpp_loss").update(value.detach(), gate=stats[2:3])
+        _em(pl_module).flush()
     return ret
 
 
@@ -483,6 +519,7 @@ def compute_moco_contrastive(pl_module, batch):
     ret["k"] = k.clone()
     ret["q_original"] = clean["q"]
     pl_module.log(f"moco_loss/step/{phase}", ret["moco_loss"].detach())
+    _feed_scalars(pl_module, phase, moco_loss=ret["moco_loss"].detach())
     views = (["img"] if pl_module.image_view else []) + (["txt"] if pl_module.text_view else []) + \
             (["both"] if pl_module.image_view and pl_module.text_view else [])
     for v in views:                                                         # :402-445
@@ -564,6 +601,10 @@ def compute_barlowtwins_contrastive(pl_module, batch):
     ret["k"] = zk.clone()
     ret["barlowtwins_loss"] = loss / loss_num                                   # :548
     pl_module.log(f"barlowtwins/{phase}/loss", ret["barlowtwins_loss"].detach())
+    if _em(pl_module) is not None:
+        parts = {f"barlowtwins_loss_{part}_{name}": ret[f"barlowtwins_loss_{part}_{name}"].detach()
+                 for _, name in views for part in ("invariance", "redundancy")}
+        _feed_scalars(pl_module, phase, barlowtwins_loss=ret["barlowtwins_loss"].detach(), **parts)
     for suffix, name in views:                                                  # :555-600
         pl_module.log(f"barlowtwins_dist_{phase}_L2/Pos_attacked_{suffix}", ret[f"pos_dist_attacked_{suffix}"])
         pl_module.log(f"barlowtwins_dist_{phase}_Cosine/Pos_attacked_{suffix}", ret[f"pos_cosine_attacked_{suffix}"])
@@ -595,6 +636,10 @@ def _vqa_head_loss(pl_module, pb, op, batch, task, vb_tag, tables=None):
     phase = "train" if pl_module.training else "val"
     pl_module.log(f"{task}/{phase}/loss", value.detach())
     pl_module.log(f"{task}/{phase}/score", loss2[1])
+    if _em(pl_module) is not None:
+        # VQAScore.update: rows[b][1] of rmcl_vqa_bce IS the soft target at sample b's first maximum
+        _metric(pl_module, f"{phase}_{task}_score").update(vb.rows[:, 1], pb.B, stride=2)
+        _feed_scalars(pl_module, phase, **{f"{task}_loss": value.detach()})
     return ret
 
 
@@ -659,6 +704,24 @@ def _log_split(pl_module, batch, task, nb, ref_nb=None):
                           (nb.argmax.index_select(0, ix) != ref_nb.argmax.index_select(0, ix)).float().mean())
 
 
+def _split_groups(batch, device):
+    """the group table of a validation batch for the grouped metric ops: 0 = dev, 1 = test, -1 = neither; built once per batch.  (A name
+    with both words would sit in both of the reference's lists; no table of the NLVR2 datasets has one, and dev wins here.)"""
+    names = batch.get("table_name", [])
+    return torch.tensor([0 if "dev" in n else (1 if "test" in n else -1) for n in names], dtype=torch.int32).to(device, non_blocking=True)
+
+
+def _feed_split(pl_module, task, nb, group, ref_nb=None):
+    """Validation metrics of one NLVR2 pass by split: the mean CE of the split's rows (Scalar), its accuracy, and - against `ref_nb` - the
+    rate of changed predictions; dev and test in one grouped op each."""
+    em = pl_module.epoch_metrics
+    B = int(nb.rows.shape[0])
+    em.rowmean([f"dev_{task}_loss", f"test_{task}_loss"], nb.rows, B, group=group)
+    em.match([f"dev_{task}_accuracy", f"test_{task}_accuracy"], nb.argmax, nb.labels, B, group=group)
+    if ref_nb is not None:
+        em.match([f"dev_{task}_change_rate_cross", f"test_{task}_change_rate_cross"], nb.argmax, ref_nb.argmax, B, invert=True, group=group)
+
+
 def compute_nlvr2(pl_module, batch):
     """objectives.py:1002-1060: CE(nlvr2_classifier(cat(cls(image_0, type 1), cls(image_1, type 2))), answers)."""
     eng = pl_module.engine
@@ -669,8 +732,14 @@ def compute_nlvr2(pl_module, batch):
     if pl_module.training:
         pl_module.log("nlvr2/train/loss", value.detach())
         pl_module.log("nlvr2/train/accuracy", _scalar(stats[1]) / float(npass.B))
+        if _em(pl_module) is not None:
+            _metric(pl_module, "train_nlvr2_accuracy").update_match(nb.argmax, nb.labels, npass.B)
+            _feed_scalars(pl_module, "train", nlvr2_loss=value.detach())
     else:
         _log_split(pl_module, batch, "nlvr2", nb)
+        if _em(pl_module) is not None:
+            _feed_split(pl_module, "nlvr2", nb, _split_groups(batch, eng.device))
+            pl_module.epoch_metrics.flush()
     return ret
 
 
@@ -693,12 +762,14 @@ def compute_nlvr2_attack(pl_module, batch):
     npg.labels.copy_(nb_c.labels)
     if pl_module.image_view:
         pl_module.pgd_attacker.attack_pairs(pl_module, apass, npg)            # compute_pgd (:914)
-        pl_module.log(f"nlvr2_attacked_attack/{phase}/delta", pl_module.pgd_attacker.delta_log(pl_module, apass, batch))
+        delta = pl_module.pgd_attacker.delta_log(pl_module, apass, batch)
+        pl_module.log(f"nlvr2_attacked_attack/{phase}/delta", delta)
         apass.ops = [pv.patchesT_full for pv in apass.views]                  # img + delta_{K-1} + delta_K, left by the last step
     else:
         apass.clean_operands()
     if pl_module.text_view:
         aug = compute_geometric(pl_module, copy(batch), "nlvr2_attacked")     # (:927) on the clean pair
+        text_stats = dict(zip(("nlvr2_attacked_num_changes", "nlvr2_attacked_change_rate"), aug["txt_attack_stats"]))
         apass.set_text(aug["text_ids"].to(eng.device, torch.int64), aug["text_masks"].to(eng.device, torch.int64))
     v_att, lg_att, nb_a, st_a = _nlvr2_loss(pl_module, apass, batch, "att", labels_from=nb_c, ref=nb_c)
     ret["nlvr2_attacked_logits"] = lg_att
@@ -706,9 +777,19 @@ def compute_nlvr2_attack(pl_module, batch):
     if phase == "train":
         pl_module.log("nlvr2_attacked/train/loss", v_att.detach())
         pl_module.log("nlvr2_attacked/train/accuracy", _scalar(st_a[1]) / float(npass.B))
+        if _em(pl_module) is not None:
+            _metric(pl_module, "train_nlvr2_attacked_accuracy").update_match(nb_a.argmax, nb_a.labels, npass.B)
+            views = dict(text_stats if pl_module.text_view else {}, **({"nlvr2_attacked_delta": delta} if pl_module.image_view else {}))
+            _feed_scalars(pl_module, "train", nlvr2_attacked_loss=v_att.detach(), **views)
     else:
         _log_split(pl_module, batch, "nlvr2_original", nb_c)
         _log_split(pl_module, batch, "nlvr2_attacked", nb_a, ref_nb=nb_c)
+        if _em(pl_module) is not None:
+            group = _split_groups(batch, eng.device)
+            _feed_split(pl_module, "nlvr2_original", nb_c, group)
+            if pl_module.image_view or pl_module.text_view:                  # (the wrap-up reads and resets the attacked slots under a view only)
+                _feed_split(pl_module, "nlvr2_attacked", nb_a, group, ref_nb=nb_c)
+            pl_module.epoch_metrics.flush()
     return ret
 
 
@@ -757,6 +838,7 @@ def compute_irtr(pl_module, batch):
         value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
     phase = "train" if pl_module.training else "val"
     pl_module.log(f"irtr/{phase}/irtr_loss", value.detach())
+    _feed_scalars(pl_module, phase, irtr_loss=value.detach())
     return {"irtr_loss": value, "irtr_scores": scores.view(B, R)}
 
 

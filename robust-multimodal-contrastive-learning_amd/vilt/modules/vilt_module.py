@@ -93,6 +93,7 @@ class ViLTransformerSS(nn.Module):
             eng.fold = {}
         self.current_tasks = []
         self.logged = {}
+        self.epoch_metrics = None          # the epoch-metric table (vilt_utils.set_metrics); None: the objectives queue nothing
         self._infer_busy = set()               # stash slots of differentiable infer() calls whose backward is pending
         # query parameters = views into the flat fp32 arena; .grad = views into the gradient arena
         for name, off, shape in eng.specs:
@@ -343,6 +344,8 @@ class ViLTransformerSS(nn.Module):
               "python_rng": [int(version), [int(x) for x in internal], gauss]}
         if e.q32.is_cuda:
             st["device_rng"] = torch.cuda.get_rng_state(e.q32.device)
+        if self.epoch_metrics is not None:
+            st["epoch_metrics"] = self.epoch_metrics.state_dict()
         return st
 
     def load_training_state(self, state):
@@ -355,6 +358,8 @@ class ViLTransformerSS(nn.Module):
         for name in ("mlm_epoch_counts", "mpp_epoch_counts"):
             if state.get(name):
                 setattr(self, name, {k: v.to(e.device) for k, v in state[name].items()})
+        if self.epoch_metrics is not None:
+            self.epoch_metrics.load_state_dict(state.get("epoch_metrics"))      # (a state without the key: an empty table)
         torch.set_rng_state(state["torch_rng"].cpu().to(torch.uint8))
         if "device_rng" in state and e.q32.is_cuda:
             torch.cuda.set_rng_state(state["device_rng"].cpu().to(torch.uint8), e.q32.device)

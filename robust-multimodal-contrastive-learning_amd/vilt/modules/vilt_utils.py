@@ -24,11 +24,177 @@ def set_task(pl_module):
     return
 
 
+def _views(pl_module):
+    return (bool(getattr(pl_module, "image_view", False)), bool(getattr(pl_module, "text_view", False)),
+            bool(getattr(pl_module, "augmentation", False)))
+
+
+def metric_attributes(loss_names, image_view=False, text_view=False, augmentation=False):
+    """[(attribute name, class name)] of vilt_utils.set_metrics (:13-84), in its order, under its conditions.  ``irtr_attacked`` is
+    broken upstream and not built here: it gets no attribute."""
+    out = []
+    add = lambda name, cls: out.append((name, cls))
+    for split in ("train", "val"):
+        for k, v in loss_names.items():
+            if v < 1 or k == "irtr_attacked":
+                continue
+            if k in ("vqa", "vqa_attacked"):
+                add(f"{split}_{k}_score", "VQAScore")
+                add(f"{split}_{k}_loss", "Scalar")
+            elif k == "nlvr2":
+                for s in (("train",) if split == "train" else ("dev", "test")):
+                    add(f"{s}_nlvr2_accuracy", "Accuracy")
+                    add(f"{s}_nlvr2_loss", "Scalar")
+            elif k == "nlvr2_attacked":
+                if split == "train":
+                    add(f"train_{k}_accuracy", "Accuracy")
+                    add(f"train_{k}_loss", "Scalar")
+                    if image_view:
+                        add(f"train_{k}_delta", "Scalar")
+                    if text_view:
+                        add(f"train_{k}_num_changes", "Scalar")
+                        add(f"train_{k}_change_rate", "Scalar")
+                else:
+                    for s in ("dev", "test"):
+                        for which in ("original", "attacked"):
+                            add(f"{s}_nlvr2_{which}_accuracy", "Accuracy")
+                            add(f"{s}_nlvr2_{which}_loss", "Scalar")
+                    add("test_nlvr2_attacked_change_rate_cross", "change_rate")
+                    add("dev_nlvr2_attacked_change_rate_cross", "change_rate")
+            elif k == "irtr":
+                add(f"{split}_irtr_loss", "Scalar")
+            elif k in ("mppd", "mpfr"):
+                add(f"{split}_{k}_loss", "Scalar")
+            elif k == "itm":
+                add(f"{split}_itm_accuracy", "Accuracy")
+                add(f"{split}_itm_loss", "Scalar")
+                add(f"{split}_itm_wpa_loss", "Scalar")
+            elif k in ("moco", "barlowtwins"):
+                add(f"{split}_{k}_loss", "Scalar")
+                if k == "barlowtwins":
+                    names = (["img"] if image_view else []) + (["text"] if text_view else []) + \
+                            (["both"] if image_view and text_view and not augmentation else [])
+                    for n in names:
+                        add(f"{split}_{k}_loss_invariance_{n}", "Scalar")
+                        add(f"{split}_{k}_loss_redundancy_{n}", "Scalar")
+            else:
+                add(f"{split}_{k}_accuracy", "Accuracy")
+                add(f"{split}_{k}_loss", "Scalar")
+    return out
+
+
+def set_metrics(pl_module):
+    """vilt_utils.set_metrics (:13-84): the reference's metric attributes under its names, as handles on the slots of ONE device table,
+    ``pl_module.epoch_metrics`` (vilt/gadgets/my_metrics.py).  The dev / test twins of NLVR2 get neighbouring slots: one grouped op
+    serves both splits of a validation batch."""
+    from ..gadgets import my_metrics
+    image_view, text_view, augmentation = _views(pl_module)
+    em = my_metrics.EpochMetrics(pl_module.device)
+    attrs = metric_attributes(pl_module.hparams.config["loss_names"], image_view, text_view, augmentation)
+    names = [n for n, _ in attrs]
+    for name in names:
+        if name.startswith("dev_") and "test_" + name[4:] in names:
+            em.register(name, "test_" + name[4:])
+    for name, cls in attrs:
+        setattr(pl_module, name, getattr(my_metrics, cls)(em, name))
+    pl_module.epoch_metrics = em
+    return em
+
+
+def epoch_plan(loss_names, phase, image_view=False, text_view=False, augmentation=False):
+    """What vilt_utils.epoch_wrapup (:98-311) logs for `phase`, task by task in dict order: [(task, [(key, attribute, shown, is_value)])].
+    ``attribute`` is computed and reset; the logged value is the one of ``shown`` (the reference logs the TEXT redundancy under
+    redundancy_both, :298); the LAST entry with ``is_value`` is the task's term of the_metric, 0 when there is none (IRTR)."""
+    plan = []
+    for k, v in loss_names.items():
+        if v < 1 or k == "irtr_attacked":
+            continue
+        e = []
+        add = lambda key, attr, is_value=False, shown=None: e.append((key, attr, shown or attr, is_value))
+        if k in ("vqa", "vqa_attacked"):
+            add(f"{k}/{phase}/score_epoch", f"{phase}_{k}_score", True)
+            add(f"{k}/{phase}/loss_epoch", f"{phase}_{k}_loss")
+        elif k == "nlvr2":
+            for s in (("train",) if phase == "train" else ("dev", "test")):
+                add(f"nlvr2/{s}/accuracy_epoch", f"{s}_nlvr2_accuracy", True)
+                add(f"nlvr2/{s}/loss_epoch", f"{s}_nlvr2_loss")
+        elif k == "nlvr2_attacked":
+            if phase == "train":
+                add(f"{k}/train/accuracy_epoch", f"train_{k}_accuracy", True)
+                add(f"{k}/train/loss_epoch", f"train_{k}_loss")
+                if image_view:
+                    add(f"{k}/train/img_delta_epoch", f"train_{k}_delta", True)
+                if text_view:
+                    add(f"{k}/train/txt_num_changes", f"train_{k}_num_changes", True)
+                    add(f"{k}/train/txt_change_rate", f"train_{k}_change_rate", True)
+            else:
+                for s in ("dev", "test"):
+                    add(f"nlvr2_original/{s}/accuracy_epoch", f"{s}_nlvr2_original_accuracy", True)
+                    add(f"nlvr2_original/{s}/loss_epoch", f"{s}_nlvr2_original_loss")
+                    if image_view or text_view:
+                        add(f"nlvr2_attacked/{s}/accuracy_epoch", f"{s}_nlvr2_attacked_accuracy", True)
+                        add(f"nlvr2_attacked/{s}/loss_epoch", f"{s}_nlvr2_attacked_loss")
+                        add(f"nlvr2_attacked/{s}/change_rate_cross_epoch", f"{s}_nlvr2_attacked_change_rate_cross", True)
+        elif k == "irtr":
+            add(f"irtr/{phase}/irtr_loss_epoch", f"{phase}_irtr_loss")
+        elif k in ("mppd", "mpfr"):
+            add(f"{k}/{phase}/loss_epoch", f"{phase}_{k}_loss")
+        elif k == "itm":
+            add(f"itm/{phase}/accuracy_epoch", f"{phase}_itm_accuracy", True)
+            add(f"itm/{phase}/loss_epoch", f"{phase}_itm_loss")
+            add(f"itm/{phase}/wpa_loss_epoch", f"{phase}_itm_wpa_loss")
+        elif k in ("moco", "barlowtwins"):
+            add(f"{k}_loss/epoch/{phase}", f"{phase}_{k}_loss", True)          # (the LOSS joins the_metric, under mode max)
+            if k == "barlowtwins":
+                for n in (["img"] if image_view else []) + (["text"] if text_view else []) + \
+                        (["both"] if image_view and text_view and not augmentation else []):   # (no `both` attributes under augmentation: the reference raises there)
+                    add(f"{k}_loss_invariance_{n}/epoch/{phase}", f"{phase}_{k}_loss_invariance_{n}")
+                    add(f"{k}_loss_redundancy_{n}/epoch/{phase}", f"{phase}_{k}_loss_redundancy_{n}",
+                        shown=f"{phase}_{k}_loss_redundancy_text" if n == "both" else None)
+        else:
+            add(f"{k}/{phase}/accuracy_epoch", f"{phase}_{k}_accuracy", True)
+            add(f"{k}/{phase}/loss_epoch", f"{phase}_{k}_loss")
+        plan.append((k, e))
+    return plan
+
+
+def _epoch_values(pl_module, phase, out):
+    """The epoch keys of the reference's wrap-up from ``pl_module.epoch_metrics``, appended to `out`, and ``{phase}/the_metric``.  A slot
+    that received nothing gives no key (the reference would log NaN), and the_metric is left out when a slot its sum reads is empty; a
+    ``{phase}/the_metric`` the step logs already hold wins."""
+    em = pl_module.epoch_metrics
+    image_view, text_view, augmentation = _views(pl_module)
+    em.reduce_()
+    pairs = em.pairs()
+    value_of = lambda name: (pairs[name][0] / pairs[name][1]) if name in pairs and pairs[name][1] else None
+    the_metric, complete, touched = 0.0, True, []
+    if "recalls/ir_r1" in out:
+        the_metric += out["recalls/ir_r1"] + out["recalls/tr_r1"]
+    for _task, entries in epoch_plan(pl_module.hparams.config["loss_names"], phase, image_view, text_view, augmentation):
+        value = 0.0
+        for key, attr, shown, is_value in entries:
+            v = value_of(shown)
+            if v is not None:
+                out.setdefault(key, v)
+            if attr in em.slots:
+                touched.append(em.slots[attr])
+            if is_value:
+                value = v
+        if value is None:
+            complete = False
+        else:
+            the_metric += value
+    if touched:
+        em.table[torch.tensor(sorted(set(touched)), dtype=torch.int64, device=em.table.device)] = 0.0
+    if complete:
+        out.setdefault(f"{phase}/the_metric", the_metric)
+
+
 def epoch_wrapup(pl_module):
-    """vilt_utils.epoch_wrapup (:227-323) for the tasks on this path: the reference computes and logs the epoch value of
-    every task metric and resets it.  Metrics here are the per-step values kept in ``pl_module.logged``; the wrap-up
-    returns them as ``the_metric`` inputs and clears them.  (As written, the reference's own wrap-up reads undefined
-    ``text_attack`` / ``image_attack`` attributes, :236 - not imitated.)"""
+    """vilt_utils.epoch_wrapup (:86-313): the per-step values kept in ``pl_module.logged`` pass through and are cleared, the counted
+    MLM / MPP accuracies and the recalls follow, and - when ``set_metrics`` has given the module its ``epoch_metrics`` - the reference's
+    epoch keys under its names and ``{phase}/the_metric``, its sum of the recalls and every task's value (DESIGN.md "Epoch metrics").
+    (As written, the reference's own wrap-up reads undefined ``text_attack`` / ``image_attack`` attributes, :236 - not imitated.)"""
     phase = "train" if pl_module.training else "val"
     out = {k: (float(v) if torch.is_tensor(v) and v.numel() == 1 else v) for k, v in pl_module.logged.items()}
     pl_module.logged = {}
@@ -50,6 +216,8 @@ def epoch_wrapup(pl_module):
         for name, v in zip(("ir_r1", "ir_r5", "ir_r10", "tr_r1", "tr_r5", "tr_r10"), rec):
             out[f"recalls/{name}"] = float(v)
         out["the_metric"] = out.get("the_metric", 0.0) + out["recalls/ir_r1"] + out["recalls/tr_r1"]
+    if getattr(pl_module, "epoch_metrics", None) is not None:
+        _epoch_values(pl_module, phase, out)
     pl_module.last_epoch_metrics = {"phase": phase, **out}
     return pl_module.last_epoch_metrics
 
