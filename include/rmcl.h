@@ -89,7 +89,10 @@ typedef struct rmcl_ragged {
  *   sc [layers][2][3D + mlp] f32  : s = row sums of W', c = W beta + bias
  * and must be re-run whenever that arena changes (optimizer step, momentum update, checkpoint load).  Passing the pair to
  * rmcl_encoder_forward removes the 2 LayerNorm launches per layer (the producer GEMMs emit the bf16 copy of the residual
- * stream and per-row partial sums in their epilogues); NULL keeps the separate LayerNorm kernels.                       */
+ * stream and per-row partial sums in their epilogues); NULL keeps the separate LayerNorm kernels.  The fold is taken only where
+ * all four GEMMs of a layer run on the bf16 192-row tile kernels: D % 192 == 0 and a routing that sends them there (automatic at the
+ * step's shapes, rmcl_tune_set key 0 = 60 at any).  Every other pass given the pair runs the separate LayerNorm kernels, bit for bit
+ * the pass without it: for such an encoder (D % 192 != 0) building the pair with rmcl_ln_fold is wasted work.             */
 typedef struct rmcl_fold {
   const void* wf;
   const float* sc;
@@ -769,7 +772,8 @@ int rmcl_gemm_rows_bf16(const void* A, const float* W, float* C, float* C2, cons
 int rmcl_rows_gather_f32(const void* in, int dtype, float* out, int R, int D, int64_t stride, int64_t off, void* stream);
 /* Kernel family the bf16 fast path gives a GEMM of this shape / epilogue / layout to under the current tuning: 0 = 128x128 tiles,
  * 1 = 192x192 one workgroup per CU (gemm_st.hip), 2 = 192x384 (gemm_sw.hip), 3 = 192x192x32 two workgroups per CU (gemm_dp.hip),
- * 4 / 5 = 256x256.  Lets a parity test state WHICH kernels it compared with the oracle.                                          */
+ * 4 / 5 = 256x256.  Lets a parity test state WHICH kernels it compared with the oracle.  The answer 0 holds for a GEMM the 128x128
+ * kernel can take (N % 128 == 0, K % 64 == 0, bf16 operands): rmcl_gemm runs any other such GEMM on the exact kernels.              */
 int rmcl_gemm_route(int M, int N, int K, int epi, int dt_out, int a_kc, int b_kc);
 /* rmcl_gemm with bf16 operands stored K-BLOCKED, [K/32][rows][32] (kblk bit 0: A, bit 1: B): the layout the two-workgroups-per-CU
  * kernel (csrc/gemm_dp.hip) streams as whole 128-byte lines; A [M,K] x B [N,K]^T only; fails when no kernel takes the layout  */

@@ -32,9 +32,13 @@ int rmcl_launch_gemm(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_k
   if (timed) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], stream);
   int rc;
   // (a tiled stash is the 192x384 bf16 kernel's own layout: never the exact kernels, which would read / write it row-major)
-  RMCL_REQUIRE(!(g.epi & EPI_PREACT_TILED) || (!exact && rmcl_gemm_fast_supported(g, dt_in, dt_out, a_kc, b_kc)),
+  RMCL_REQUIRE(!(g.epi & EPI_PREACT_TILED) || (!exact && rmcl_gemm_fast_takes(g, dt_in, dt_out, a_kc, b_kc)),
                "gemm: EPI_PREACT_TILED needs the bf16 192x384 kernel (bf16 in and out, exact = 0)");
-  if (!exact && rmcl_gemm_fast_supported(g, dt_in, dt_out, a_kc, b_kc)) rc = rmcl_launch_gemm_fast(g, dt_out, a_kc, b_kc, stream);
+  // (the LayerNorm-folded epilogues exist in the bf16 192-row tile kernels only: the exact kernels would drop them without a word - at
+  // N = 192 they did, before rmcl_gemm_fast_takes: the producer's bf16 copy and row partials stayed unwritten, tests/test_encoder_fp64_gpu.py case K)
+  RMCL_REQUIRE(!(g.epi & (EPI_LNFOLD | EPI_ROWSTAT)) || (!exact && rmcl_gemm_fast_takes(g, dt_in, dt_out, a_kc, b_kc)),
+               "gemm: EPI_LNFOLD / EPI_ROWSTAT need the bf16 192-row tile kernels (bf16 operands, exact = 0, a shape and routing that reach them)");
+  if (!exact && rmcl_gemm_fast_takes(g, dt_in, dt_out, a_kc, b_kc)) rc = rmcl_launch_gemm_fast(g, dt_out, a_kc, b_kc, stream);
   else rc = rmcl_launch_gemm_exact(g, dt_in, dt_out, a_kc, b_kc, stream);
   if (timed) {
     (void)hipEventRecord(g_prof.ev[2 * g_prof.n + 1], stream);

@@ -492,7 +492,8 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
     if (folded) { p1.ln_s = fold->sc; p1.ln_c = fold->sc; p1.ln_part = w.part_mid; p1.ln_nparts = nparts; p1.ln_cols = D; }
     GemmArgs p2 = gemm_args(w.dxT, c.W(c.L(0, y.fc2_w)), w.du, M, d->mlp, D, D, D, d->mlp);
     p2.epi = EPI_DGELU | EPI_PREACT_TILED | (dth ? EPI_DROP_BWD : 0); p2.aux = w.u; p2.ld_aux = d->mlp;
-    tiled = rmcl_gemm_route_code(p1, RMCL_BF16, 1, 1) == 2 && rmcl_gemm_route_code(p2, RMCL_BF16, 1, 1) == 2;
+    tiled = rmcl_gemm_fast_takes(p1, RMCL_BF16, RMCL_BF16, 1, 1) && rmcl_gemm_fast_takes(p2, RMCL_BF16, RMCL_BF16, 1, 1) &&
+            rmcl_gemm_route_code(p1, RMCL_BF16, 1, 1) == 2 && rmcl_gemm_route_code(p2, RMCL_BF16, 1, 1) == 2;
   }
   if (keep) note_stash(stash, streamed, tiled);
   const int epi_tiled = tiled ? EPI_PREACT_TILED : 0;

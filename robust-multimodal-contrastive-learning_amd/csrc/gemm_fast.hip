@@ -231,11 +231,12 @@ void rmcl_gemm_fast_set_cfg(int cfg) {
   g_gemm_cfg = cfg;
 }
 
-bool rmcl_gemm_fast_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc) {
+// n128: the 128x128 kernel itself must be able to take the GEMM (N % 128 == 0); without it, everything but that column rule
+static bool fast_base(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc, bool n128) {
   if (dt_in != RMCL_BF16) return false;
   if (g.nb1 * g.nb2 != 1) return false;                        // batched GEMMs: exact kernel
   if (!a_kc && b_kc) return false;
-  if (g.K < FBK || g.K % FBK != 0 || g.N % FBN != 0) return false;
+  if (g.K < FBK || g.K % FBK != 0 || (n128 && g.N % FBN != 0)) return false;
   if (!a_kc && g.M % FBM != 0) return false;                   // m-contiguous A is read in full 256-B rows
   if (g.lda % 8 || g.ldb % 8 || g.ldc % 4 || ((uintptr_t)g.A & 15) || ((uintptr_t)g.B & 15) || ((uintptr_t)g.C & 15)) return false;
   if (g.epi & (EPI_TANH | EPI_ATOMIC)) return false;
@@ -245,6 +246,18 @@ bool rmcl_gemm_fast_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc
   if ((g.epi & EPI_SAVE_PREACT) && ((uintptr_t)g.C2 & 15)) return false;
   if (g.splitk > 1) return false;                              // split-K goes through rmcl_launch_gemm_fast_slab
   return true;
+}
+bool rmcl_gemm_fast_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc) { return fast_base(g, dt_in, dt_out, a_kc, b_kc, true); }
+
+int rmcl_gemm_route_code(const GemmArgs& g, int dt_out, int a_kc, int b_kc);
+// What rmcl_launch_gemm gives to rmcl_launch_gemm_fast: every GEMM the 128x128 kernel could take, and a [rows][K] x [cols][K] GEMM whose N is a
+// multiple of 192 but not of 128 (N = 192, 576, 960) when the router sends it to a 192-row tile kernel.  Such a GEMM used to fall to the exact
+// kernels whatever the router said - with a folded epilogue (EPI_ROWSTAT / EPI_LNFOLD), which they do not have, dropped without a word.
+bool rmcl_gemm_fast_takes(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc) {
+  if (fast_base(g, dt_in, dt_out, a_kc, b_kc, true)) return true;
+  if (!a_kc || !b_kc || !fast_base(g, dt_in, dt_out, a_kc, b_kc, false)) return false;
+  const int r = rmcl_gemm_route_code(g, dt_out, a_kc, b_kc);
+  return r >= 1 && r <= 3;
 }
 
 template <bool A_KC, bool B_KC, bool DROP>
@@ -298,7 +311,10 @@ int rmcl_gemm_route_code(const GemmArgs& g, int dt_out, int a_kc, int b_kc) {
 // true when the GEMM runs on one of the 192-row tile kernels (the only ones that implement the LayerNorm-folded epilogues
 // EPI_LNFOLD / EPI_ROWSTAT)
 bool rmcl_gemm_routes_to_tile192(const GemmArgs& g, int a_kc, int b_kc) {
-  const int r = rmcl_gemm_route_code(g, (g.epi & EPI_ROWSTAT) ? RMCL_F32 : RMCL_BF16, a_kc, b_kc);
+  const int dt_out = (g.epi & EPI_ROWSTAT) ? RMCL_F32 : RMCL_BF16;
+  // (rmcl_launch_gemm asks rmcl_gemm_fast_takes before the router: what it turns away goes to the exact kernels, which have no folded epilogue)
+  if (!rmcl_gemm_fast_takes(g, RMCL_BF16, dt_out, a_kc, b_kc)) return false;
+  const int r = rmcl_gemm_route_code(g, dt_out, a_kc, b_kc);
   return r == 1 || r == 2 || r == 3;
 }
 

@@ -7,7 +7,8 @@
 
 int rmcl_launch_gemm_exact(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc, hipStream_t s);
 int rmcl_launch_gemm_fast(const GemmArgs& g, int dt_out, int a_kc, int b_kc, hipStream_t s);  // bf16 in
-bool rmcl_gemm_fast_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc);
+bool rmcl_gemm_fast_supported(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc);   // the 128x128 kernel can take it
+bool rmcl_gemm_fast_takes(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_kc);       // rmcl_launch_gemm gives it to the bf16 path
 int rmcl_launch_gemm_fast_slab(const GemmArgs& g, float* slab, float* out, hipStream_t s);
 int rmcl_slab_reduce(const float* slab, float* out, long n, int nz, hipStream_t s);
 int rmcl_gemm_fast_get_cfg();

@@ -128,7 +128,9 @@ def test_full_pass_producer_bits(data, M):
 def test_rowstat_producer_bits(data, M):
     for N in NS:
         for K in KS:
-            ab(lambda: run_rowstat(data, M, N, K), f"rowstat M={M} N={N} K={K}", M)
+            out, outb, part = ab(lambda: run_rowstat(data, M, N, K), f"rowstat M={M} N={N} K={K}", M)
+            # written, not the sentinels of both forms (at N = 192 the exact kernels once took the launch and dropped the producer's outputs)
+            assert torch.equal(outb[:M], out[:M].to(torch.bfloat16)) and not bool((part[:M] == 7.0).all()), (N, K)
 
 
 @pytest.mark.parametrize("M", [1, 185, 193])
