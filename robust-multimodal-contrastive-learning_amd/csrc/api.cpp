@@ -48,6 +48,18 @@ int rmcl_launch_gemm(const GemmArgs& g, int dt_in, int dt_out, int a_kc, int b_k
   return rc;
 }
 
+// Weight and bias gradient of a linear layer from a few fp32 rows (the heads, the cls-only tail): dW[Nout, Kin] += dY[rows, Nout]^T X[rows, Kin]
+// and db[Nout] += the column sums of dY - from the same launch where the short-K kernel takes the GEMM, else by a column-sum launch
+int rmcl_dw_rows(const float* dY, const float* X, float* dW, float* db, int Nout, int Kin, int rows, hipStream_t s) {
+  GemmArgs g = gemm_args(dY, X, dW, Nout, Kin, rows, Nout, Kin, Kin);
+  g.epi = EPI_ACCUM;
+  const bool cs = rmcl_gemm_tn_shortk_takes(g);
+  if (cs) { g.epi |= EPI_COLSUM; g.colsum = db; }
+  RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
+  if (!cs) RMCL_TRY(rmcl_colsum(dY, Nout, RMCL_F32, db, rows, Nout, s));
+  return 0;
+}
+
 void rmcl_gemm_fast_set_cfg(int cfg);
 
 namespace {
@@ -73,12 +85,6 @@ size_t carve_heads(const rmcl_dims& d, void* base, HeadStash* hs) {
 // plain forward on it, so a freed and re-used buffer keeps its entry until its next forward, which every legal backward follows.
 std::mutex g_nowgrad_mu;
 std::unordered_set<const void*> g_nowgrad_stash;
-GemmArgs ga(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = 1.f; g.splitk = 1; g.nb1 = 1; g.nb2 = 1;
-  return g;
-}
 }  // namespace
 
 extern "C" {
@@ -89,8 +95,7 @@ int rmcl_prof_begin(int tag_mask, int max_launches) {
   RMCL_REQUIRE(max_launches > 0 && max_launches <= (1 << 16), "prof_begin: bad max_launches");
   while (g_prof.ev.size() < (size_t)2 * max_launches) {
     hipEvent_t e;
-    hipError_t r = hipEventCreate(&e);
-    if (r != hipSuccess) { rmcl_set_error(hipGetErrorString(r)); return (int)r; }
+    HIP_TRY(hipEventCreate(&e));
     g_prof.ev.push_back(e);
   }
   g_prof.on = true; g_prof.mask = tag_mask; g_prof.n = 0; g_prof.cap = max_launches; g_prof.flops = 0.0;
@@ -100,10 +105,9 @@ int rmcl_prof_end(double* ms_total, int64_t* launches, double* flops_total) {
   g_prof.on = false;
   double ms = 0.0;
   for (size_t i = 0; i < g_prof.n; ++i) {
-    hipError_t r = hipEventSynchronize(g_prof.ev[2 * i + 1]);
     float t = 0.f;
-    if (r == hipSuccess) r = hipEventElapsedTime(&t, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]);
-    if (r != hipSuccess) { rmcl_set_error(hipGetErrorString(r)); return (int)r; }
+    HIP_TRY(hipEventSynchronize(g_prof.ev[2 * i + 1]));
+    HIP_TRY(hipEventElapsedTime(&t, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]));
     ms += t;
   }
   if (ms_total) *ms_total = ms;
@@ -184,27 +188,24 @@ int rmcl_heads_forward2(const rmcl_dims* d, const float* pool32, const float* he
   }
   if (stash_in) RMCL_TRY(rmcl_gather_rows(xn, h.cls_in, B, D, 1, N, 0, s));
   {
-    GemmArgs g = stash_in ? ga(h.cls_in, pool32 + y.pool_w, h.pooled, B, D, D, D, D, D)
-                          : ga(xn, pool32 + y.pool_w, h.pooled, B, D, D, N * D, D, D);
+    GemmArgs g = stash_in ? gemm_args(h.cls_in, pool32 + y.pool_w, h.pooled, B, D, D, D, D, D)
+                          : gemm_args(xn, pool32 + y.pool_w, h.pooled, B, D, D, N * D, D, D);
     g.epi = EPI_BIAS | EPI_TANH | EPI_DUP; g.bias = pool32 + y.pool_b; g.C2 = cls_feats;   // (cls_feats: written by the GEMM, no copy launch)
     const bool dup = rmcl_gemm_skinny_supported(g, RMCL_F32, RMCL_F32, 1);                  // (only the skinny kernels know EPI_DUP)
     if (!dup) { g.epi &= ~EPI_DUP; g.C2 = nullptr; }
     RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
-    if (!dup) {
-      hipError_t e = hipMemcpyAsync(cls_feats, h.pooled, (size_t)B * D * 4, hipMemcpyDeviceToDevice, s);
-      if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
-    }
+    if (!dup) HIP_TRY(hipMemcpyAsync(cls_feats, h.pooled, (size_t)B * D * 4, hipMemcpyDeviceToDevice, s));
   }
   if (!q) return 0;
   RMCL_REQUIRE(head32, "heads_forward: head arena is NULL");
   {
-    GemmArgs g = ga(h.pooled, head32 + y.mh0_w, h.h1, B, D, D, D, D, D);
+    GemmArgs g = gemm_args(h.pooled, head32 + y.mh0_w, h.h1, B, D, D, D, D, D);
     g.epi = EPI_BIAS; g.bias = head32 + y.mh0_b;
     RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
   }
   RMCL_TRY(rmcl_ln_fwd(h.h1, D, head32 + y.mh1_w, head32 + y.mh1_b, 1e-5f, h.h2r, D, RMCL_F32, h.mean, h.rstd, B, D, 1, s));
   {
-    GemmArgs g = ga(h.h2r, head32 + y.mh3_w, h.z, B, d->proj, D, D, D, d->proj);
+    GemmArgs g = gemm_args(h.h2r, head32 + y.mh3_w, h.z, B, d->proj, D, D, D, d->proj);
     RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
   }
   RMCL_TRY(rmcl_l2norm_fwd(h.z, h.q, h.nrm, B, d->proj, 1e-12f, s, q));
@@ -228,50 +229,34 @@ int rmcl_heads_backward(const rmcl_dims* d, const float* pool32, const float* he
   float* t0 = reinterpret_cast<float*>(workspace);
   float* t1 = t0 + (size_t)B * D;
   float* t2 = t1 + (size_t)B * D;
-  hipError_t e;
   if (dq) {
     RMCL_REQUIRE(head32, "heads_backward: head arena is NULL");
     RMCL_TRY(rmcl_l2norm_bwd(dq, h.q, h.nrm, t0, B, Pd, s));                            // dz
     if (G) {
-      GemmArgs g = ga(t0, h.h2r, G + y.mh3_w, Pd, D, B, Pd, D, D);                       // dW3 += dz^T h2r
+      GemmArgs g = gemm_args(t0, h.h2r, G + y.mh3_w, Pd, D, B, Pd, D, D);                       // dW3 += dz^T h2r
       g.epi = EPI_ACCUM;
       RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
     }
     {
-      GemmArgs g = ga(t0, head32 + y.mh3_w, t1, B, D, Pd, Pd, D, D);                     // dh2r = dz W3
+      GemmArgs g = gemm_args(t0, head32 + y.mh3_w, t1, B, D, Pd, Pd, D, D);                     // dh2r = dz W3
       RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 0, s));
     }
     RMCL_TRY(rmcl_ln_bwd(t1, D, RMCL_F32, h.h1, D, h.mean, h.rstd, head32 + y.mh1_w, head32 + y.mh1_b, t2, D, 0,
                          G ? G + y.mh1_w : nullptr, G ? G + y.mh1_b : nullptr, B, D, 1, s));   // dh1 (ReLU mask inside)
-    if (G) {
-      GemmArgs g = ga(t2, h.pooled, G + y.mh0_w, D, D, B, D, D, D);                      // dW0 += dh1^T pooled
-      g.epi = EPI_ACCUM;
-      const bool cs = rmcl_gemm_tn_shortk_takes(g);                                      // bias gradient as a by-product of the same launch
-      if (cs) { g.epi |= EPI_COLSUM; g.colsum = G + y.mh0_b; }
-      RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
-      if (!cs) RMCL_TRY(rmcl_colsum(t2, D, RMCL_F32, G + y.mh0_b, B, D, s));
-    }
+    if (G) RMCL_TRY(rmcl_dw_rows(t2, h.pooled, G + y.mh0_w, G + y.mh0_b, D, D, B, s));      // dW0 += dh1^T pooled, db0 += colsum(dh1)
     {
-      GemmArgs g = ga(t2, head32 + y.mh0_w, t0, B, D, D, D, D, D);                       // dpooled = dh1 W0
+      GemmArgs g = gemm_args(t2, head32 + y.mh0_w, t0, B, D, D, D, D, D);                       // dpooled = dh1 W0
       RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 0, s));
     }
     if (dcls_extra) RMCL_TRY(rmcl_scatter_rows(dcls_extra, t0, B, D, B, 0, 0, 1, s));    // += gradient from other heads
   } else {
     RMCL_REQUIRE(dcls_extra, "heads_backward: neither dq nor dcls_extra given");
-    e = hipMemcpyAsync(t0, dcls_extra, (size_t)B * D * 4, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+    HIP_TRY(hipMemcpyAsync(t0, dcls_extra, (size_t)B * D * 4, hipMemcpyDeviceToDevice, s));
   }
   RMCL_TRY(rmcl_tanh_bwd(t0, h.pooled, (long)B * D, s));                                  // through tanh
-  if (G) {
-    GemmArgs g = ga(t0, h.cls_in, G + y.pool_w, D, D, B, D, D, D);                        // dWp += dpre^T cls_in
-    g.epi = EPI_ACCUM;
-    const bool cs = rmcl_gemm_tn_shortk_takes(g);
-    if (cs) { g.epi |= EPI_COLSUM; g.colsum = G + y.pool_b; }
-    RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
-    if (!cs) RMCL_TRY(rmcl_colsum(t0, D, RMCL_F32, G + y.pool_b, B, D, s));
-  }
+  if (G) RMCL_TRY(rmcl_dw_rows(t0, h.cls_in, G + y.pool_w, G + y.pool_b, D, D, B, s));     // dWp += dpre^T cls_in, dbp += colsum(dpre)
   {
-    GemmArgs g = ga(t0, pool32 + y.pool_w, dcls, B, D, D, D, D, D);                       // dcls = dpre Wp
+    GemmArgs g = gemm_args(t0, pool32 + y.pool_w, dcls, B, D, D, D, D, D);                       // dcls = dpre Wp
     RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 0, s));
   }
   return 0;
@@ -311,7 +296,7 @@ int rmcl_linear_lnfold(const void* xb, const void* wf, const float* s, const flo
 int rmcl_linear_rowstat_c(const void* A, const void* W, const float* bias, const float* residual, const float* center, float* out,
                           void* out_bf16, float* part, int M, int N, int K, void* stream) {
   RMCL_REQUIRE(A && W && bias && residual && out && out_bf16 && part, "linear_rowstat: NULL argument");
-  GemmArgs g = ga(A, W, out, M, N, K, K, K, N);
+  GemmArgs g = gemm_args(A, W, out, M, N, K, K, K, N);
   g.epi = EPI_BIAS | EPI_RESIDUAL | EPI_ROWSTAT; g.bias = bias; g.aux = residual; g.ld_aux = N; g.C2 = out_bf16;
   g.ln_part = part; g.ln_nparts = 4 * (N / 192); g.ln_center = center;
   RMCL_REQUIRE(N % 192 == 0 && rmcl_gemm_routes_to_tile192(g, 1, 1), "linear_rowstat: shape does not run on the 192-row tile kernels");
@@ -320,7 +305,7 @@ int rmcl_linear_rowstat_c(const void* A, const void* W, const float* bias, const
 int rmcl_linear_lnfold_c(const void* xb, const void* wf, const float* s, const float* c, const float* part, int nparts, const float* center,
                          void* out, void* preact, int M, int N, int K, int gelu, float eps, float* mean, float* rstd, void* stream) {
   RMCL_REQUIRE(xb && wf && s && c && part && out, "linear_lnfold: NULL argument");
-  GemmArgs g = ga(xb, wf, out, M, N, K, K, K, N);
+  GemmArgs g = gemm_args(xb, wf, out, M, N, K, K, K, N);
   g.epi = EPI_LNFOLD | ((gelu & 1) ? EPI_GELU : 0) | (preact ? EPI_SAVE_PREACT : 0) | ((gelu & 2) ? EPI_PREACT_TILED : 0); g.C2 = preact;
   g.ln_s = s; g.ln_c = c; g.ln_part = const_cast<float*>(part); g.ln_nparts = nparts; g.ln_cols = K; g.ln_eps = eps;
   g.ln_mean = mean; g.ln_rstd = rstd; g.ln_center = center;
@@ -498,7 +483,7 @@ int rmcl_gemm(const void* A, const void* B, void* C, void* C2, const float* bias
 int rmcl_gemm_rows_bf16(const void* A, const float* W, float* C, float* C2, const float* bias, const float* aux, int M, int N, int K,
                         int64_t lda, int ldc, int ld_aux, int epi, void* stream) {
   RMCL_REQUIRE(A && W && C, "gemm_rows_bf16: NULL operand");
-  GemmArgs g = ga(A, W, C, M, N, K, lda, K, ldc);
+  GemmArgs g = gemm_args(A, W, C, M, N, K, lda, K, ldc);
   g.C2 = C2; g.bias = bias; g.aux = aux; g.ld_aux = ld_aux; g.epi = epi; g.a_bf16 = 1;
   return rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, (hipStream_t)stream);
 }
@@ -513,7 +498,7 @@ int rmcl_gemm_chain(const rmcl_chain_stage* st, int n, int M, uint32_t* tickets,
   a.n = n; a.ticket = tickets; a.target = 4u * epoch; a.flags = flags; a.xcc = xcc; a.stamps = (long long*)stamps; a.stamp_wg = stamp_wg;
   for (int i = 0; i < n; ++i) {
     const rmcl_chain_stage& q = st[i];
-    GemmArgs g = ga(q.A, q.W, q.out, M, q.N, q.K, q.K, q.K, q.N);
+    GemmArgs g = gemm_args(q.A, q.W, q.out, M, q.N, q.K, q.K, q.K, q.N);
     g.epi = q.epi; g.bias = q.bias; g.aux = q.residual; g.ld_aux = q.N; g.C2 = q.out2;
     g.ln_part = q.part; g.ln_nparts = (q.epi & EPI_ROWSTAT) ? 4 * (q.N / 192) : q.nparts; g.ln_center = q.center;
     g.ln_s = q.ln_s; g.ln_c = q.ln_c; g.ln_cols = q.K; g.ln_eps = q.ln_eps; g.ln_mean = q.mean; g.ln_rstd = q.rstd;

@@ -237,8 +237,7 @@ int rmcl_bt_head_forward(const rmcl_bt_head* h, const float* params, const float
     rm[2] = rv[1] + h->H2; rv[2] = rm[2] + h->H3;
   }
   float* mean1 = st.stat, *rstd1 = mean1 + h->H1, *mean2 = rstd1 + h->H1, *rstd2 = mean2 + h->H2, *mean3 = rstd2 + h->H2, *rstd3 = mean3 + h->H3;
-  hipError_t e = hipMemcpyAsync(st.x0, cls_feats, (size_t)B * h->D * 4, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+  HIP_TRY(hipMemcpyAsync(st.x0, cls_feats, (size_t)B * h->D * 4, hipMemcpyDeviceToDevice, s));
   RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.x0, params + h->w1, st.h1, B, h->H1, h->D, h->D, h->D, h->H1, 0), RMCL_F32, RMCL_F32, 1, 1, s));
   RMCL_TRY(bn_fwd(st.h1, params + h->g1, params + h->b1, st.a1, mean1, rstd1, rm[0], rv[0], momentum, B, h->H1, 1, training, s));
   RMCL_TRY(rmcl_launch_gemm_exact(head_gemm(st.a1, params + h->w2, st.h2, B, h->H2, h->H1, h->H1, h->H1, h->H2, 0), RMCL_F32, RMCL_F32, 1, 1, s));

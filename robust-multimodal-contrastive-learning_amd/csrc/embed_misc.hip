@@ -405,8 +405,7 @@ int rmcl_im2patch_sel(float* img, float* pat, const int* sel, const int* counts,
                       int to_image, hipStream_t s) {
   RMCL_REQUIRE(ps % 4 == 0 && Hh % ps == 0 && Ww % ps == 0, "im2patch_sel: image sides must be multiples of the patch size");
   if (to_image) {
-    hipError_t e = hipMemsetAsync(img, 0, (size_t)B * C * Hh * Ww * sizeof(float), s);
-    if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+    HIP_TRY(hipMemsetAsync(img, 0, (size_t)B * C * Hh * Ww * sizeof(float), s));
   }
   RMCL_LAUNCH(im2patch_sel_kernel, dim3(cdiv((long)B * n * (C * ps * ps / 4), 256)), dim3(256), 0, s, img, pat, sel, counts, sel_ld, B, n, C, Hh, Ww, ps,
               to_image);
@@ -588,8 +587,7 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(const unsigned char* __r
 int rmcl_resize_u8(const unsigned char* src, const int* src_sizes, int B, int Hs, int Ws, const int* dst_sizes, int Hd, int Wd, const int* hb,
                    const int* hk, int ksh, const int* vb, const int* vk, int ksv, unsigned char* tmp, unsigned char* dst, hipStream_t s) {
   RMCL_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && ksh > 0 && ksv > 0, "resize_u8: bad dims");
-  hipError_t e = hipMemsetAsync(dst, 0, (size_t)B * Hd * Wd * 3, s);           // (the pad region of the resized batch reads as zeros)
-  if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+  HIP_TRY(hipMemsetAsync(dst, 0, (size_t)B * Hd * Wd * 3, s));                 // (the pad region of the resized batch reads as zeros)
   RMCL_LAUNCH(resize_u8_kernel<false>, dim3(cdiv(Wd, 64), cdiv(Hs, 4), B), dim3(256), 0, s, src, tmp, src_sizes, dst_sizes, Hs, Ws, Hd, Wd, hb, hk, ksh);
   RMCL_CHECK_LAUNCH();
   RMCL_LAUNCH(resize_u8_kernel<true>, dim3(cdiv(Wd, 64), cdiv(Hd, 4), B), dim3(256), 0, s, tmp, dst, src_sizes, dst_sizes, Hs, Wd, Hd, Wd, vb, vk, ksv);

@@ -25,25 +25,24 @@ struct StashNote { const void* stash; bool stream; bool tiled; };
 StashNote g_stash_notes[64];
 int g_stash_next = 0;
 std::mutex g_stash_mu;
+// the one lookup (g_stash_mu held): the note of this stash, NULL for a stash the table does not or no longer know
+StashNote* find_note(const void* stash) {
+  for (auto& n : g_stash_notes)
+    if (n.stash == stash) return &n;
+  return nullptr;
+}
 void note_stash(const void* stash, bool stream, bool tiled) {
   std::lock_guard<std::mutex> lk(g_stash_mu);
-  for (auto& n : g_stash_notes)
-    if (n.stash == stash) { n.stream = stream; n.tiled = tiled; return; }
-  g_stash_notes[g_stash_next] = StashNote{stash, stream, tiled};
-  g_stash_next = (g_stash_next + 1) % 64;
+  StashNote* n = find_note(stash);
+  if (!n) { n = &g_stash_notes[g_stash_next]; g_stash_next = (g_stash_next + 1) % 64; }
+  *n = StashNote{stash, stream, tiled};
 }
-// 1 / 0: the forward that filled this stash wrote `u` tiled / row-major; -1: a stash this table no longer knows
-int stash_tiled(const void* stash) {
+// false: a stash this table no longer knows
+bool stash_note(const void* stash, StashNote* out) {
   std::lock_guard<std::mutex> lk(g_stash_mu);
-  for (auto& n : g_stash_notes)
-    if (n.stash == stash) return n.tiled ? 1 : 0;
-  return -1;
-}
-bool stash_disagrees(const void* stash, bool stream) {
-  std::lock_guard<std::mutex> lk(g_stash_mu);
-  for (auto& n : g_stash_notes)
-    if (n.stash == stash) return n.stream != stream;
-  return false;                                                // a stash this table no longer knows: nothing to compare
+  const StashNote* n = find_note(stash);
+  if (n) *out = *n;
+  return n != nullptr;
 }
 
 struct Bump {
@@ -197,14 +196,6 @@ int check_dims(const rmcl_dims* d) {
   return 0;
 }
 
-GemmArgs gemm_args(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = 1.0f; g.epi = 0; g.splitk = 1; g.nb1 = 1; g.nb2 = 1;
-  return g;
-}
-
 struct Ctx {
   const rmcl_dims& d;
   const float* P32;
@@ -233,10 +224,10 @@ int dw_splitk(int Mout, int Nout, int K) {
 }
 
 // dW[Nout, Kin] += dY[tokens, Nout]^T @ X[tokens, Kin]   (fp32 atomics into the gradient arena)
-int gemm_dw(const Ctx& c, const void* dY, long lddy, const void* X, long ldx, float* dW, int Nout, int Kin, int tokens, int dt_in,
-            float* slab, size_t slab_floats) {
-  GemmArgs g = gemm_args(dY, X, dW, Nout, Kin, tokens, lddy, ldx, Kin);
-  if (!c.d.exact && dt_in == RMCL_BF16 && slab) {
+int gemm_dw(const Ctx& c, const Work& w, const void* dY, const void* X, float* dW, int Nout, int Kin, int tokens) {
+  const size_t slab_floats = SLAB_FLOATS(c.d);
+  GemmArgs g = gemm_args(dY, X, dW, Nout, Kin, tokens, Nout, Kin, Kin);
+  if (!c.d.exact && c.dt == RMCL_BF16 && w.slab) {
     // bf16 MFMA path: split-K over tokens into fp32 slabs + ordered reduce (no float atomics)
     GemmArgs probe = g;
     const int cfg = rmcl_gemm_fast_get_cfg();                       // tune cfg 1..4 pins the 128x128 kernel (tests A/B the two paths)
@@ -246,21 +237,286 @@ int gemm_dw(const Ctx& c, const void* dY, long lddy, const void* X, long ldx, fl
       int sk = std::max(1, 256 / tiles);
       sk = std::min<int>(sk, std::max<size_t>(1, slab_floats / ((size_t)Nout * Kin)));
       g.splitk = sk; g.tag = GEMM_TAG_DW;
-      return rmcl_launch_gemm_st_slab(g, slab, dW, c.s);
+      return rmcl_launch_gemm_st_slab(g, w.slab, dW, c.s);
     }
-    if (rmcl_gemm_fast_supported(probe, dt_in, RMCL_F32, 0, 0)) {
+    if (rmcl_gemm_fast_supported(probe, c.dt, RMCL_F32, 0, 0)) {
       const int tiles = (Nout / 128) * (Kin / 128);
       int sk = std::max(1, std::min(8, (256 + tiles - 1) / tiles));
       sk = std::min<int>(sk, std::max<size_t>(1, slab_floats / ((size_t)Nout * Kin)));
       sk = std::min(sk, std::max(1, tokens / 64));
       g.splitk = sk; g.tag = GEMM_TAG_DW;
-      return rmcl_launch_gemm_fast_slab(g, slab, dW, c.s);
+      return rmcl_launch_gemm_fast_slab(g, w.slab, dW, c.s);
     }
   }
   g.epi = EPI_ATOMIC; g.tag = GEMM_TAG_DW;
   g.splitk = dw_splitk(Nout, Kin, tokens);
   if (g.splitk == 1) g.epi = EPI_ACCUM;
-  return gemm(c, g, dt_in, RMCL_F32, 0, 0);
+  return gemm(c, g, c.dt, RMCL_F32, 0, 0);
+}
+// The weight gradient of one linear layer Y = X W^T + b on the per-GEMM path: dW += dY^T X and db += the column sums of dY, both on c's stream
+int linear_dw(const Ctx& c, const Work& w, const void* dY, const void* X, float* dW, float* db, int Nout, int Kin, int tokens) {
+  RMCL_TRY(gemm_dw(c, w, dY, X, dW, Nout, Kin, tokens));
+  return rmcl_colsum(dY, Nout, c.dt, db, tokens, Nout, c.s);
+}
+
+// The dropout of one pass: threshold p * 2^32 (0: off), 1 / (1 - p) and the pass seed every site's seed derives from.  A mask is a pure function
+// of (site seed, element index) (rmcl_common.h), so the backward builds the same value and regenerates the forward's masks.
+struct Dropout {
+  uint32_t seed, thresh;
+  float inv_keep;
+  uint32_t site(int layer, int site_id) const { return rmcl_site_seed(seed, layer, site_id); }
+  void set(GemmArgs& g, int epi_bit, int layer, int site_id, int row_mul) const {
+    if (thresh) { g.epi |= epi_bit; g.drop_seed = site(layer, site_id); g.drop_thresh = thresh; g.drop_inv_keep = inv_keep; g.drop_row_mul = row_mul; }
+  }
+  // a forward GEMM site.  row_mul: compact row r of the cls-only tail draws the mask of the dense row r * row_mul (gemm.h drop_row_mul)
+  void fwd(GemmArgs& g, int layer, int site_id, int row_mul = 1) const { set(g, EPI_DROPOUT, layer, site_id, row_mul); }
+  // fc2-dX: the gradient of the hidden activation takes that activation's forward mask
+  void bwd(GemmArgs& g, int layer, int row_mul = 0) const { set(g, EPI_DROP_BWD, layer, DROP_SITE_HIDDEN, row_mul); }
+};
+int make_dropout(uint32_t seed, float p, bool forward, Dropout* out) {
+  if (forward) { RMCL_REQUIRE(p >= 0.f && p < 1.f, "encoder_forward: dropout probability must be in [0,1)"); }
+  else { RMCL_REQUIRE(p >= 0.f && p < 1.f, "encoder_backward: dropout probability must be in [0,1)"); }
+  *out = Dropout{seed, p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u, 1.0f / (1.0f - p)};
+  return 0;
+}
+
+// ---- the routed GEMM sites of a pass.  ONE builder per site knows its operands, leading dimensions, epilogue bits, ln_* fields and tag, for a
+// layer and the pass's switches.  The launch calls it, and so do the routing decisions of the pass (folded, tiled) for layer 0: what a decision
+// asked about a GEMM and what the launch then does with it cannot drift apart. ----
+
+// the buffers of one layer in a forward pass: its stash slots, or the workspace where the pass keeps none; x_in is the block's input
+struct FwdLayer : LayerStash {
+  float* x_out;
+  const float* m2_prev;   // LayerNorm 2's row means of the previous layer = the centre the previous fc2 used for this layer's LayerNorm-1 operand
+};
+
+struct FwdPass {
+  const Ctx& c;
+  const Work& w;
+  const Stash& st;
+  const rmcl_fold* fold;
+  int M, D, mlp;
+  bool keep, full;              // the pass keeps a stash (DATA, FULL) / also the LayerNorm outputs and h (FULL)
+  bool folded, centred, tiled;  // LayerNorm fold, its shift-robust form, tiled pre-activation stash (encoder_forward_impl decides them)
+  // A routing decision asks how layer 0's GEMMs WOULD route, on the workspace buffers of a pass without a stash (keep = full = false), in the
+  // forms layer 0 may never launch itself: qkv folded (layer 0's own qkv reads the embedding through the LayerNorm kernel), fc1 keeping its
+  // pre-activation (C2 = w.u, non-NULL: the 192x192 kernel's rule reads it) and fc2 as a producer even in a one-layer encoder.
+  bool probe;
+  Dropout drop;
+  FwdPass as_probe(bool folded_, bool tiled_) const {
+    FwdPass q = *this;
+    q.keep = q.full = false; q.probe = true; q.folded = folded_; q.tiled = tiled_;
+    return q;
+  }
+
+  int fold_rows() const { return 3 * D + mlp; }
+  int nparts() const { return 4 * (D / 192); }
+  const bf16_t* fold_w(int l, int row) const { return (const bf16_t*)fold->wf + ((long)l * fold_rows() + row) * D; }
+  const float* fold_s(int l, int row) const { return fold->sc + (long)l * 2 * fold_rows() + row; }        // s[0..rows), c[rows..2 rows)
+
+  FwdLayer layer(int l, float* x) const {
+    void* wu = probe ? w.u : nullptr;
+    // (LayerStash in the order of its members: x_in, x_mid, mean1, rstd1, mean2, rstd2, qkv, probs, u, ao, u_t, ln1, ln2, h)
+    const LayerStash ws{x, w.x_mid, w.stat, w.stat + M, w.stat + 2 * M, w.stat + 3 * M, w.qkv, w.probs, wu, w.ao, wu, w.ln, w.ln, w.h};
+    FwdLayer b{keep ? st.layer[l] : ws, nullptr, nullptr};
+    if (!full) { b.ln1 = b.ln2 = w.ln; b.h = w.h; }        // (DATA: the stash has no slots for them)
+    b.x_out = keep ? (l + 1 < c.d.layers ? st.layer[l + 1].x_in : st.x_final) : (x == w.x_a ? w.x_b : w.x_a);
+    b.m2_prev = l > 0 ? (keep ? st.layer[l - 1].mean2 : w.stat + 2 * M) : nullptr;
+    return b;
+  }
+  // consumer side of the fold: column vectors of W' rows [row, row + N), row statistics from `part`, written to mean / rstd in every mode (the next
+  // producer centres on them).  The partials (and the bf16 operand) were taken about `centre`, the row mean of the row's previous LayerNorm.
+  void lnfold(GemmArgs& g, int l, int row, float* part, float* mean, float* rstd, const float* centre) const {
+    g.ln_s = fold_s(l, row); g.ln_c = fold_s(l, row) + fold_rows(); g.ln_part = part; g.ln_nparts = nparts(); g.ln_cols = D; g.ln_eps = 1e-6f;
+    g.ln_mean = mean; g.ln_rstd = rstd; g.ln_center = centred ? centre : nullptr;
+  }
+  // producer side: the bf16 copy of the output (x - centre) and its per-row partial sums for the next consumer
+  void rowstat(GemmArgs& g, void* xb, float* part, const float* centre) const {
+    g.epi |= EPI_ROWSTAT; g.C2 = xb; g.ln_part = part; g.ln_nparts = nparts(); g.ln_center = centred ? centre : nullptr;
+  }
+
+  GemmArgs qkv(int l, const FwdLayer& b) const {
+    if (folded && (l > 0 || probe)) {
+      // qkv = LN1(x) Wqkv^T + b: A = the bf16 copy of x the previous fc2 epilogue wrote, row statistics from its partial sums
+      GemmArgs g = gemm_args(w.xb_in, fold_w(l, 0), b.qkv, M, 3 * D, D, D, D, 3 * D);
+      g.epi = EPI_LNFOLD; g.tag = GEMM_TAG_QKV;
+      lnfold(g, l, 0, w.part_in, b.mean1, b.rstd1, b.m2_prev);
+      return g;
+    }
+    GemmArgs g = gemm_args(b.ln1, c.W(c.L(l, c.lay.qkv_w)), b.qkv, M, 3 * D, D, D, D, 3 * D);
+    g.epi = EPI_BIAS; g.bias = c.V(c.L(l, c.lay.qkv_b)); g.tag = GEMM_TAG_QKV;
+    return g;
+  }
+  GemmArgs proj(int l, const FwdLayer& b) const {
+    GemmArgs g = gemm_args(b.ao, c.W(c.L(l, c.lay.proj_w)), b.x_mid, M, D, D, D, D, D);
+    g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, c.lay.proj_b)); g.aux = b.x_in; g.ld_aux = D; g.tag = GEMM_TAG_PROJ;
+    if (folded) rowstat(g, w.xb_mid, w.part_mid, b.mean1);
+    drop.fwd(g, l, DROP_SITE_PROJ);
+    return g;
+  }
+  GemmArgs fc1(int l, const FwdLayer& b) const {
+    void* u = tiled ? b.u_t : b.u;                          // (NULL: a pass without a stash keeps no pre-activation)
+    GemmArgs g = folded ? gemm_args(w.xb_mid, fold_w(l, 3 * D), b.h, M, mlp, D, D, D, mlp)
+                        : gemm_args(b.ln2, c.W(c.L(l, c.lay.fc1_w)), b.h, M, mlp, D, D, D, mlp);
+    g.epi = (folded ? EPI_LNFOLD : EPI_BIAS) | EPI_GELU | (u ? EPI_SAVE_PREACT | (tiled ? EPI_PREACT_TILED : 0) : 0); g.C2 = u; g.tag = GEMM_TAG_FC1;
+    if (folded) lnfold(g, l, 3 * D, w.part_mid, b.mean2, b.rstd2, b.mean1);
+    else g.bias = c.V(c.L(l, c.lay.fc1_b));
+    drop.fwd(g, l, DROP_SITE_HIDDEN);
+    return g;
+  }
+  GemmArgs fc2(int l, const FwdLayer& b) const {
+    GemmArgs g = gemm_args(b.h, c.W(c.L(l, c.lay.fc2_w)), b.x_out, M, D, mlp, mlp, mlp, D);
+    g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, c.lay.fc2_b)); g.aux = b.x_mid; g.ld_aux = D; g.tag = GEMM_TAG_FC2;
+    if (folded && (l + 1 < c.d.layers || probe)) rowstat(g, w.xb_in, w.part_in, b.mean2);
+    drop.fwd(g, l, DROP_SITE_FC2);
+    return g;
+  }
+};
+
+// the four data-gradient GEMMs of a layer, dX = dY W.  The caller names the buffers: the chain rotates them (encoder_backward_impl)
+struct BwdSites {
+  const Ctx& c;
+  int M;
+  const void* lpT;     // transposed bf16 weight shadows: dX = dY W as [rows][K] x [cols][K] (W^T stored [in][out], k = out contiguous); NULL: W as it is
+  bool u_tiled;        // the `u` slots hold the tiled form (gemm.h EPI_PREACT_TILED)
+  Dropout drop;
+  int b_kc() const { return lpT ? 1 : 0; }
+  GemmArgs dx(const void* dY, int64_t w_off, void* dX, int n_in, int n_out) const {
+    const void* W = lpT ? (const void*)((const bf16_t*)lpT + w_off) : c.W(w_off);
+    GemmArgs g = gemm_args(dY, W, dX, M, n_in, n_out, n_out, lpT ? n_out : n_in, n_in);
+    g.tag = GEMM_TAG_DX;
+    return g;
+  }
+  // du = (dx W2) * gelu'(u) [* hidden mask]
+  // (tiled stash: the launch fails with a message when the GEMM no longer routes to the 192x384 kernel - never a row-major read)
+  GemmArgs fc2(int l, const void* dY, const void* u, void* du) const {
+    GemmArgs g = dx(dY, c.L(l, c.lay.fc2_w), du, c.d.mlp, c.d.D);
+    g.epi = EPI_DGELU | (u_tiled ? EPI_PREACT_TILED : 0); g.aux = u; g.ld_aux = c.d.mlp;
+    drop.bwd(g, l);
+    return g;
+  }
+  GemmArgs fc1(int l, const void* du, void* dln) const { return dx(du, c.L(l, c.lay.fc1_w), dln, c.d.D, c.d.mlp); }          // dln2 = du W1
+  GemmArgs proj(int l, const void* dY, void* dao) const { return dx(dY, c.L(l, c.lay.proj_w), dao, c.d.D, c.d.D); }          // dao = dx Wproj
+  GemmArgs qkv(int l, const void* dqkv, void* dln) const { return dx(dqkv, c.L(l, c.lay.qkv_w), dln, c.d.D, 3 * c.d.D); }    // dln1 = dqkv Wqkv
+};
+
+// The pixel path's patch rows w.pe: patch GEMM, mask-token substitution, per-sample position rows (encoder forward and rmcl_visual_embed)
+int patch_embed(const Ctx& c, const Work& w, const void* patches, const int32_t* replaced, int64_t mask_token_off, const rmcl_ragged* ragged) {
+  const rmcl_dims& d = c.d;
+  const rmcl_layout& y = c.lay;
+  GemmArgs g = gemm_args(patches, c.W(y.patch_w), w.pe, d.B * d.P, d.D, d.patch_k, d.patch_k, d.patch_k, d.D);
+  g.epi = EPI_BIAS; g.bias = c.V(y.patch_b); g.tag = GEMM_TAG_PATCH;
+  RMCL_TRY(gemm(c, g, c.dt, RMCL_F32, 1, 1));
+  // masked patch prediction: the learned mask token takes the place of the replaced patches' embeddings (rmcl_encoder_forward_mpp)
+  if (replaced) RMCL_TRY(rmcl_mask_token_fwd(w.pe, replaced, c.V(mask_token_off), d.B * d.P, d.D, c.s));
+  if (ragged) {
+    // zero-padded batch: per-sample position rows = the table resized to each image's (h, w), gathered at its selected
+    // patches (vision_transformer.py:570-600, 645-650); recomputed every pass from the arena of THIS pass (query or momentum)
+    RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, d.B, d.P, d.D,
+                                 ragged->pos_tok, c.s));
+  }
+  return 0;
+}
+
+// cls-only tail of a forward pass (RMCL_MODE_CLS_TAIL), the last block behind its attention: of that block's output only row 0 of every
+// sample is read (the pooler takes hidden_states[:, 0], heads.py:17), and everything behind the attention is row-wise - proj, LayerNorm 2,
+// the MLP and the final LayerNorm run on the B cls rows (fp32, exact skinny GEMMs) instead of on all B * N tokens.  Compact results live in
+// the FIRST B rows of the buffers the dense path would have filled (x_mid, u, h, ln2, x_final, the LN statistics) - the backward with
+// cls_only = 2 reads them there.  Dropout: compact row b draws the mask of the dense row b * N it stands for (gemm.h drop_row_mul), so the
+// tail gives the dense block's numbers under dropout too.
+int forward_tail(const FwdPass& p, int l, const FwdLayer& b, float* xn) {
+  const Ctx& c = p.c;
+  const Work& w = p.w;
+  const rmcl_layout& y = c.lay;
+  const int B = c.d.B, N = c.d.L + 1 + c.d.P, D = c.d.D, mlp = c.d.mlp;
+  hipStream_t s = c.s;
+  float* ao_c = reinterpret_cast<float*>(w.dao);          // backward scratch, free during a forward
+  float* ln2_c = reinterpret_cast<float*>(b.ln2);
+  float* u_c = reinterpret_cast<float*>(p.keep ? b.u : w.u);              // (always the row-major slot: the compact fp32 u_c is no tiled GEMM stash)
+  float* h_c = reinterpret_cast<float*>(b.h);
+  float* xo_c = b.x_out;                                   // (a pass with a stash: x_final, this is the last layer)
+  {
+    // residual operand: the cls rows of the dense residual stream, read in place (row b at b * N * D: no gather launch).  The A
+    // operand likewise where the streaming skinny kernel runs the GEMM: the cls rows of the attention output at row stride
+    // N * D, bf16 widened in its registers - the bits of the gather-and-cast launch, which only the other forms still need
+    GemmArgs g = gemm_args(b.ao, c.V(c.L(l, y.proj_w)), b.x_mid, B, D, D, (long)N * D, D, D);
+    g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, y.proj_b)); g.aux = b.x_in; g.ld_aux = N * D;
+    g.a_bf16 = c.dt == RMCL_BF16;
+    p.drop.fwd(g, l, DROP_SITE_PROJ, N);
+    if (!rmcl_gemm_skinny_streams(g, 1)) {
+      RMCL_TRY(rmcl_rows_gather_cast(b.ao, c.dt, ao_c, B, D, N, 0, s));
+      g.A = ao_c; g.lda = D; g.a_bf16 = 0;
+    }
+    RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
+  }
+  RMCL_TRY(rmcl_ln_fwd(b.x_mid, D, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), 1e-6f, ln2_c, D, RMCL_F32, b.mean2, b.rstd2, B, D, 0, s));
+  {
+    GemmArgs g = gemm_args(ln2_c, c.V(c.L(l, y.fc1_w)), h_c, B, mlp, D, D, D, mlp);
+    g.epi = EPI_BIAS | EPI_GELU | EPI_SAVE_PREACT; g.bias = c.V(c.L(l, y.fc1_b)); g.C2 = u_c;
+    p.drop.fwd(g, l, DROP_SITE_HIDDEN, N);
+    RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
+  }
+  {
+    GemmArgs g = gemm_args(h_c, c.V(c.L(l, y.fc2_w)), xo_c, B, D, mlp, mlp, mlp, D);
+    g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, y.fc2_b)); g.aux = b.x_mid; g.ld_aux = D;
+    p.drop.fwd(g, l, DROP_SITE_FC2, N);
+    RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
+  }
+  // final LayerNorm of the cls rows, written to their places in xn (row b * N); the other rows of xn are NOT written
+  return rmcl_ln_fwd(xo_c, D, c.V(y.norm_w), c.V(y.norm_b), 1e-6f, xn, (long)N * D, RMCL_F32, p.keep ? p.st.meanF : w.stat,
+                     p.keep ? p.st.rstdF : w.stat + p.M, B, D, 0, s);
+}
+
+// cls-only tail of a backward pass (cls_only = 2), the last layer behind its attention on the cls rows only: MLP, LayerNorm 2 and proj
+// backward on [B, .] fp32 (exact skinny GEMMs); weight / bias gradients of fc2, fc1, proj (G != NULL: FULL mode) reduce over B rows
+// instead of B * N; then the two row sets the dense chain continues from are rebuilt: the residual-stream gradient w.dx and d(attention
+// output) w.dao, zero except on the cls rows.  dxc: the gradient of the B cls rows [B, D] f32, updated in place.
+int backward_tail(const Ctx& c, const Work& w, const LayerStash& ls, int l, float* G, const Dropout& drop, float* dxc) {
+  const rmcl_layout& y = c.lay;
+  const int B = c.d.B, N = c.d.L + 1 + c.d.P, D = c.d.D, mlp = c.d.mlp, M = B * N;
+  hipStream_t s = c.s;
+  auto Gp = [&](int64_t rel) { return G + c.L(l, rel); };
+  float* u_c = reinterpret_cast<float*>(ls.u);
+  float* h_c = reinterpret_cast<float*>(ls.h);
+  float* ln2_c = reinterpret_cast<float*>(ls.ln2);
+  float* du_c = reinterpret_cast<float*>(w.du);
+  float* dln_c = w.dln;
+  float* ao_c = reinterpret_cast<float*>(w.dqkv2);
+  float* dao_c = reinterpret_cast<float*>(w.du2);
+  // dropout: the gradient entering fc2 / proj is the residual-stream gradient times the mask of that branch's output - the mask of
+  // the DENSE cls row b * N (forward: drop_row_mul = N); dxc itself keeps flowing down the residual path unmasked
+  const float* dy2 = dxc;                                 // d(fc2 output)
+  if (drop.thresh) {
+    float* m2 = reinterpret_cast<float*>(w.dS);           // (attention-backward scratch: free until the attention backward that follows the tail)
+    RMCL_TRY(rmcl_dropout_rows(dxc, m2, B, D, N, drop.site(l, DROP_SITE_FC2), drop.thresh, drop.inv_keep, s));
+    dy2 = m2;
+  }
+  {
+    GemmArgs g = gemm_args(dy2, c.V(c.L(l, y.fc2_w)), du_c, B, mlp, D, D, mlp, mlp);                  // du = (dx W2) * gelu'(u) [* hidden mask]
+    g.epi = EPI_DGELU; g.aux = u_c; g.ld_aux = mlp;
+    drop.bwd(g, l, N);
+    RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 0, s));
+  }
+  if (G) RMCL_TRY(rmcl_dw_rows(dy2, h_c, Gp(y.fc2_w), Gp(y.fc2_b), D, mlp, B, s));                    // dW2 += dx^T h
+  RMCL_TRY(rmcl_launch_gemm_exact(gemm_args(du_c, c.V(c.L(l, y.fc1_w)), dln_c, B, D, mlp, mlp, D, D), RMCL_F32, RMCL_F32, 1, 0, s));   // dln2 = du W1
+  if (G) RMCL_TRY(rmcl_dw_rows(du_c, ln2_c, Gp(y.fc1_w), Gp(y.fc1_b), mlp, D, B, s));                 // dW1 += du^T ln2
+  RMCL_TRY(rmcl_ln_bwd(dln_c, D, RMCL_F32, ls.x_mid, D, ls.mean2, ls.rstd2, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), dxc, D, 1,
+                       G ? Gp(y.ln2_w) : nullptr, G ? Gp(y.ln2_b) : nullptr, B, D, 0, s));   // dxc = d x_mid
+  const float* dyp = dxc;                                 // d(proj output)
+  if (drop.thresh) {
+    float* mp = reinterpret_cast<float*>(w.dS) + (size_t)B * D;
+    RMCL_TRY(rmcl_dropout_rows(dxc, mp, B, D, N, drop.site(l, DROP_SITE_PROJ), drop.thresh, drop.inv_keep, s));
+    dyp = mp;
+  }
+  RMCL_TRY(rmcl_launch_gemm_exact(gemm_args(dyp, c.V(c.L(l, y.proj_w)), dao_c, B, D, D, D, D, D), RMCL_F32, RMCL_F32, 1, 0, s));       // dao = dx Wproj
+  if (G) {
+    RMCL_TRY(rmcl_rows_gather_cast(ls.ao, c.dt, ao_c, B, D, N, 0, s));
+    RMCL_TRY(rmcl_dw_rows(dyp, ao_c, Gp(y.proj_w), Gp(y.proj_b), D, D, B, s));                        // dWproj += dx^T ao
+  }
+  HIP_TRY(hipMemsetAsync(w.dx, 0, (size_t)M * D * sizeof(float), s));
+  RMCL_TRY(rmcl_scatter_rows(dxc, w.dx, B, D, 1, N, 0, 0, s));
+  HIP_TRY(hipMemsetAsync(w.dao, 0, (size_t)M * D * esz(c.dt), s));
+  return rmcl_rows_scatter_cast(dao_c, w.dao, c.dt, B, D, N, 0, s);
 }
 
 // ---- side stream for the weight-gradient GEMMs (fills the tile-quantisation tails of the dX chain) ----
@@ -268,14 +524,18 @@ hipStream_t g_side = nullptr;
 hipEvent_t g_ev[128];
 int g_nev = 0;
 int ensure_events() {
-  while (g_nev < 128) {
-    hipError_t e = hipEventCreateWithFlags(&g_ev[g_nev], hipEventDisableTiming);
-    if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
-    ++g_nev;
-  }
+  for (; g_nev < 128; ++g_nev) HIP_TRY(hipEventCreateWithFlags(&g_ev[g_nev], hipEventDisableTiming));
   return 0;
 }
-#define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { rmcl_set_error(hipGetErrorString(_e)); return (int)_e; } } while (0)
+// The events of a weight-gradient backward, one slot per (kind, layer); the ONE place the slot arithmetic lives (encoder_backward_impl
+// records and waits, rmcl_grad_ready_wait waits).  EV_FORK is indexed by sub-layer (2 l: MLP, 2 l + 1: attention), the others by layer.
+enum EvKind {
+  EV_FORK = 0,        // main -> side: the dY of a sub-layer's weight gradients is final
+  EV_MLP_DONE = 1,    // side: the MLP weight gradients of a layer are done (its du and dx copy may be rewritten)
+  EV_SIDE_DONE = 2,   // side: all weight gradients of a layer are done (attention half on the per-GEMM path; the grouped launch)
+  EV_MAIN_DONE = 3,   // main: everything of a layer that runs on the main stream is enqueued
+};
+hipEvent_t ev_slot(EvKind kind, int idx) { return g_ev[(kind * 32 + (idx & 31)) & 127]; }
 
 }  // namespace
 
@@ -299,9 +559,15 @@ static bool g_grad_side = false;   // the weight gradients of that backward ran 
 extern "C" int rmcl_grad_ready_wait(int layer, void* stream) {
   RMCL_REQUIRE(g_grad_layers > 0, "grad_ready_wait: no weight-gradient backward has been enqueued");
   RMCL_REQUIRE(layer >= 0 && layer < g_grad_layers && layer < 32, "grad_ready_wait: bad layer");
-  HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, g_ev[(3 * 32 + layer) & 127], 0));                 // dX chain + LayerNorm grads
-  if (g_grad_side) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, g_ev[(2 * 32 + layer) & 127], 0));  // weight-gradient GEMMs
+  HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, ev_slot(EV_MAIN_DONE, layer), 0));                 // dX chain + LayerNorm grads
+  if (g_grad_side) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, ev_slot(EV_SIDE_DONE, layer), 0));  // weight-gradient GEMMs
   return 0;
+}
+
+// one GEMM per (sample, head): element strides of A, B and C per sample (1) and per head (2)
+static void per_head(GemmArgs& g, int B, int H, long sA1, long sA2, long sB1, long sB2, long sC1, long sC2) {
+  g.nb1 = B; g.nb2 = H;
+  g.sA1 = sA1; g.sA2 = sA2; g.sB1 = sB1; g.sB2 = sB2; g.sC1 = sC1; g.sC2 = sC2;
 }
 
 int rmcl_attention_fwd_impl(const void* qkv, const int* mask, void* out, void* probs, float* scores, int B, int N, int H, int dt,
@@ -314,16 +580,12 @@ int rmcl_attention_fwd_impl(const void* qkv, const int* mask, void* out, void* p
   // S = 0.125 * Q K^T   (batched over (b,h); Q/K rows are 3D apart, heads 64 apart)
   GemmArgs g = gemm_args(qkv, (const char*)qkv + (size_t)D * e, scores, N, N, 64, 3 * D, 3 * D, ldp);
   g.alpha = 0.125f;
-  g.nb1 = B; g.nb2 = H;
-  g.sA1 = (long)N * 3 * D; g.sA2 = 64; g.sB1 = g.sA1; g.sB2 = 64;
-  g.sC1 = (long)H * N * ldp; g.sC2 = (long)N * ldp;
+  per_head(g, B, H, (long)N * 3 * D, 64, (long)N * 3 * D, 64, (long)H * N * ldp, (long)N * ldp);
   RMCL_TRY(rmcl_launch_gemm(g, dt, RMCL_F32, 1, 1, exact, s));
   RMCL_TRY(rmcl_softmax_fwd(scores, ldp, mask, probs, ldp, dt, B * H, N, H, s));
   // out[b*N+i, h*64+d] = sum_j P[b,h,i,j] V[b*N+j, 2D + h*64 + d]
   GemmArgs o = gemm_args(probs, (const char*)qkv + (size_t)2 * D * e, out, N, 64, N, ldp, 3 * D, D);
-  o.nb1 = B; o.nb2 = H;
-  o.sA1 = (long)H * N * ldp; o.sA2 = (long)N * ldp; o.sB1 = (long)N * 3 * D; o.sB2 = 64;
-  o.sC1 = (long)N * D; o.sC2 = 64;
+  per_head(o, B, H, (long)H * N * ldp, (long)N * ldp, (long)N * 3 * D, 64, (long)N * D, 64);
   RMCL_TRY(rmcl_launch_gemm(o, dt, dt, 1, 0, exact, s));
   return 0;
 }
@@ -340,24 +602,20 @@ int rmcl_attention_bwd_impl(const void* qkv, const int* mask, const void* probs,
   const long sQ1 = (long)N * 3 * D, sP1 = (long)H * N * ldp, sP2 = (long)N * ldp;
   // dP = dO V^T
   GemmArgs g = gemm_args(dout, (const char*)qkv + (size_t)2 * D * e, scores, N, N, 64, D, 3 * D, ldp);
-  g.nb1 = B; g.nb2 = H;
-  g.sA1 = (long)N * D; g.sA2 = 64; g.sB1 = sQ1; g.sB2 = 64; g.sC1 = sP1; g.sC2 = sP2;
+  per_head(g, B, H, (long)N * D, 64, sQ1, 64, sP1, sP2);
   RMCL_TRY(rmcl_launch_gemm(g, dt, RMCL_F32, 1, 1, exact, s));
   RMCL_TRY(rmcl_softmax_bwd(probs, ldp, scores, ldp, dS, ldp, dt, B * H, N, 0.125f, s));
   // dQ = dS K
   GemmArgs q = gemm_args(dS, (const char*)qkv + (size_t)D * e, dqkv, N, 64, N, ldp, 3 * D, 3 * D);
-  q.nb1 = B; q.nb2 = H;
-  q.sA1 = sP1; q.sA2 = sP2; q.sB1 = sQ1; q.sB2 = 64; q.sC1 = sQ1; q.sC2 = 64;
+  per_head(q, B, H, sP1, sP2, sQ1, 64, sQ1, 64);
   RMCL_TRY(rmcl_launch_gemm(q, dt, dt, 1, 0, exact, s));
   // dK = dS^T Q
   GemmArgs k = gemm_args(dS, qkv, (char*)dqkv + (size_t)D * e, N, 64, N, ldp, 3 * D, 3 * D);
-  k.nb1 = B; k.nb2 = H;
-  k.sA1 = sP1; k.sA2 = sP2; k.sB1 = sQ1; k.sB2 = 64; k.sC1 = sQ1; k.sC2 = 64;
+  per_head(k, B, H, sP1, sP2, sQ1, 64, sQ1, 64);
   RMCL_TRY(rmcl_launch_gemm(k, dt, dt, 0, 0, exact, s));
   // dV = P^T dO
   GemmArgs v = gemm_args(probs, dout, (char*)dqkv + (size_t)2 * D * e, N, 64, N, ldp, D, 3 * D);
-  v.nb1 = B; v.nb2 = H;
-  v.sA1 = sP1; v.sA2 = sP2; v.sB1 = (long)N * D; v.sB2 = 64; v.sC1 = sQ1; v.sC2 = 64;
+  per_head(v, B, H, sP1, sP2, (long)N * D, 64, sQ1, 64);
   RMCL_TRY(rmcl_launch_gemm(v, dt, dt, 0, 0, exact, s));
   return 0;
 }
@@ -429,187 +687,71 @@ static int encoder_forward_impl(const rmcl_dims* d, int mode, const float* param
   const int B = d->B, L = d->L, P = d->P, N = L + 1 + P, D = d->D, M = B * N, dt = d->dtype;
   const bool keep = mode != RMCL_MODE_INFER, full = mode == RMCL_MODE_FULL;
   hipStream_t s = c.s;
-  RMCL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "encoder_forward: dropout probability must be in [0,1)");
-  const uint32_t dth = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-  const float dinv = 1.0f / (1.0f - drop_p);
-  auto with_drop = [&](GemmArgs& g, int layer, int site, int row_mul = 1) {
-    if (dth) { g.epi |= EPI_DROPOUT; g.drop_seed = rmcl_site_seed(drop_seed, layer, site); g.drop_thresh = dth; g.drop_inv_keep = dinv; g.drop_row_mul = row_mul; }
-  };
+  Dropout drop{};
+  RMCL_TRY(make_dropout(drop_seed, drop_p, true, &drop));
 
   float* x0 = keep ? st.layer[0].x_in : w.x_a;
   RMCL_TRY(rmcl_text_embed_fwd((const long*)text_ids, c.V(y.word), c.V(y.pos), c.V(y.btype), c.V(y.eln_w), c.V(y.eln_b),
                                c.V(y.vtype), 1e-12f, x0, keep ? st.text_e : nullptr, keep ? st.text_mean : nullptr,
-                               keep ? st.text_rstd : nullptr, B, L, N, D, rmcl_site_seed(drop_seed, 0, DROP_SITE_TEXT), dth, dinv, s));
+                               keep ? st.text_rstd : nullptr, B, L, N, D, drop.site(0, DROP_SITE_TEXT), drop.thresh, drop.inv_keep, s));
   if (rank) {
     RMCL_TRY(rmcl_rank_assemble(rank->embeds, rank->masks, rank->img_of, rank->n_img, rank->ld_tok, (const long*)text_mask, c.V(y.vtype) + D,
                                 x0, co_mask, B, P, L, N, D, s));
   } else {
-    // the pixel path: patch GEMM, (resized) position rows, cls + token type, mask from the patch rows
-    GemmArgs g = gemm_args(patches, c.W(y.patch_w), w.pe, B * P, D, d->patch_k, d->patch_k, d->patch_k, D);
-    g.epi = EPI_BIAS; g.bias = c.V(y.patch_b); g.tag = GEMM_TAG_PATCH;
-    RMCL_TRY(gemm(c, g, dt, RMCL_F32, 1, 1));
-    // masked patch prediction: the learned mask token takes the place of the replaced patches' embeddings (rmcl_encoder_forward_mpp)
-    if (replaced) RMCL_TRY(rmcl_mask_token_fwd(w.pe, replaced, c.V(mask_token_off), B * P, D, s));
-    if (ragged) {
-      // zero-padded batch: per-sample position rows = the table resized to each image's (h, w), gathered at its selected
-      // patches (vision_transformer.py:570-600, 645-650); recomputed every pass from the arena of THIS pass (query or momentum)
-      RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
-                                   ragged->pos_tok, s));
-    }
+    // the pixel path: patch rows, (resized) position rows, cls + token type, mask from the patch rows
+    RMCL_TRY(patch_embed(c, w, patches, replaced, mask_token_off, ragged));
     // image token type (vilt_module.py:315-321): row 1, row 2 (img_type 2), or row 1 + (b & 1) per pair (img_type -1)
     RMCL_TRY(rmcl_image_assemble_fwd(w.pe, c.V(y.cls), ragged ? ragged->pos_tok : c.V(y.pos_img), c.V(y.vtype) + (d->img_type == 2 ? 2 : 1) * D,
-                                     x0, B, P, L, N, D, rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, ragged ? 1 : 0,
+                                     x0, B, P, L, N, D, drop.site(0, DROP_SITE_IMAGE), drop.thresh, drop.inv_keep, ragged ? 1 : 0,
                                      d->img_type == -1 ? 1 : 0, s));
     RMCL_TRY(rmcl_co_mask((const long*)text_mask, patches, dt, co_mask, B, L, P, 3, d->patch_k / 3, s));
   }
 
+  FwdPass pass{c, w, st, fold, M, D, d->mlp, keep, full, /*folded, centred, tiled, probe: decided below*/ false, false, false, false, drop};
   // LayerNorm folded into the consuming GEMMs (gemm.h EPI_LNFOLD / EPI_ROWSTAT): passes that keep no LayerNorm output
   // (INFER, DATA), bf16, dropout off, and only where every GEMM involved runs on the 192-row tile kernels
   // (dropout: the 192-row tile kernels carry the dropout epilogues as separate instantiations since round 4, so the fold stays on)
-  bool folded = fold && fold->wf && fold->sc && !full && dt == RMCL_BF16 && !d->exact && D % 192 == 0;
-  const int fold_rows = 3 * D + d->mlp, nparts = 4 * (D / 192);
-  if (folded) {
-    GemmArgs t1 = gemm_args(w.xb_in, fold->wf, w.qkv, M, 3 * D, D, D, D, 3 * D);
-    t1.epi = EPI_LNFOLD; t1.ln_s = fold->sc; t1.ln_c = fold->sc; t1.ln_part = w.part_in; t1.ln_nparts = nparts; t1.ln_cols = D;
-    GemmArgs t2 = gemm_args(w.xb_mid, fold->wf, w.h, M, d->mlp, D, D, D, d->mlp);
-    t2.epi = EPI_LNFOLD | EPI_GELU | EPI_SAVE_PREACT | (dth ? EPI_DROPOUT : 0); t2.C2 = w.u; t2.ln_s = fold->sc; t2.ln_c = fold->sc; t2.ln_part = w.part_mid; t2.ln_nparts = nparts; t2.ln_cols = D;
-    GemmArgs t3 = gemm_args(w.ao, c.W(c.L(0, y.proj_w)), w.x_mid, M, D, D, D, D, D);
-    t3.epi = EPI_BIAS | EPI_RESIDUAL | EPI_ROWSTAT | (dth ? EPI_DROPOUT : 0); t3.bias = c.V(y.norm_b); t3.aux = w.x_a; t3.ld_aux = D; t3.C2 = w.xb_mid; t3.ln_part = w.part_mid; t3.ln_nparts = nparts;
-    GemmArgs t4 = gemm_args(w.h, c.W(c.L(0, y.fc2_w)), w.x_a, M, D, d->mlp, d->mlp, d->mlp, D);
-    t4.epi = t3.epi; t4.bias = t3.bias; t4.aux = w.x_mid; t4.ld_aux = D; t4.C2 = w.xb_in; t4.ln_part = w.part_in; t4.ln_nparts = nparts;
-    folded = rmcl_gemm_routes_to_tile192(t1, 1, 1) && rmcl_gemm_routes_to_tile192(t2, 1, 1) && rmcl_gemm_routes_to_tile192(t3, 1, 1) &&
-             rmcl_gemm_routes_to_tile192(t4, 1, 1);
+  pass.folded = fold && fold->wf && fold->sc && !full && dt == RMCL_BF16 && !d->exact && D % 192 == 0;
+  if (pass.folded) {
+    const FwdPass q = pass.as_probe(true, false);
+    const FwdLayer b = q.layer(0, w.x_a);
+    pass.folded = rmcl_gemm_routes_to_tile192(q.qkv(0, b), 1, 1) && rmcl_gemm_routes_to_tile192(q.fc1(0, b), 1, 1) &&
+                  rmcl_gemm_routes_to_tile192(q.proj(0, b), 1, 1) && rmcl_gemm_routes_to_tile192(q.fc2(0, b), 1, 1);
   }
-  const bf16_t* fw = folded ? (const bf16_t*)fold->wf : nullptr;
   // Tiled pre-activation stash (gemm.h EPI_PREACT_TILED): decided ONCE per pass - both the pass's fc1 form and the backward's fc2-dX
   // (transposed weight shadows, [cols][K]) must go to the 192x384 kernel with the flag - and recorded with the stash: the backward
   // reads the record.  (The cls-only tail's compact fp32 u_c of the last layer is not a GEMM stash of this kind and stays as it is.)
   // (and the attention must leave the tail of the `probs` slots to the tiled buffer, carve_stash: the fused kernels, N <= 256, or the streamed ones)
-  bool tiled = g_preact_tiled && keep && dt == RMCL_BF16 && !d->exact && (N <= 256 || streamed) && st.layer[0].u_t != nullptr;
-  if (tiled) {
-    GemmArgs p1 = gemm_args(w.xb_mid, c.W(c.L(0, y.fc1_w)), w.h, M, d->mlp, D, D, D, d->mlp);
-    p1.epi = (folded ? EPI_LNFOLD : EPI_BIAS) | EPI_GELU | EPI_SAVE_PREACT | EPI_PREACT_TILED | (dth ? EPI_DROPOUT : 0); p1.C2 = w.u;
-    if (folded) { p1.ln_s = fold->sc; p1.ln_c = fold->sc; p1.ln_part = w.part_mid; p1.ln_nparts = nparts; p1.ln_cols = D; }
-    GemmArgs p2 = gemm_args(w.dxT, c.W(c.L(0, y.fc2_w)), w.du, M, d->mlp, D, D, D, d->mlp);
-    p2.epi = EPI_DGELU | EPI_PREACT_TILED | (dth ? EPI_DROP_BWD : 0); p2.aux = w.u; p2.ld_aux = d->mlp;
-    tiled = rmcl_gemm_fast_takes(p1, RMCL_BF16, RMCL_BF16, 1, 1) && rmcl_gemm_fast_takes(p2, RMCL_BF16, RMCL_BF16, 1, 1) &&
-            rmcl_gemm_route_code(p1, RMCL_BF16, 1, 1) == 2 && rmcl_gemm_route_code(p2, RMCL_BF16, 1, 1) == 2;
+  pass.tiled = g_preact_tiled && keep && dt == RMCL_BF16 && !d->exact && (N <= 256 || streamed) && st.layer[0].u_t != nullptr;
+  if (pass.tiled) {
+    const FwdPass q = pass.as_probe(pass.folded, true);
+    const GemmArgs p1 = q.fc1(0, q.layer(0, w.x_a));
+    // the backward's fc2-dX on its workspace buffers; the forward has no transposed shadows, the shadow arena stands in for them (same layout offsets)
+    const GemmArgs p2 = BwdSites{c, M, c.Plp, true, drop}.fc2(0, w.dxT, w.u, w.du);
+    pass.tiled = rmcl_gemm_fast_takes(p1, RMCL_BF16, RMCL_BF16, 1, 1) && rmcl_gemm_fast_takes(p2, RMCL_BF16, RMCL_BF16, 1, 1) &&
+                 rmcl_gemm_route_code(p1, RMCL_BF16, 1, 1) == 2 && rmcl_gemm_route_code(p2, RMCL_BF16, 1, 1) == 2;
   }
-  if (keep) note_stash(stash, streamed, tiled);
-  const int epi_tiled = tiled ? EPI_PREACT_TILED : 0;
+  if (keep) note_stash(stash, streamed, pass.tiled);
   // shift-robust form of the fold (gemm.h ln_center): every producer stores bf16(x - c) and the partial sums of (x - c), c = the row mean
   // of the row's PREVIOUS LayerNorm (LN is shift-invariant: exact for any c), so the operand's rounding follows the row's spread instead of
   // its offset.  rmcl_tune_set(11, 0) restores the uncentred round-2 form (A/B, precision tests).
-  const bool centred = folded && rmcl_lnfold_centred();
+  pass.centred = pass.folded && rmcl_lnfold_centred();
   float* x = x0;
   for (int l = 0; l < d->layers; ++l) {
-    LayerStash ls{};
-    if (keep) ls = st.layer[l];
-    float* x_mid = keep ? ls.x_mid : w.x_mid;
-    float* x_out = keep ? (l + 1 < d->layers ? st.layer[l + 1].x_in : st.x_final) : (x == w.x_a ? w.x_b : w.x_a);
-    float *m1 = keep ? ls.mean1 : w.stat, *r1 = keep ? ls.rstd1 : w.stat + M;
-    float *m2 = keep ? ls.mean2 : w.stat + 2 * M, *r2 = keep ? ls.rstd2 : w.stat + 3 * M;
-    void* ln1 = full ? ls.ln1 : w.ln;
-    void* ln2 = full ? ls.ln2 : w.ln;
-    void* qkv = keep ? ls.qkv : w.qkv;
-    void* probs = keep ? ls.probs : w.probs;
-    void* ao = keep ? ls.ao : w.ao;
-    void* h = full ? ls.h : w.h;
-    void* u = keep ? (tiled ? ls.u_t : ls.u) : nullptr;
-    const float* sc_l = folded ? fold->sc + (long)l * 2 * fold_rows : nullptr;        // s[0..rows), c[rows..2 rows)
-    // LayerNorm 2's row means of the previous layer = the centre the previous fc2 used for this layer's LayerNorm-1 operand
-    const float* m2_prev = l > 0 ? (keep ? st.layer[l - 1].mean2 : w.stat + 2 * M) : nullptr;
-
-    if (folded && l > 0) {
-      // qkv = LN1(x) Wqkv^T + b: A = the bf16 copy of x the previous fc2 epilogue wrote, row statistics from its partial sums
-      GemmArgs g = gemm_args(w.xb_in, fw + (long)l * fold_rows * D, qkv, M, 3 * D, D, D, D, 3 * D);
-      g.epi = EPI_LNFOLD; g.tag = GEMM_TAG_QKV;
-      g.ln_s = sc_l; g.ln_c = sc_l + fold_rows; g.ln_part = w.part_in; g.ln_nparts = nparts; g.ln_cols = D; g.ln_eps = 1e-6f;
-      // the partials (and the bf16 operand) were taken about the previous LayerNorm's row mean (m2 of layer l - 1, see the fc2 producer);
-      // the statistics are written in every mode now: the next producer centres on them
-      g.ln_mean = m1; g.ln_rstd = r1; g.ln_center = centred ? m2_prev : nullptr;
-      RMCL_TRY(gemm(c, g, dt, dt, 1, 1));
-    } else {
-      RMCL_TRY(rmcl_ln_fwd(x, D, c.V(c.L(l, y.ln1_w)), c.V(c.L(l, y.ln1_b)), 1e-6f, ln1, D, dt, m1, r1, M, D, 0, s));
-      GemmArgs g = gemm_args(ln1, c.W(c.L(l, y.qkv_w)), qkv, M, 3 * D, D, D, D, 3 * D);
-      g.epi = EPI_BIAS; g.bias = c.V(c.L(l, y.qkv_b)); g.tag = GEMM_TAG_QKV;
-      RMCL_TRY(gemm(c, g, dt, dt, 1, 1));
-    }
-    if (streamed) RMCL_TRY(rmcl_attn_stream_fwd(qkv, co_mask, ao, (float*)probs, B, N, d->H, s));   // `probs` keeps the log-sum-exp
-    else RMCL_TRY(rmcl_attention_fwd_impl(qkv, co_mask, ao, probs, w.scores, B, N, d->H, dt, d->exact, s));
-    if (tail_req && l + 1 == d->layers) {
-      // cls-only tail: of the last block's output only row 0 of every sample is read (the pooler takes hidden_states[:, 0],
-      // heads.py:17), and everything behind the attention is row-wise - proj, LayerNorm 2, the MLP and the final LayerNorm run
-      // on the B cls rows (fp32, exact skinny GEMMs) instead of on all B * N tokens.  Compact results live in the FIRST B rows
-      // of the buffers the dense path would have filled (x_mid, u, h, ln2, x_final, the LN statistics) - the backward with
-      // cls_only = 2 reads them there.  Dropout: compact row b draws the mask of the dense row b * N it stands for (gemm.h
-      // drop_row_mul), so the tail gives the dense block's numbers under dropout too.
-      float* ao_c = reinterpret_cast<float*>(w.dao);          // backward scratch, free during a forward
-      float* ln2_c = reinterpret_cast<float*>(full ? ls.ln2 : w.ln);
-      float* u_c = reinterpret_cast<float*>(keep ? ls.u : w.u);
-      float* h_c = reinterpret_cast<float*>(full ? ls.h : w.h);
-      float* xo_c = keep ? st.x_final : x_out;
-      {
-        // residual operand: the cls rows of the dense residual stream, read in place (row b at b * N * D: no gather launch).  The A
-        // operand likewise where the streaming skinny kernel runs the GEMM: the cls rows of the attention output at row stride
-        // N * D, bf16 widened in its registers - the bits of the gather-and-cast launch, which only the other forms still need
-        GemmArgs g = gemm_args(ao, c.V(c.L(l, y.proj_w)), x_mid, B, D, D, (long)N * D, D, D);
-        g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, y.proj_b)); g.aux = x; g.ld_aux = N * D;
-        g.a_bf16 = dt == RMCL_BF16;
-        with_drop(g, l, DROP_SITE_PROJ, N);
-        if (!rmcl_gemm_skinny_streams(g, 1)) {
-          RMCL_TRY(rmcl_rows_gather_cast(ao, dt, ao_c, B, D, N, 0, s));
-          g.A = ao_c; g.lda = D; g.a_bf16 = 0;
-        }
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
-      }
-      RMCL_TRY(rmcl_ln_fwd(x_mid, D, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), 1e-6f, ln2_c, D, RMCL_F32, m2, r2, B, D, 0, s));
-      {
-        GemmArgs g = gemm_args(ln2_c, c.V(c.L(l, y.fc1_w)), h_c, B, d->mlp, D, D, D, d->mlp);
-        g.epi = EPI_BIAS | EPI_GELU | EPI_SAVE_PREACT; g.bias = c.V(c.L(l, y.fc1_b)); g.C2 = u_c;
-        with_drop(g, l, DROP_SITE_HIDDEN, N);
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
-      }
-      {
-        GemmArgs g = gemm_args(h_c, c.V(c.L(l, y.fc2_w)), xo_c, B, D, d->mlp, d->mlp, d->mlp, D);
-        g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, y.fc2_b)); g.aux = x_mid; g.ld_aux = D;
-        with_drop(g, l, DROP_SITE_FC2, N);
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 1, s));
-      }
-      // final LayerNorm of the cls rows, written to their places in xn (row b * N); the other rows of xn are NOT written
-      RMCL_TRY(rmcl_ln_fwd(xo_c, D, c.V(y.norm_w), c.V(y.norm_b), 1e-6f, xn, (long)N * D, RMCL_F32, keep ? st.meanF : w.stat,
-                           keep ? st.rstdF : w.stat + M, B, D, 0, s));
-      return 0;
-    }
-    {
-      GemmArgs g = gemm_args(ao, c.W(c.L(l, y.proj_w)), x_mid, M, D, D, D, D, D);
-      g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, y.proj_b)); g.aux = x; g.ld_aux = D; g.tag = GEMM_TAG_PROJ;
-      if (folded) { g.epi |= EPI_ROWSTAT; g.C2 = w.xb_mid; g.ln_part = w.part_mid; g.ln_nparts = nparts; g.ln_center = centred ? m1 : nullptr; }
-      with_drop(g, l, DROP_SITE_PROJ);
-      RMCL_TRY(gemm(c, g, dt, RMCL_F32, 1, 1));
-    }
-    if (folded) {
-      GemmArgs g = gemm_args(w.xb_mid, fw + ((long)l * fold_rows + 3 * D) * D, h, M, d->mlp, D, D, D, d->mlp);
-      g.epi = EPI_LNFOLD | EPI_GELU | (u ? EPI_SAVE_PREACT | epi_tiled : 0); g.C2 = u; g.tag = GEMM_TAG_FC1;
-      g.ln_s = sc_l + 3 * D; g.ln_c = sc_l + fold_rows + 3 * D; g.ln_part = w.part_mid; g.ln_nparts = nparts; g.ln_cols = D; g.ln_eps = 1e-6f;
-      g.ln_mean = m2; g.ln_rstd = r2; g.ln_center = centred ? m1 : nullptr;
-      with_drop(g, l, DROP_SITE_HIDDEN);
-      RMCL_TRY(gemm(c, g, dt, dt, 1, 1));
-    } else {
-      RMCL_TRY(rmcl_ln_fwd(x_mid, D, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), 1e-6f, ln2, D, dt, m2, r2, M, D, 0, s));
-      GemmArgs g = gemm_args(ln2, c.W(c.L(l, y.fc1_w)), h, M, d->mlp, D, D, D, d->mlp);
-      g.epi = EPI_BIAS | EPI_GELU | (u ? EPI_SAVE_PREACT | epi_tiled : 0); g.bias = c.V(c.L(l, y.fc1_b)); g.C2 = u; g.tag = GEMM_TAG_FC1;
-      with_drop(g, l, DROP_SITE_HIDDEN);
-      RMCL_TRY(gemm(c, g, dt, dt, 1, 1));
-    }
-    {
-      GemmArgs g = gemm_args(h, c.W(c.L(l, y.fc2_w)), x_out, M, D, d->mlp, d->mlp, d->mlp, D);
-      g.epi = EPI_BIAS | EPI_RESIDUAL; g.bias = c.V(c.L(l, y.fc2_b)); g.aux = x_mid; g.ld_aux = D; g.tag = GEMM_TAG_FC2;
-      if (folded && l + 1 < d->layers) { g.epi |= EPI_ROWSTAT; g.C2 = w.xb_in; g.ln_part = w.part_in; g.ln_nparts = nparts; g.ln_center = centred ? m2 : nullptr; }
-      with_drop(g, l, DROP_SITE_FC2);
-      RMCL_TRY(gemm(c, g, dt, RMCL_F32, 1, 1));
-    }
-    x = x_out;
+    const FwdLayer b = pass.layer(l, x);
+    // (a folded pass: layer 0's qkv still reads the embedding through the LayerNorm kernel; later layers read the previous fc2's bf16 copy)
+    if (!(pass.folded && l > 0))
+      RMCL_TRY(rmcl_ln_fwd(x, D, c.V(c.L(l, y.ln1_w)), c.V(c.L(l, y.ln1_b)), 1e-6f, b.ln1, D, dt, b.mean1, b.rstd1, M, D, 0, s));
+    RMCL_TRY(gemm(c, pass.qkv(l, b), dt, dt, 1, 1));
+    if (streamed) RMCL_TRY(rmcl_attn_stream_fwd(b.qkv, co_mask, b.ao, (float*)b.probs, B, N, d->H, s));   // `probs` keeps the log-sum-exp
+    else RMCL_TRY(rmcl_attention_fwd_impl(b.qkv, co_mask, b.ao, b.probs, w.scores, B, N, d->H, dt, d->exact, s));
+    if (tail_req && l + 1 == d->layers) return forward_tail(pass, l, b, xn);
+    RMCL_TRY(gemm(c, pass.proj(l, b), dt, RMCL_F32, 1, 1));
+    if (!pass.folded)
+      RMCL_TRY(rmcl_ln_fwd(b.x_mid, D, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), 1e-6f, b.ln2, D, dt, b.mean2, b.rstd2, M, D, 0, s));
+    RMCL_TRY(gemm(c, pass.fc1(l, b), dt, dt, 1, 1));
+    RMCL_TRY(gemm(c, pass.fc2(l, b), dt, RMCL_F32, 1, 1));
+    x = b.x_out;
   }
   RMCL_TRY(rmcl_ln_fwd(x, D, c.V(y.norm_w), c.V(y.norm_b), 1e-6f, xn, D, RMCL_F32, keep ? st.meanF : w.stat,
                        keep ? st.rstdF : w.stat + M, M, D, 0, s));
@@ -659,16 +801,7 @@ static int visual_embed_impl(const rmcl_dims* d, const float* params32, const vo
   Work w{};
   carve_work(*d, workspace, &w);
   const int B = d->B, P = d->P, D = d->D;
-  {
-    GemmArgs g = gemm_args(patches, c.W(y.patch_w), w.pe, B * P, D, d->patch_k, d->patch_k, d->patch_k, D);
-    g.epi = EPI_BIAS; g.bias = c.V(y.patch_b); g.tag = GEMM_TAG_PATCH;
-    RMCL_TRY(gemm(c, g, d->dtype, RMCL_F32, 1, 1));
-  }
-  if (replaced) RMCL_TRY(rmcl_mask_token_fwd(w.pe, replaced, c.V(mask_token_off), B * P, D, c.s));
-  if (ragged) {
-    RMCL_TRY(rmcl_pos_resize_fwd(c.V(y.pos_img), ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
-                                 ragged->pos_tok, c.s));
-  }
+  RMCL_TRY(patch_embed(c, w, patches, replaced, mask_token_off, ragged));
   RMCL_TRY(rmcl_visual_assemble(w.pe, c.V(y.cls), ragged ? ragged->pos_tok : c.V(y.pos_img), ragged ? 1 : 0, out, B, P, D, c.s));
   // the mask of rmcl_encoder_forward's image tokens (L = 0: no text columns; the text-mask pointer is never read)
   RMCL_TRY(rmcl_co_mask(nullptr, patches, d->dtype, masks, B, 0, P, 3, d->patch_k / 3, c.s));
@@ -702,10 +835,12 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
   RMCL_REQUIRE(!ragged || mode != RMCL_MODE_FULL || ragged->dpos_tok, "encoder_backward: rmcl_ragged.dpos_tok needed in FULL mode");
   RMCL_REQUIRE(mode == RMCL_MODE_DATA || mode == RMCL_MODE_FULL, "encoder_backward: mode must be DATA or FULL");
   RMCL_REQUIRE(params32 && stash && workspace && dxn && co_mask, "encoder_backward: NULL argument");
-  RMCL_REQUIRE(!stash_disagrees(stash, streamed), "encoder_backward: RMCL_MODE_STREAM_ATTN differs from the forward that filled this stash");
+  StashNote note{};
+  const bool noted = stash_note(stash, &note);                 // (a stash the table no longer knows: nothing to compare the attention setting with)
+  RMCL_REQUIRE(!noted || note.stream == streamed, "encoder_backward: RMCL_MODE_STREAM_ATTN differs from the forward that filled this stash");
   RMCL_REQUIRE(mode != RMCL_MODE_FULL || (G && text_ids && patches), "encoder_backward: FULL mode needs grads32, text_ids, patches");
   // layout of the `u` slots: what the forward that filled this stash recorded
-  const int u_tiled = d->dtype == RMCL_BF16 && !d->exact ? stash_tiled(stash) : 0;
+  const int u_tiled = d->dtype == RMCL_BF16 && !d->exact ? (noted ? (note.tiled ? 1 : 0) : -1) : 0;
   RMCL_REQUIRE(u_tiled >= 0, "encoder_backward: no forward on record for this stash (the layout of its pre-activation slots is unknown)");
   RMCL_REQUIRE(!u_tiled || (d->L + 1 + d->P <= 256 || streamed), "encoder_backward: a tiled pre-activation stash goes with fused or streamed attention");
   RMCL_REQUIRE(!u_tiled || params_lpT, "encoder_backward: this stash holds the tiled pre-activation (rmcl_tune_set key 15), whose backward needs the "
@@ -728,21 +863,19 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
   const bool tail = cls_only == 2;               // the forward of this stash used the cls-only tail (compact last-layer rows)
   RMCL_REQUIRE(!tail || d->B <= 1024, "encoder_backward: the cls-only tail needs B <= 1024");
   if (cls_only && !tail) {
-    hipError_t e = hipMemsetAsync(w.dxn_full, 0, (size_t)M * D * sizeof(float), s);
-    if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+    HIP_TRY(hipMemsetAsync(w.dxn_full, 0, (size_t)M * D * sizeof(float), s));
     RMCL_TRY(rmcl_scatter_rows(dxn, w.dxn_full, B, D, 1, N, 0, 0, s));
     dy = w.dxn_full;
   }
   // bf16 copy of dx written by every LN backward (ping-pong T[0]/T[1]); with a side stream the weight
   // gradients of layer l run concurrently with the data-gradient chain, reading the copy the chain no
   // longer writes (events order the reuse of T / du / dqkv two sub-layers later).
-  RMCL_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "encoder_backward: dropout probability must be in [0,1)");
-  const uint32_t dth = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-  const float dinv = 1.0f / (1.0f - drop_p);
-  const bool lpm = dt != RMCL_F32 || dth != 0;      // a (masked) copy of dx in the GEMM operand type is needed
-  // transposed bf16 weight shadows: dX = dY W as [rows][K] x [cols][K] (W^T stored [in][out], k = out contiguous)
+  Dropout drop{};
+  RMCL_TRY(make_dropout(drop_seed, drop_p, false, &drop));
+  const bool lpm = dt != RMCL_F32 || drop.thresh != 0;      // a (masked) copy of dx in the GEMM operand type is needed
+  // transposed bf16 weight shadows: dX = dY W as [rows][K] x [cols][K] (BwdSites::lpT)
   const bool WT = params_lpT != nullptr && dt == RMCL_BF16 && !d->exact;
-  auto WTp = [&](int64_t off) { return (const void*)((const bf16_t*)params_lpT + off); };
+  const BwdSites sites{c, M, WT ? params_lpT : nullptr, u_tiled != 0, drop};
   // GROUPED weight gradients (bf16 fast path at the step's shapes): ONE launch per layer computes the four dW, the four bias
   // gradients and finishes the layer's LayerNorm dgamma/dbeta (gemm_dw_group_kernel); otherwise four split-K GEMMs + slab
   // reduces + column sums per layer.
@@ -757,18 +890,13 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
   void* T[3] = {lpm ? w.dxT : nullptr, lpm ? ((use_side || grouped) ? w.dxT2 : w.dxT) : nullptr, lpm ? w.dxT3 : nullptr};
   void* DU[2] = {w.du, (use_side || grouped) ? w.du2 : w.du};
   void* DQ[2] = {w.dqkv, (use_side || grouped) ? w.dqkv2 : w.dqkv};
-  Ctx cs{c.d, c.P32, c.Plp, c.lay, use_side ? g_side : c.s, c.dt};
-  auto EV = [&](int kind, int l) { return g_ev[(kind * 32 + (l & 31)) & 127]; };   // kind 0: fork, 1: done1, 2: done2 / side done, 3: main done
+  Ctx cs{c.d, c.P32, c.Plp, c.lay, use_side ? g_side : c.s, c.dt};      // where the weight gradients run
   auto rep_slot = [&](int idx) { return grouped ? w.ln_rep + (size_t)idx * RMCL_LN_REP_FLOATS : nullptr; };   // 0: final norm, 1+2l: ln2, 2+2l: ln1
   if (grouped) HIP_TRY(hipMemsetAsync(w.ln_rep, 0, (size_t)(2 * Lr + 1) * RMCL_LN_REP_FLOATS * sizeof(float), s));
   // stash prefetch: while layer l's backward runs, the idle CUs touch layer l - 1's cold operands into the Infinity Cache
   const bool pref = g_prefetch_mask != 0 && g_pref != nullptr && dt == RMCL_BF16 && !d->exact && M >= 4096;
-  if (pref) {
-    while (g_npev < 64) {
-      HIP_TRY(hipEventCreateWithFlags(&g_pev[g_npev], hipEventDisableTiming));
-      ++g_npev;
-    }
-  }
+  if (pref)
+    for (; g_npev < 64; ++g_npev) HIP_TRY(hipEventCreateWithFlags(&g_pev[g_npev], hipEventDisableTiming));
   static int pev_rot = 0;
   auto prefetch_layer = [&](int l) -> int {
     if (!pref || l < 0) return 0;
@@ -797,7 +925,7 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
   } else {
     RMCL_TRY(rmcl_ln_bwd_lp(dy, D, RMCL_F32, st.x_final, D, st.meanF, st.rstdF, c.V(y.norm_w), c.V(y.norm_b), w.dx, D, 0,
                             full ? Gp(y.norm_w) : nullptr, full ? Gp(y.norm_b) : nullptr, M, D, 0, T[0], dt,
-                            rmcl_site_seed(drop_seed, d->layers - 1, DROP_SITE_FC2), dth, dinv, rep_slot(0), s));
+                            drop.site(d->layers - 1, DROP_SITE_FC2), drop.thresh, drop.inv_keep, rep_slot(0), s));
   }
   // gradient w.r.t. the LayerNorm outputs (dX GEMM -> LN backward): in the operand dtype, like du / dqkv / dao (bf16 mode
   // halves the 36 MB write + read per LayerNorm); fp32 mode is unchanged
@@ -809,186 +937,97 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
     void* dqkv = DQ[l & 1];
     const int ia = cur, ib = grouped ? (cur + 1) % 3 : cur ^ 1, ic = grouped ? (cur + 2) % 3 : cur;
     const bool tail_l = tail && l == Lr - 1;
-    if (tail_l) {
-      // ---- last layer, cls rows only: MLP, LayerNorm 2 and proj backward on [B, .] fp32 (exact skinny GEMMs); weight / bias
-      // gradients of fc2, fc1, proj reduce over B rows instead of B * N; then the two row sets the dense chain continues
-      // from are rebuilt: the residual-stream gradient w.dx and d(attention output) w.dao, zero except on the cls rows.
-      float* u_c = reinterpret_cast<float*>(ls.u);
-      float* h_c = reinterpret_cast<float*>(ls.h);
-      float* ln2_c = reinterpret_cast<float*>(ls.ln2);
-      float* du_c = reinterpret_cast<float*>(w.du);
-      float* dln_c = w.dln;
-      float* ao_c = reinterpret_cast<float*>(w.dqkv2);
-      float* dao_c = reinterpret_cast<float*>(w.du2);
-      // dropout: the gradient entering fc2 / proj is the residual-stream gradient times the mask of that branch's output - the mask of
-      // the DENSE cls row b * N (forward: drop_row_mul = N); dxc itself keeps flowing down the residual path unmasked
-      const float* dy2 = dxc;                                 // d(fc2 output)
-      if (dth) {
-        float* m2 = reinterpret_cast<float*>(w.dS);           // (attention-backward scratch: free until the attention backward below)
-        RMCL_TRY(rmcl_dropout_rows(dxc, m2, B, D, N, rmcl_site_seed(drop_seed, l, DROP_SITE_FC2), dth, dinv, s));
-        dy2 = m2;
-      }
-      {
-        GemmArgs g = gemm_args(dy2, c.V(c.L(l, y.fc2_w)), du_c, B, mlp, D, D, mlp, mlp);               // du = (dx W2) * gelu'(u) [* hidden mask]
-        g.epi = EPI_DGELU; g.aux = u_c; g.ld_aux = mlp;
-        if (dth) { g.epi |= EPI_DROP_BWD; g.drop_seed = rmcl_site_seed(drop_seed, l, DROP_SITE_HIDDEN); g.drop_thresh = dth; g.drop_inv_keep = dinv; g.drop_row_mul = N; }
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 0, s));
-      }
-      if (full) {
-        GemmArgs g = gemm_args(dy2, h_c, Gp(c.L(l, y.fc2_w)), D, mlp, B, D, mlp, mlp);                   // dW2 += dx^T h
-        g.epi = EPI_ACCUM;
-        const bool cs = rmcl_gemm_tn_shortk_takes(g);                                                    // bias gradient from the same launch
-        if (cs) { g.epi |= EPI_COLSUM; g.colsum = Gp(c.L(l, y.fc2_b)); }
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
-        if (!cs) RMCL_TRY(rmcl_colsum(dy2, D, RMCL_F32, Gp(c.L(l, y.fc2_b)), B, D, s));
-      }
-      {
-        GemmArgs g = gemm_args(du_c, c.V(c.L(l, y.fc1_w)), dln_c, B, D, mlp, mlp, D, D);                 // dln2 = du W1
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 0, s));
-      }
-      if (full) {
-        GemmArgs g = gemm_args(du_c, ln2_c, Gp(c.L(l, y.fc1_w)), mlp, D, B, mlp, D, D);                  // dW1 += du^T ln2
-        g.epi = EPI_ACCUM;
-        const bool cs = rmcl_gemm_tn_shortk_takes(g);
-        if (cs) { g.epi |= EPI_COLSUM; g.colsum = Gp(c.L(l, y.fc1_b)); }
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
-        if (!cs) RMCL_TRY(rmcl_colsum(du_c, mlp, RMCL_F32, Gp(c.L(l, y.fc1_b)), B, mlp, s));
-      }
-      RMCL_TRY(rmcl_ln_bwd(dln_c, D, RMCL_F32, ls.x_mid, D, ls.mean2, ls.rstd2, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), dxc, D, 1,
-                           full ? Gp(c.L(l, y.ln2_w)) : nullptr, full ? Gp(c.L(l, y.ln2_b)) : nullptr, B, D, 0, s));   // dxc = d x_mid
-      const float* dyp = dxc;                                 // d(proj output)
-      if (dth) {
-        float* mp = reinterpret_cast<float*>(w.dS) + (size_t)B * D;
-        RMCL_TRY(rmcl_dropout_rows(dxc, mp, B, D, N, rmcl_site_seed(drop_seed, l, DROP_SITE_PROJ), dth, dinv, s));
-        dyp = mp;
-      }
-      {
-        GemmArgs g = gemm_args(dyp, c.V(c.L(l, y.proj_w)), dao_c, B, D, D, D, D, D);                     // dao = dx Wproj
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 1, 0, s));
-      }
-      if (full) {
-        RMCL_TRY(rmcl_rows_gather_cast(ls.ao, dt, ao_c, B, D, N, 0, s));
-        GemmArgs g = gemm_args(dyp, ao_c, Gp(c.L(l, y.proj_w)), D, D, B, D, D, D);                       // dWproj += dx^T ao
-        g.epi = EPI_ACCUM;
-        const bool cs = rmcl_gemm_tn_shortk_takes(g);
-        if (cs) { g.epi |= EPI_COLSUM; g.colsum = Gp(c.L(l, y.proj_b)); }
-        RMCL_TRY(rmcl_launch_gemm_exact(g, RMCL_F32, RMCL_F32, 0, 0, s));
-        if (!cs) RMCL_TRY(rmcl_colsum(dyp, D, RMCL_F32, Gp(c.L(l, y.proj_b)), B, D, s));
-      }
-      HIP_TRY(hipMemsetAsync(w.dx, 0, (size_t)M * D * sizeof(float), s));
-      RMCL_TRY(rmcl_scatter_rows(dxc, w.dx, B, D, 1, N, 0, 0, s));
-      HIP_TRY(hipMemsetAsync(w.dao, 0, (size_t)M * D * esz(dt), s));
-      RMCL_TRY(rmcl_rows_scatter_cast(dao_c, w.dao, dt, B, D, N, 0, s));
-      if (full && !grouped && use_side) HIP_TRY(hipEventRecord(EV(1, l), cs.s));   // (no MLP weight-gradient work on the side stream)
-    }
-    // ---- MLP ----
+    const bool per_gemm = full && !grouped;      // the layer's weight gradients as separate GEMMs (on the side stream when there is one)
     const void* dxT = lpm ? T[ia] : (const void*)w.dx;
     const void* dxT_b = lpm ? T[ib] : (const void*)w.dx;
-    if (!tail_l) {
-    if (use_side && !grouped && l + 2 < Lr) HIP_TRY(hipStreamWaitEvent(s, EV(1, l + 2), 0));   // du buffer free again
-    {
-      GemmArgs g = gemm_args(dxT, WT ? WTp(c.L(l, y.fc2_w)) : c.W(c.L(l, y.fc2_w)), du, M, mlp, D, D, WT ? D : mlp, mlp);   // du = (dx W2) * gelu'(u)
-      // (tiled stash: the launch fails with a message when the GEMM no longer routes to the 192x384 kernel - never a row-major read)
-      g.epi = EPI_DGELU | (u_tiled ? EPI_PREACT_TILED : 0); g.aux = u_tiled ? ls.u_t : ls.u; g.ld_aux = mlp; g.tag = GEMM_TAG_DX;
-      if (dth) { g.epi |= EPI_DROP_BWD; g.drop_seed = rmcl_site_seed(drop_seed, l, DROP_SITE_HIDDEN); g.drop_thresh = dth; g.drop_inv_keep = dinv; }
-      RMCL_TRY(gemm(c, g, dt, dt, 1, WT ? 1 : 0));
+    auto dw = [&](const void* dY, const void* X, int64_t w_rel, int64_t b_rel, int Nout, int Kin) {
+      return linear_dw(cs, w, dY, X, Gp(c.L(l, w_rel)), Gp(c.L(l, b_rel)), Nout, Kin, M);
+    };
+    auto dw_qkv = [&] { return dw(dqkv, ls.ln1, y.qkv_w, y.qkv_b, 3 * D, D); };
+    if (tail_l) {
+      RMCL_TRY(backward_tail(c, w, ls, l, full ? G : nullptr, drop, dxc));
+      if (per_gemm && use_side) HIP_TRY(hipEventRecord(ev_slot(EV_MLP_DONE, l), cs.s));   // (no MLP weight-gradient work on the side stream)
+    } else {
+      // ---- MLP ----
+      if (use_side && !grouped && l + 2 < Lr) HIP_TRY(hipStreamWaitEvent(s, ev_slot(EV_MLP_DONE, l + 2), 0));   // du buffer free again
+      RMCL_TRY(gemm(c, sites.fc2(l, dxT, u_tiled ? ls.u_t : ls.u, du), dt, dt, 1, sites.b_kc()));
+      if (per_gemm) {
+        if (use_side) { HIP_TRY(hipEventRecord(ev_slot(EV_FORK, 2 * l), s)); HIP_TRY(hipStreamWaitEvent(cs.s, ev_slot(EV_FORK, 2 * l), 0)); }
+        RMCL_TRY(dw(dxT, ls.h, y.fc2_w, y.fc2_b, D, mlp));
+        RMCL_TRY(dw(du, ls.ln2, y.fc1_w, y.fc1_b, mlp, D));
+        if (use_side) HIP_TRY(hipEventRecord(ev_slot(EV_MLP_DONE, l), cs.s));
+      }
+      RMCL_TRY(gemm(c, sites.fc1(l, du, w.dln), dt, dln_dt, 1, sites.b_kc()));
+      if (use_side && l + 1 < Lr) HIP_TRY(hipStreamWaitEvent(s, ev_slot(EV_SIDE_DONE, l + 1), 0));   // T[ib] free again (grouped: layer l+1's whole
+                                                                                                     // weight-gradient launch has finished)
+      RMCL_TRY(rmcl_ln_bwd_lp(w.dln, D, dln_dt, ls.x_mid, D, ls.mean2, ls.rstd2, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), w.dx, D, 1,
+                              full ? Gp(c.L(l, y.ln2_w)) : nullptr, full ? Gp(c.L(l, y.ln2_b)) : nullptr, M, D, 0, T[ib], dt,
+                              drop.site(l, DROP_SITE_PROJ), drop.thresh, drop.inv_keep, rep_slot(1 + 2 * l), s));
+      // ---- attention ----
+      RMCL_TRY(gemm(c, sites.proj(l, dxT_b, w.dao), dt, dt, 1, sites.b_kc()));
     }
-    if (full && !grouped) {
-      if (use_side) { HIP_TRY(hipEventRecord(EV(0, 2 * l), s)); HIP_TRY(hipStreamWaitEvent(cs.s, EV(0, 2 * l), 0)); }
-      RMCL_TRY(gemm_dw(cs, dxT, D, ls.h, mlp, Gp(c.L(l, y.fc2_w)), D, mlp, M, dt, w.slab, SLAB_FLOATS(*d)));
-      RMCL_TRY(rmcl_colsum(dxT, D, dt, Gp(c.L(l, y.fc2_b)), M, D, cs.s));
-      RMCL_TRY(gemm_dw(cs, du, mlp, ls.ln2, D, Gp(c.L(l, y.fc1_w)), mlp, D, M, dt, w.slab, SLAB_FLOATS(*d)));
-      RMCL_TRY(rmcl_colsum(du, mlp, dt, Gp(c.L(l, y.fc1_b)), M, mlp, cs.s));
-      if (use_side) HIP_TRY(hipEventRecord(EV(1, l), cs.s));
-    }
-    {
-      GemmArgs g = gemm_args(du, WT ? WTp(c.L(l, y.fc1_w)) : c.W(c.L(l, y.fc1_w)), w.dln, M, D, mlp, mlp, WT ? mlp : D, D);   // dln2 = du W1
-      g.tag = GEMM_TAG_DX;
-      RMCL_TRY(gemm(c, g, dt, dln_dt, 1, WT ? 1 : 0));
-    }
-    if (use_side && l + 1 < Lr) HIP_TRY(hipStreamWaitEvent(s, EV(2, l + 1), 0));           // T[ib] free again (grouped: layer l+1's whole
-                                                                                           // weight-gradient launch has finished)
-    RMCL_TRY(rmcl_ln_bwd_lp(w.dln, D, dln_dt, ls.x_mid, D, ls.mean2, ls.rstd2, c.V(c.L(l, y.ln2_w)), c.V(c.L(l, y.ln2_b)), w.dx, D, 1,
-                            full ? Gp(c.L(l, y.ln2_w)) : nullptr, full ? Gp(c.L(l, y.ln2_b)) : nullptr, M, D, 0, T[ib], dt,
-                            rmcl_site_seed(drop_seed, l, DROP_SITE_PROJ), dth, dinv, rep_slot(1 + 2 * l), s));
-    // ---- attention ----
-    {
-      GemmArgs g = gemm_args(dxT_b, WT ? WTp(c.L(l, y.proj_w)) : c.W(c.L(l, y.proj_w)), w.dao, M, D, D, D, D, D);   // dao = dx Wproj
-      g.tag = GEMM_TAG_DX;
-      RMCL_TRY(gemm(c, g, dt, dt, 1, WT ? 1 : 0));
-    }
-    }   // !tail_l
-    if (use_side && !grouped && l + 2 < Lr) HIP_TRY(hipStreamWaitEvent(s, EV(2, l + 2), 0));   // dqkv buffer free again
+    if (use_side && !grouped && l + 2 < Lr) HIP_TRY(hipStreamWaitEvent(s, ev_slot(EV_SIDE_DONE, l + 2), 0));   // dqkv buffer free again
     if (streamed) RMCL_TRY(rmcl_attn_stream_bwd(ls.qkv, co_mask, w.dao, ls.ao, (const float*)ls.probs, w.scores, dqkv, B, N, d->H, s));
     else RMCL_TRY(rmcl_attention_bwd_impl(ls.qkv, co_mask, ls.probs, w.dao, ls.ao, dqkv, w.scores, w.dS, B, N, d->H, dt, d->exact, s));
-    if (full && !grouped) {
-      if (use_side) { HIP_TRY(hipEventRecord(EV(0, 2 * l + 1), s)); HIP_TRY(hipStreamWaitEvent(cs.s, EV(0, 2 * l + 1), 0)); }
-      if (!tail_l) {
-        RMCL_TRY(gemm_dw(cs, dxT_b, D, ls.ao, D, Gp(c.L(l, y.proj_w)), D, D, M, dt, w.slab, SLAB_FLOATS(*d)));
-        RMCL_TRY(rmcl_colsum(dxT_b, D, dt, Gp(c.L(l, y.proj_b)), M, D, cs.s));
-      }
-      RMCL_TRY(gemm_dw(cs, dqkv, 3 * D, ls.ln1, D, Gp(c.L(l, y.qkv_w)), 3 * D, D, M, dt, w.slab, SLAB_FLOATS(*d)));
-      RMCL_TRY(rmcl_colsum(dqkv, 3 * D, dt, Gp(c.L(l, y.qkv_b)), M, 3 * D, cs.s));
-      if (use_side) HIP_TRY(hipEventRecord(EV(2, l), cs.s));
+    if (per_gemm) {
+      if (use_side) { HIP_TRY(hipEventRecord(ev_slot(EV_FORK, 2 * l + 1), s)); HIP_TRY(hipStreamWaitEvent(cs.s, ev_slot(EV_FORK, 2 * l + 1), 0)); }
+      if (!tail_l) RMCL_TRY(dw(dxT_b, ls.ao, y.proj_w, y.proj_b, D, D));
+      RMCL_TRY(dw_qkv());
+      if (use_side) HIP_TRY(hipEventRecord(ev_slot(EV_SIDE_DONE, l), cs.s));
     }
-    {
-      GemmArgs g = gemm_args(dqkv, WT ? WTp(c.L(l, y.qkv_w)) : c.W(c.L(l, y.qkv_w)), w.dln, M, D, 3 * D, 3 * D, WT ? 3 * D : D, D);   // dln1 = dqkv Wqkv
-      g.tag = GEMM_TAG_DX;
-      RMCL_TRY(gemm(c, g, dt, dln_dt, 1, WT ? 1 : 0));
-    }
-    if (use_side && !grouped) HIP_TRY(hipStreamWaitEvent(s, EV(1, l), 0));                 // T[ic] free again
+    RMCL_TRY(gemm(c, sites.qkv(l, dqkv, w.dln), dt, dln_dt, 1, sites.b_kc()));
+    if (use_side && !grouped) HIP_TRY(hipStreamWaitEvent(s, ev_slot(EV_MLP_DONE, l), 0));             // T[ic] free again
     RMCL_TRY(rmcl_ln_bwd_lp(w.dln, D, dln_dt, ls.x_in, D, ls.mean1, ls.rstd1, c.V(c.L(l, y.ln1_w)), c.V(c.L(l, y.ln1_b)), w.dx, D, 1,
                             full ? Gp(c.L(l, y.ln1_w)) : nullptr, full ? Gp(c.L(l, y.ln1_b)) : nullptr, M, D, 0, T[ic], dt,
-                            rmcl_site_seed(drop_seed, l - 1, DROP_SITE_FC2), l > 0 ? dth : 0u, dinv, tail_l ? nullptr : rep_slot(2 + 2 * l), s));
+                            drop.site(l - 1, DROP_SITE_FC2), l > 0 ? drop.thresh : 0u, drop.inv_keep, tail_l ? nullptr : rep_slot(2 + 2 * l), s));
     cur = ic;
-    // EV(3, l): everything of layer l that runs on the main stream is enqueued (with the grouped launch on the SAME stream that
+    // EV_MAIN_DONE: everything of layer l that runs on the main stream is enqueued (with the grouped launch on the SAME stream that
     // includes the launch, recorded below)
-    if (full && (use_side || !grouped)) HIP_TRY(hipEventRecord(EV(3, l), s));
-    if (grouped && tail_l) {
-      // tail layer: fc2 / fc1 / proj gradients were formed from the B cls rows above; only qkv reduces over all tokens
-      if (use_side) HIP_TRY(hipStreamWaitEvent(cs.s, EV(3, l), 0));
-      RMCL_TRY(gemm_dw(cs, dqkv, 3 * D, ls.ln1, D, Gp(c.L(l, y.qkv_w)), 3 * D, D, M, dt, w.slab, SLAB_FLOATS(*d)));
-      RMCL_TRY(rmcl_colsum(dqkv, 3 * D, dt, Gp(c.L(l, y.qkv_b)), M, 3 * D, cs.s));
-      HIP_TRY(hipEventRecord(EV(use_side ? 2 : 3, l), cs.s));
-    } else if (grouped) {
+    if (full && (use_side || !grouped)) HIP_TRY(hipEventRecord(ev_slot(EV_MAIN_DONE, l), s));
+    if (grouped) {
       // everything the layer's weight gradients read is final: both dx copies, du, dqkv, the stash, the LN replicas
-      if (use_side) HIP_TRY(hipStreamWaitEvent(cs.s, EV(3, l), 0));
-      DwGroupArgs a{};
-      const void* As[4] = {dxT, du, dxT_b, dqkv};                                          // dY of fc2, fc1, proj, qkv
-      const void* Bs[4] = {ls.h, ls.ln2, ls.ao, ls.ln1};                                   // their inputs X
-      const int64_t wo[4] = {y.fc2_w, y.fc1_w, y.proj_w, y.qkv_w}, bo[4] = {y.fc2_b, y.fc1_b, y.proj_b, y.qkv_b};
-      const int nout[4] = {D, mlp, D, 3 * D}, kin[4] = {mlp, D, D, D};
-      a.tile_base[0] = 0;
-      for (int q = 0; q < 4; ++q) {
-        a.A[q] = (const unsigned short*)As[q]; a.B[q] = (const unsigned short*)Bs[q];
-        a.C[q] = Gp(c.L(l, wo[q])); a.bias[q] = Gp(c.L(l, bo[q]));
-        a.lda[q] = nout[q]; a.ldb[q] = kin[q]; a.ldc[q] = kin[q]; a.tiles_n[q] = kin[q] / 192;
-        a.tile_base[q + 1] = a.tile_base[q] + (nout[q] / 192) * (kin[q] / 192);
+      if (use_side) HIP_TRY(hipStreamWaitEvent(cs.s, ev_slot(EV_MAIN_DONE, l), 0));
+      if (tail_l) {
+        // tail layer: fc2 / fc1 / proj gradients were formed from the B cls rows (backward_tail); only qkv reduces over all tokens
+        RMCL_TRY(dw_qkv());
+      } else {
+        DwGroupArgs a{};
+        const void* As[4] = {dxT, du, dxT_b, dqkv};                                          // dY of fc2, fc1, proj, qkv
+        const void* Bs[4] = {ls.h, ls.ln2, ls.ao, ls.ln1};                                   // their inputs X
+        const int64_t wo[4] = {y.fc2_w, y.fc1_w, y.proj_w, y.qkv_w}, bo[4] = {y.fc2_b, y.fc1_b, y.proj_b, y.qkv_b};
+        const int nout[4] = {D, mlp, D, 3 * D}, kin[4] = {mlp, D, D, D};
+        a.tile_base[0] = 0;
+        for (int q = 0; q < 4; ++q) {
+          a.A[q] = (const unsigned short*)As[q]; a.B[q] = (const unsigned short*)Bs[q];
+          a.C[q] = Gp(c.L(l, wo[q])); a.bias[q] = Gp(c.L(l, bo[q]));
+          a.lda[q] = nout[q]; a.ldb[q] = kin[q]; a.ldc[q] = kin[q]; a.tiles_n[q] = kin[q] / 192;
+          a.tile_base[q + 1] = a.tile_base[q] + (nout[q] / 192) * (kin[q] / 192);
+        }
+        a.K = M;
+        a.rep = w.ln_rep; a.G = G; a.D = D;
+        a.nslots = 0;
+        auto add_slot = [&](int idx, int64_t gw, int64_t gb) { a.slot[a.nslots] = idx; a.g_gamma[a.nslots] = gw; a.g_beta[a.nslots] = gb; ++a.nslots; };
+        add_slot(1 + 2 * l, c.L(l, y.ln2_w), c.L(l, y.ln2_b));
+        add_slot(2 + 2 * l, c.L(l, y.ln1_w), c.L(l, y.ln1_b));
+        if (l == Lr - 1) add_slot(0, y.norm_w, y.norm_b);
+        RMCL_TRY(rmcl_launch_dw_group(a, cs.s));
       }
-      a.K = M;
-      a.rep = w.ln_rep; a.G = G; a.D = D;
-      a.nslots = 0;
-      auto add_slot = [&](int idx, int64_t gw, int64_t gb) { a.slot[a.nslots] = idx; a.g_gamma[a.nslots] = gw; a.g_beta[a.nslots] = gb; ++a.nslots; };
-      add_slot(1 + 2 * l, c.L(l, y.ln2_w), c.L(l, y.ln2_b));
-      add_slot(2 + 2 * l, c.L(l, y.ln1_w), c.L(l, y.ln1_b));
-      if (l == Lr - 1) add_slot(0, y.norm_w, y.norm_b);
-      RMCL_TRY(rmcl_launch_dw_group(a, cs.s));
-      HIP_TRY(hipEventRecord(EV(use_side ? 2 : 3, l), cs.s));
+      HIP_TRY(hipEventRecord(ev_slot(use_side ? EV_SIDE_DONE : EV_MAIN_DONE, l), cs.s));
     }
   }
   if (full) { g_grad_layers = Lr; g_grad_side = use_side; }
-  if (use_side) HIP_TRY(hipStreamWaitEvent(s, EV(2, 0), 0));                               // join: all side work done
+  if (use_side) HIP_TRY(hipStreamWaitEvent(s, ev_slot(EV_SIDE_DONE, 0), 0));                 // join: all side work done
 
   // ---- embeddings ----
   RMCL_TRY(rmcl_image_assemble_bwd(w.dx, w.dpe, dt, full ? Gp(y.pos_img) : nullptr, full ? Gp(y.cls) : nullptr,
                                    full ? Gp(y.vtype) + (d->img_type == 2 ? 2 : 1) * D : nullptr, B, P, L, N, D,
-                                   rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, (ragged && full) ? ragged->dpos_tok : nullptr,
+                                   drop.site(0, DROP_SITE_IMAGE), drop.thresh, drop.inv_keep, (ragged && full) ? ragged->dpos_tok : nullptr,
                                    d->img_type == -1 ? 1 : 0, s));
   // the replaced patches' gradient goes to the mask token; their dpe rows are zeroed BEFORE dpatches, the patch-weight gradient and the
   // patch-bias column sum read them
   if (replaced)
     RMCL_TRY(rmcl_mask_token_bwd(w.dx, w.dpe, dt, replaced, full ? Gp(mask_token_off) : nullptr, w.dln /* free until the text rows */, B, P, L, N, D,
-                                 rmcl_site_seed(drop_seed, 0, DROP_SITE_IMAGE), dth, dinv, s));
+                                 drop.site(0, DROP_SITE_IMAGE), drop.thresh, drop.inv_keep, s));
   if (ragged && full)                                          // position-table gradient through the per-sample resize
     RMCL_TRY(rmcl_pos_resize_bwd(ragged->dpos_tok, ragged->sel, ragged->counts, ragged->hw, ragged->sel_ld, ragged->gw, ragged->G0, B, P, D,
                                  Gp(y.pos_img), s));
@@ -996,17 +1035,14 @@ static int encoder_backward_impl(const rmcl_dims* d, int mode, const float* para
     GemmArgs g = gemm_args(w.dpe, c.W(y.patch_w), dpatches, B * P, d->patch_k, D, D, d->patch_k, d->patch_k);
     RMCL_TRY(gemm(c, g, dt, dt, 1, 0));
   }
-  if (full) {
-    RMCL_TRY(gemm_dw(c, w.dpe, D, patches, d->patch_k, Gp(y.patch_w), D, d->patch_k, B * P, dt, w.slab, SLAB_FLOATS(*d)));
-    RMCL_TRY(rmcl_colsum(w.dpe, D, dt, Gp(y.patch_b), B * P, D, s));
-  }
+  if (full) RMCL_TRY(linear_dw(c, w, w.dpe, patches, Gp(y.patch_w), Gp(y.patch_b), D, d->patch_k, B * P));
   if (full || dtext) {
     // text rows: x[b*N+t] = LN(e) + vtype[0];  de = gradient wrt the embedding sum e, i.e. wrt the output of
     // word_embeddings (the tensor the reference's saliency hook captures, greedy_attack_vilt.py:414-452)
     float* de = dtext ? dtext : w.de;
     RMCL_TRY(rmcl_gather_rows(w.dx, w.dln, B * L, D, L, N, 0, s));
     if (full) RMCL_TRY(rmcl_colsum(w.dln, D, RMCL_F32, Gp(y.vtype), B * L, D, s));
-    RMCL_TRY(rmcl_dropout_apply(w.dln, (long)B * L * D, rmcl_site_seed(drop_seed, 0, DROP_SITE_TEXT), dth, dinv, s));
+    RMCL_TRY(rmcl_dropout_apply(w.dln, (long)B * L * D, drop.site(0, DROP_SITE_TEXT), drop.thresh, drop.inv_keep, s));
     RMCL_TRY(rmcl_ln_bwd(w.dln, D, RMCL_F32, st.text_e, D, st.text_mean, st.text_rstd, c.V(y.eln_w), c.V(y.eln_b), de, D, 0,
                          full ? Gp(y.eln_w) : nullptr, full ? Gp(y.eln_b) : nullptr, B * L, D, 0, s));
     if (full) RMCL_TRY(rmcl_text_embed_scatter((const long*)text_ids, de, Gp(y.word), Gp(y.pos), Gp(y.btype), B, L, D, 0, s));

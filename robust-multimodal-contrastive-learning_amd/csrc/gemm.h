@@ -96,6 +96,14 @@ struct GemmArgs {
 };
 
 #ifdef __cplusplus
+// a plain GEMM (alpha 1, no epilogue, one batch, no split-K): what every host-side caller starts from
+inline GemmArgs gemm_args(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc) {
+  GemmArgs g{};
+  g.A = A; g.B = B; g.C = C;
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.alpha = 1.0f; g.splitk = 1; g.nb1 = 1; g.nb2 = 1;
+  return g;
+}
 // EPI_PREACT_TILED: the ONE place the layout is defined (store: fc1's epilogue, load: fc2-dX's epilogue; gemm_sw.hip).
 // Element offset inside a tile's block of the four bf16 values of accumulator fragment acc[ch * 3 + il][hb * 3 + j] of (wave, lane):
 // a wave's store / load instruction of one fragment covers one contiguous, fully used 512-byte span (8 bytes per lane); the nine

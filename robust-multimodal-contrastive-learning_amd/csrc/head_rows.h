@@ -120,9 +120,7 @@ __device__ __forceinline__ void block_tree_sum2(float (&red)[2][256], float a, f
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
 // a plain GEMM (alpha 1, no split, no batch) of profiling class `tag`; the caller adds its epilogue
 static inline GemmArgs head_gemm(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, int ldc, int tag) {
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = 1.f; g.splitk = 1; g.nb1 = 1; g.nb2 = 1;
+  GemmArgs g = gemm_args(A, B, C, M, N, K, lda, ldb, ldc);
   g.tag = tag;
   return g;
 }

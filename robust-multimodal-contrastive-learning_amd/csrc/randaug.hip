@@ -249,15 +249,13 @@ int rmcl_randaug(const unsigned char* src, const int* sizes, int B, int Hs, int 
   unsigned char* tab_d = reinterpret_cast<unsigned char*>(base + (size_t)B * RA_STAT_WORDS * 4);
   double* par_d = reinterpret_cast<double*>(base + (size_t)B * (RA_STAT_WORDS * 4 + RA_TABLE_BYTES));
   int* ops_d = reinterpret_cast<int*>(par_d + (size_t)B * n_ops * 6);
-  hipError_t e = hipMemcpyAsync(par_d, params_host, (size_t)B * n_ops * 6 * sizeof(double), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ops_d, ops_host, (size_t)B * n_ops * sizeof(int), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+  HIP_TRY(hipMemcpyAsync(par_d, params_host, (size_t)B * n_ops * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ops_d, ops_host, (size_t)B * n_ops * sizeof(int), hipMemcpyHostToDevice, s));
   const unsigned char* in = src;
   for (int stage = 0; stage < n_ops; ++stage) {
     unsigned char* out = (n_ops - 1 - stage) % 2 == 0 ? dst : tmp;
     if (stats[stage]) {
-      e = hipMemsetAsync(st_d, 0, (size_t)B * RA_STAT_WORDS * 4, s);
-      if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+      HIP_TRY(hipMemsetAsync(st_d, 0, (size_t)B * RA_STAT_WORDS * 4, s));
       RMCL_LAUNCH(randaug_stats_kernel, dim3(cdiv(Hs, RA_STAT_ROWS), B), dim3(256), 0, s, in, sizes, ops_d, n_ops, stage, Hs, Ws, st_d);
       RMCL_CHECK_LAUNCH();
     }

@@ -335,4 +335,7 @@ static inline int rmcl_set_max_lds(RmclLdsOnce& o, const void* fn, int bytes) {
     if (_r != 0) return _r;                                   \
   } while (0)
 
+// the same for a HIP runtime call: its status goes to rmcl_last_error and out as the return code
+#define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { rmcl_set_error(hipGetErrorString(_e)); return (int)_e; } } while (0)
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -257,8 +257,7 @@ int rmcl_vqa_head_forward(const rmcl_vqa_head* h, const float* params, const flo
   hipStream_t s = (hipStream_t)stream;
   VqaStash st;
   carve(*h, B, stash, &st);
-  hipError_t e = hipMemcpyAsync(st.x0, cls, (size_t)B * h->D * 4, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) { rmcl_set_error(hipGetErrorString(e)); return (int)e; }
+  HIP_TRY(hipMemcpyAsync(st.x0, cls, (size_t)B * h->D * 4, hipMemcpyDeviceToDevice, s));
   GemmArgs g0 = head_gemm(st.x0, params + h->w0, st.h, B, h->H, h->D, h->D, h->D, h->H, GEMM_TAG_HEAD);              // h = cls W0^T + b0
   g0.epi = EPI_BIAS;
   g0.bias = params + h->b0;

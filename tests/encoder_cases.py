@@ -192,17 +192,20 @@ def keys_of(mode):
 BF16_VARIANTS = {"J:data": ("J", "data", {}), "J:full": ("J", "full", {}), "K:infer:fold_given": ("K", "infer", {}),
                  "K:data:fold_given": ("K", "data", {}), "K:infer:fold60": ("K", "infer", {"fold": True}), "K:data:fold60": ("K", "data", {"fold": True}),
                  "K2:infer:fold60": ("K2", "infer", {"fold": True}), "K2:data:fold60": ("K2", "data", {"fold": True}), "K:full": ("K", "full", {}), "L4:full": ("L4", "full", {}),
-                 "L3:full": ("L3", "full", {})}
+                 "L3:full": ("L3", "full", {}),
+                 # the cls-only tail: dxn on the cls rows, xn compared on them (tail = True: the model's switch, tests/encoder_ref.py)
+                 "J:cls_tail:data": ("J", "data", {"tail": True}), "L4:cls_tail:full": ("L4", "full", {"tail": True})}
 
 
 def model_figures(label):
     """{block: worst-row deviation of the rounding model from float64} of a bf16 variant, on the CPU."""
     name, mode, extra = BF16_VARIANTS[label]
-    c, dk = get_case(name), (None if mode == "infer" else "full")
+    tail = bool(extra.get("tail"))
+    c, dk = get_case(name), (None if mode == "infer" else "cls" if tail else "full")
     ref = reference(name, "f64", dk, **extra)
     G0 = grad_start(c, ref) if mode == "full" else None
     keys = keys_of(MODES[mode])
-    rb, mb = blocks(c, pick(ref, keys)), blocks(c, pick(reference(name, "model", dk, **extra), keys), G0)
+    rb, mb = blocks(c, pick(ref, keys), None, tail), blocks(c, pick(reference(name, "model", dk, **extra), keys), G0, tail)
     return {b: row_err(mb[b], rb[b]) for b in rb}
 
 
@@ -311,5 +314,28 @@ MODEL_MEASURED = {
         "G:transformer.norm.bias": 1.00e-07, "G:transformer.norm.weight": 3.38e-03, "G:transformer.patch_embed.proj.bias": 4.93e-03,
         "G:transformer.patch_embed.proj.weight": 6.63e-03, "G:transformer.pos_embed": 5.71e-03, "dpatches": 6.67e-03, "dtext": 2.27e-03,
         "xn_image": 4.95e-03, "xn_text": 1.07e-03},
+    "J:cls_tail:data": {
+        "dpatches": 5.69e-03, "dtext": 9.41e-04, "xn_cls": 1.67e-04},
+    "L4:cls_tail:full": {
+        "G:itm_score.fc.bias": 0.00e+00, "G:itm_score.fc.weight": 0.00e+00, "G:moco_head.projector.0.bias": 0.00e+00,
+        "G:moco_head.projector.0.weight": 0.00e+00, "G:moco_head.projector.1.bias": 0.00e+00, "G:moco_head.projector.1.weight": 0.00e+00,
+        "G:moco_head.projector.3.weight": 0.00e+00, "G:pooler.dense.bias": 0.00e+00, "G:pooler.dense.weight": 0.00e+00,
+        "G:text_embeddings.LayerNorm.bias": 8.82e-04, "G:text_embeddings.LayerNorm.weight": 8.23e-04,
+        "G:text_embeddings.position_embeddings.weight": 3.41e-03, "G:text_embeddings.token_type_embeddings.weight": 8.78e-04,
+        "G:text_embeddings.word_embeddings.weight": 4.82e-03, "G:token_type_embeddings.weight": 3.63e-03,
+        "G:transformer.blocks.0.attn.proj.bias": 2.65e-03, "G:transformer.blocks.0.attn.proj.weight": 3.03e-02,
+        "G:transformer.blocks.0.attn.qkv.bias": 3.14e-03, "G:transformer.blocks.0.attn.qkv.weight": 4.33e-02,
+        "G:transformer.blocks.0.mlp.fc1.bias": 3.29e-03, "G:transformer.blocks.0.mlp.fc1.weight": 3.17e-02,
+        "G:transformer.blocks.0.mlp.fc2.bias": 2.07e-03, "G:transformer.blocks.0.mlp.fc2.weight": 1.14e-02,
+        "G:transformer.blocks.0.norm1.bias": 3.62e-03, "G:transformer.blocks.0.norm1.weight": 3.99e-03, "G:transformer.blocks.0.norm2.bias": 4.07e-03,
+        "G:transformer.blocks.0.norm2.weight": 4.05e-03, "G:transformer.blocks.1.attn.proj.bias": 8.30e-05,
+        "G:transformer.blocks.1.attn.proj.weight": 5.88e-03, "G:transformer.blocks.1.attn.qkv.bias": 1.72e-03,
+        "G:transformer.blocks.1.attn.qkv.weight": 6.30e-02, "G:transformer.blocks.1.mlp.fc1.bias": 4.08e-04,
+        "G:transformer.blocks.1.mlp.fc1.weight": 1.00e-02, "G:transformer.blocks.1.mlp.fc2.bias": 3.59e-05,
+        "G:transformer.blocks.1.mlp.fc2.weight": 1.33e-03, "G:transformer.blocks.1.norm1.bias": 2.42e-03,
+        "G:transformer.blocks.1.norm1.weight": 3.75e-03, "G:transformer.blocks.1.norm2.bias": 3.92e-04,
+        "G:transformer.blocks.1.norm2.weight": 8.22e-04, "G:transformer.cls_token": 4.81e-03, "G:transformer.norm.bias": 6.01e-08,
+        "G:transformer.norm.weight": 7.75e-04, "G:transformer.patch_embed.proj.bias": 3.61e-03, "G:transformer.patch_embed.proj.weight": 1.37e-02,
+        "G:transformer.pos_embed": 5.04e-03, "dpatches": 6.56e-03, "dtext": 3.83e-03, "xn_cls": 7.88e-04},
 }
 MODEL_CAPS = {label: {b: 2.0 * v for b, v in fig.items()} for label, fig in MODEL_MEASURED.items()}

@@ -27,7 +27,11 @@ encoder.cpp stores a tensor in the operand type (LayerStash, Work and the backwa
 fold = True adds the LayerNorm fold of INFER / DATA passes (rmcl_ln_fold: W' = bf16(W gamma) from the fp32 masters, s = rowsum(W'),
 c = W beta + b): y = rstd (bf16(x - centre) W'^T - mean(x - centre) s) + c for fc1 of every layer (centre = LN1's row mean) and qkv of the
 layers after the first (centre = the previous LN2's row mean); its VALUE replaces the plain form's, the backward is the plain form's
-(encoder_backward reads x_in / x_mid and the statistics from the stash and the unfolded bf16 weights)."""
+(encoder_backward reads x_in / x_mid and the statistics from the stash and the unfolded bf16 weights).
+tail = True is the cls-only tail (RMCL_MODE_CLS_TAIL, backward cls_only = 2): behind the attention of the LAST block the kernel works on the cls
+rows alone, in fp32 on the fp32 master weights (exact skinny GEMMs; compact fp32 x_mid, ln2, u, h) - the model drops every rounding there, on
+all rows: the block is row-wise behind the attention, only the cls rows of xn are compared and only they carry a gradient.  What stays rounded
+is what the kernel still rounds: the attention output (bf16 stash) and its gradient (Work.dao is scatter-cast to the operand type)."""
 import math
 import types
 
@@ -195,8 +199,9 @@ def _fold_linear(x, ctr, gamma, beta, W32, bias, eps):
     return rstd * (bf(z) @ Wf.t() - mu * Wf.sum(1)) + (W32 @ beta + bias)
 
 
-def _model_block(p, b, x, mask, H, drop, fold, ctr_prev):
-    """One block with the roundings of the docstring.  Returns (x_out, the LayerNorm-2 row means: the next layer's fold centre)."""
+def _model_block(p, b, x, mask, H, drop, fold, ctr_prev, tail=False):
+    """One block with the roundings of the docstring.  Returns (x_out, the LayerNorm-2 row means: the next layer's fold centre).
+    tail: the block behind its attention in fp32 on the master weights (the cls-only tail)."""
     d = drop or {}
     W = lambda n: p[b + n] + (bf(p[b + n]) - p[b + n]).detach()
     m1 = x.mean(-1)
@@ -206,6 +211,13 @@ def _model_block(p, b, x, mask, H, drop, fold, ctr_prev):
         yf = _fold_linear(x, ctr_prev, p[b + "norm1.weight"], p[b + "norm1.bias"], p[b + "attn.qkv.weight"], p[b + "attn.qkv.bias"], 1e-6)
         y = y + (yf - y).detach()
     ao = _AttnModel.apply(q(y), mask, H)
+    if tail:
+        a = ao @ p[b + "attn.proj.weight"].t() + p[b + "attn.proj.bias"]
+        x_mid = x + (a * d["proj"] if "proj" in d else a)
+        ln2 = O.layer_norm(x_mid, p[b + "norm2.weight"], p[b + "norm2.bias"], 1e-6)
+        h = O.gelu_erf(ln2 @ p[b + "mlp.fc1.weight"].t() + p[b + "mlp.fc1.bias"])
+        o = (h * d["hidden"] if "hidden" in d else h) @ p[b + "mlp.fc2.weight"].t() + p[b + "mlp.fc2.bias"]
+        return x_mid + (o * d["fc2"] if "fc2" in d else o), x_mid.mean(-1).detach()
     a = qg(ao @ W("attn.proj.weight").t() + p[b + "attn.proj.bias"])
     x_mid = x + (a * d["proj"] if "proj" in d else a)
     m2 = x_mid.mean(-1)
@@ -221,7 +233,7 @@ def _model_block(p, b, x, mask, H, drop, fold, ctr_prev):
 
 
 def encoder_ref(arena, specs, dims, text_ids, text_mask, patches, ragged=None, replaced=None, mask_token=None, drop=None, img_type=None,
-                img_of=None, model=False, fold=False, word_embeds=None, parts=None):
+                img_of=None, model=False, fold=False, tail=False, word_embeds=None, parts=None):
     """xn [B, N, D] and co_mask [B, N] (int32) of the pass.  patches [Bi * P, patch_k] (bf16 values on a bf16 arm); ragged: dict(sel, counts, hw,
     gw, G0) of CPU tensors; replaced [Bi, P] with mask_token = the NAME of the [D] arena slot that holds the mask token (the _mpp forms); drop: {"text", "image", layer: {"proj", "hidden", "fc2"}}
     scale masks; img_type: rmcl_dims.img_type (default dims.img_type); img_of [B]: the rank pass - the Bi images are a cache and sequence b
@@ -272,7 +284,7 @@ def encoder_ref(arena, specs, dims, text_ids, text_mask, patches, ragged=None, r
     for l in range(dims.layers):
         b = f"transformer.blocks.{l}."
         if model:
-            x, ctr = _model_block(p, b, x, co, H, drop.get(l), fold, ctr)
+            x, ctr = _model_block(p, b, x, co, H, drop.get(l), fold, ctr, tail and l + 1 == dims.layers)
         else:
             x = O.block(p, b, x, co, H, drop.get(l))
     return O.layer_norm(x, p["transformer.norm.weight"], p["transformer.norm.bias"], 1e-6), co

@@ -24,10 +24,10 @@ mode passes grads32 = NULL; dpatches rows of replaced patches are exactly zero.
 Cases (2 layers, vocab 64, patch_k 192 unless noted; weights as oracle.init_params scales them).  fp32 exact: A D 64 B 3 L 5 P 9 (one sample
 with a single valid token, ids with 0 and duplicates, one all-zero patch) INFER / DATA / FULL; B D 320; C D 1024, 1 layer; D D 128 ragged
 (grids 4x4 permuted, 1x4, 4x1, 2x3 of a 4x4 table); E token-type row 2 and the pair form; F the _mpp forms (replaced: none, some, all);
-G cls_only 1 and RMCL_MODE_CLS_TAIL; H dropout 0.25 with the masks read back; I rmcl_visual_embed + the rank pass.  bf16: J D 128; K D 192
+G cls_only 1 and RMCL_MODE_CLS_TAIL (FULL and DATA); H dropout 0.25 with the masks read back, dense and on the cls tail; I rmcl_visual_embed + the rank pass.  bf16: J D 128; K D 192
 mlp 768 (rmcl_fold given under tune key 0 = 70 in INFER / DATA: tiled pre-activation, the fold is not taken there - the qkv GEMM, N = 576,
 cannot run on the 192x384 kernel; the fold taken under key 0 = 60; FULL under key 70 without the fold); K2 D 384 mlp 768, the fold under key 0 = 60; L D 768 mlp 768 at M = 256 (grouped weight
-gradients) and M = 192 (split-K).
+gradients) and M = 192 (split-K); the cls tail on J (DATA) and on L at M = 256 (FULL: the tail layer beside the grouped launch).
 
 Found by this file: the LayerNorm fold at D = 192 (test_K_bf16_layernorm_fold_taken_at_d192_under_key_60 has the cause and the fix).
 
@@ -56,6 +56,8 @@ PARITY = {}
 
 def compare(label, c, got, dxn_kind, tail=False, G0=None, **extra):
     """Figures of every block against float64, the bound of the arm, the record, then the assertion."""
+    if tail and c.bf16:                          # the yardstick follows the kernel's tail: fp32 behind the last attention (encoder_ref tail = True)
+        extra = dict(extra, tail=True)
     ref = blocks(c, pick(reference(c.name, "f64", dxn_kind, **extra), got), None, tail)
     yard = blocks(c, pick(reference(c.name, "model" if c.bf16 else "f32", dxn_kind, **extra), got), G0, tail)
     mine = blocks(c, got, G0, tail, added=True)
@@ -307,18 +309,29 @@ def test_G_cls_tail():
     check_pass("G:cls_tail", get_case("A"), L.MODE_FULL, dxn_kind="cls", tail=True, cls_only=2)
 
 
-def test_H_dropout_with_the_masks_read_back():
+def test_G_cls_tail_data_mode():
+    check_pass("G:cls_tail:data", get_case("A"), L.MODE_DATA, dxn_kind="cls", tail=True, cls_only=2)
+
+
+def _dropout_full_pass(label, tail):
+    """Case A, FULL, dropout 0.25 against the reference with the masks the library reports.  tail: the forward with RMCL_MODE_CLS_TAIL and the
+    backward with cls_only = 2 - the compact rows draw the dense rows' masks, so the reference is the dense one with the cls-only dxn."""
     c = get_case("A")
     dry = run(c, L.MODE_INFER, drop_p=0.25, masks_of=True)             # the masks are a pure function of (seed, site, element)
     drop = dry["drop"]
     assert any(bool((m == 0).any()) for m in (drop["text"], drop["image"], drop[0]["proj"], drop[1]["hidden"], drop[1]["fc2"]))
     kw = dict(ragged=None, img_of=None, drop=drop)
-    ref = R.grads(c.arena, c.specs, c.dims, c.text_ids, c.text_mask, c.patches, c.dxn, torch.float64, **kw)
-    y32 = R.grads(c.arena, c.specs, c.dims, c.text_ids, c.text_mask, c.patches, c.dxn, torch.float32, **kw)
+    dxn = c.dxn_cls if tail else c.dxn
+    ref = R.grads(c.arena, c.specs, c.dims, c.text_ids, c.text_mask, c.patches, dxn, torch.float64, **kw)
+    y32 = R.grads(c.arena, c.specs, c.dims, c.text_ids, c.text_mask, c.patches, dxn, torch.float32, **kw)
     G0 = grad_start(c, ref)
-    got = run(c, L.MODE_FULL, G0=G0, dxn=c.dxn.reshape(-1, c.dims.D), drop_p=0.25)
+    if tail:
+        got = run(c, L.MODE_FULL, G0=G0, dxn=c.dxn[:, 0], tail=True, cls_only=2, drop_p=0.25)
+    else:
+        got = run(c, L.MODE_FULL, G0=G0, dxn=c.dxn.reshape(-1, c.dims.D), drop_p=0.25)
     assert torch.equal(got["co"], ref["co"])
-    rb, yb, mb = blocks(c, ref), blocks(c, y32, G0), blocks(c, {k: got[k] for k in ("xn", "dpatches", "dtext", "G")}, G0, added=True)
+    rb, yb = blocks(c, ref, None, tail), blocks(c, y32, G0, tail)
+    mb = blocks(c, {k: got[k] for k in ("xn", "dpatches", "dtext", "G")}, G0, tail, added=True)
     rec, bad = {}, []
     for b in sorted(rb):
         assert bool(torch.isfinite(mb[b]).all()), b
@@ -326,12 +339,20 @@ def test_H_dropout_with_the_masks_read_back():
         rec[b] = {"kernel": e, "e32": y, "allowed": F32_FACTOR * max(y, F32_FLOOR)}
         if not e <= rec[b]["allowed"]:
             bad.append(f"{b}: {e:.3e} > {rec[b]['allowed']:.3e}")
-    PARITY["H:dropout"] = rec
+    PARITY[label] = rec
     assert not bad, "; ".join(bad)
 
 
-def test_I_visual_embed_cache_and_rank_pass():
-    c = get_case("I")
+def test_H_dropout_with_the_masks_read_back():
+    _dropout_full_pass("H:dropout", tail=False)
+
+
+def test_H_dropout_on_the_cls_tail():
+    _dropout_full_pass("H:dropout:cls_tail", tail=True)
+
+
+def run_rank(c):
+    """rmcl_visual_embed into a cache, then the rank pass over it, under the contract of the docstring.  Returns CPU tensors."""
     d, cd = c.dims, c.cd
     B, Pn, D, Lt, N, Bt = d.B, d.P, d.D, d.L, c.N, c.Bt
     ld_tok = Pn + 4
@@ -360,26 +381,41 @@ def test_I_visual_embed_cache_and_rank_pass():
     assert ws.intact() and ws2.intact()
     for a, b in zip((p32, pat, cache, cmask, ids, tm, img_of), keep):
         assert torch.equal(bits(a), bits(b))
+    assert bool(torch.isfinite(emb).all())
+    return {"emb": emb.cpu(), "msk": msk.cpu(), "xn": xn.cpu().view(Bt, N, D), "co": co.cpu()}
+
+
+def test_I_visual_embed_cache_and_rank_pass():
+    c = get_case("I")
+    d = c.dims
+    B, D, Lt = d.B, d.D, d.L
+    got = run_rank(c)
+    emb, msk, xn, co = got["emb"], got["msk"], got["xn"], got["co"]
     parts = {}
     R.encoder_ref(c.arena.double(), c.specs, d, c.text_ids, c.text_mask, c.patches.double(), ragged=c.ragged, img_of=c.rank, parts=parts)
     p32_parts = {}
     R.encoder_ref(c.arena, c.specs, d, c.text_ids, c.text_mask, c.patches, ragged=c.ragged, img_of=c.rank, parts=p32_parts)
-    assert torch.equal(msk.cpu(), parts["visual_mask"])
-    e = row_err(emb.cpu().reshape(-1, D), parts["visual"].reshape(-1, D))
+    assert torch.equal(msk, parts["visual_mask"])
+    e = row_err(emb.reshape(-1, D), parts["visual"].reshape(-1, D))
     y = row_err(p32_parts["visual"].reshape(-1, D), parts["visual"].reshape(-1, D))
     PARITY["I:visual_embed"] = {"visual": {"kernel": e, "e32": y, "allowed": F32_FACTOR * max(y, F32_FLOOR)}}
-    assert bool(torch.isfinite(emb).all()) and e <= F32_FACTOR * max(y, F32_FLOOR), (e, y)
+    assert e <= F32_FACTOR * max(y, F32_FLOOR), (e, y)
     ref = reference("I", "f64", None)
-    assert torch.equal(co.cpu(), ref["co"])
+    assert torch.equal(co, ref["co"])
     missing = [b for b, i in enumerate(c.rank) if not 0 <= i < B]
-    assert not bool(co.cpu()[missing, Lt:].any())
-    compare("I:rank", c, {"xn": xn.cpu().view(Bt, N, D)}, None)
+    assert not bool(co[missing, Lt:].any())
+    compare("I:rank", c, {"xn": xn}, None)
 
 
 # ------------------------------------------------------------------------------------------ bf16 arms
 @pytest.mark.parametrize("mode", ["data", "full"])
 def test_J_bf16_generic_small_route(mode):
     check_pass(f"J:{mode}", get_case("J"), MODES[mode])
+
+
+def test_J_bf16_cls_tail_data_mode():
+    """The bf16 cls-row gather (or the in-place bf16 read of the streaming skinny kernel) and the scatter-cast of d(attention output)."""
+    check_pass("J:cls_tail:data", get_case("J"), L.MODE_DATA, dxn_kind="cls", tail=True, cls_only=2)
 
 
 def _same_xn(a, b):
@@ -440,3 +476,9 @@ def test_L_bf16_d768_grouped_and_split_k_weight_gradients(name):
     M = c.dims.B * c.N
     assert (M % 64 == 0 and M >= 256) == (name == "L4")
     check_pass(f"{name}:full", c, L.MODE_FULL, lpT=True)
+
+
+def test_L4_bf16_cls_tail_with_grouped_weight_gradients():
+    """M = 256: the grouped weight-gradient launch for the first layer; the tail layer forms fc2 / fc1 / proj gradients from the B cls rows and
+    only its qkv gradient reduces over all tokens (encoder_backward_impl, the grouped branch of the tail layer)."""
+    check_pass("L4:cls_tail:full", get_case("L4"), L.MODE_FULL, dxn_kind="cls", tail=True, cls_only=2, lpT=True)

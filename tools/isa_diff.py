@@ -10,7 +10,9 @@ Each file is compiled in each tree with the flags of the ISA tests (tests/test_i
   * fp: the histogram of the floating-point instructions (v_fma* v_fmac* v_mul_f* v_add_f* v_sub_f* v_pk_* v_mfma* v_exp* v_rcp*
     v_sqrt*), before and after - with -ffp-contract=fast this is what shows a changed contraction, i.e. changed bits.
 Nothing else of the assembly is looked at.  Conditions (exit status 1 if one fails): same kernels on both sides, fp histogram equal,
-scratch not larger, VGPRs in the same allocation granule (8 registers) or lower; for files after --identical, identical assembly."""
+scratch not larger, VGPRs in the same allocation granule (8 registers) or lower; for files after --identical, identical assembly.
+--brief keeps the report small: a kernel whose assembly is identical is counted per file (kernels, identical, instructions), not listed;
+every other kernel is reported in full."""
 import argparse
 import json
 import os
@@ -65,6 +67,7 @@ def main():
     ap.add_argument("--after", required=True)
     ap.add_argument("--out")
     ap.add_argument("--identical", nargs="*", default=[], help="files whose assembly must not change at all")
+    ap.add_argument("--brief", action="store_true", help="count identical kernels per file instead of listing them")
     ap.add_argument("-j", type=int, default=8)
     ap.add_argument("files", nargs="+")
     a = ap.parse_args()
@@ -101,6 +104,10 @@ def main():
         ks = report[f].values()
         print(f"{f}: {len(ks)} kernels, {sum(k['identical'] for k in ks)} identical, {sum(k['fp_equal'] for k in ks)} with an equal fp histogram, "
               f"{sum(k['scratch'][1] > 0 for k in ks)} with scratch")
+    if a.brief:
+        report = {f: {"kernels": len(ks), "identical": sum(k["identical"] for k in ks.values()),
+                      "instructions_of_the_identical": sum(k["instructions"][0] for k in ks.values() if k["identical"]),
+                      "not_identical": {n: k for n, k in ks.items() if not k["identical"]}} for f, ks in report.items()}
     result = {"flags": FLAGS, "vgpr_granule": VGPR_GRANULE, "must_be_identical": a.identical, "conditions_met": not failed, "failed": failed, "files": report}
     if a.out:
         with open(a.out, "w") as fh:
