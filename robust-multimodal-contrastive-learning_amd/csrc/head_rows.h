@@ -1,4 +1,5 @@
-// Row primitives that only the task heads share (vqa.hip, nlvr2.hip, irtr.hip, mlm.hip; barlow.hip takes the host helpers).
+// Row primitives that only the task heads share (vqa.hip, nlvr2.hip, irtr.hip, head_transform.hip, mlm.hip, mpp.hip; barlow.hip takes
+// the host helpers), and the host interface of the prediction-head transform that mlm.hip and mpp.hip call (head_transform.hip).
 // Every piece has a fixed summation order and uses no float atomics: a kernel built from them gives identical bits per call.
 // The kernels keep what is their own - where GELU sits, eps, where gamma / beta are loaded, what is stored; nothing here knows
 // which head calls it.  The encoder's LayerNorm (norm_softmax.hip: left-to-right sums, rsqrtf) and the text embedding's
@@ -134,3 +135,39 @@ struct StashCarver {
     return p;
   }
 };
+
+// ---- the BERT prediction-head transform, Linear(D,D) - GELU - LayerNorm(eps 1e-12) over a compacted row list (head_transform.hip) ------
+#define PRED_ROWS_PER_BLK 16     // rows of one transform-backward workgroup (one partial of dgamma / dbeta / dbias per workgroup)
+struct PredTransform {           // D and the arena offsets of dense.weight [D, D], dense.bias, LayerNorm.weight, LayerNorm.bias
+  int D;
+  long tw, tb, lg, lb;
+};
+struct PredWs {                  // views into the calling head's workspace; h / hT [D, rows] in the decoder's operand type, hT may be NULL
+  float *x, *a, *stat;
+  void *h, *hT;
+  float *dh, *da, *dx, *lnpart;
+};
+static inline bool pred_head_ok(int D) { return D == 256 || D == 768; }
+static inline bool pred_rows_ok(int rows) { return rows >= 128 && rows % 128 == 0 && rows <= (1 << 20); }
+// the two runs of slices every head's workspace holds in this order, with the head's own slices between and behind them
+static inline void pred_carve_fwd(StashCarver& c, int rows, int D, PredWs* w) {
+  const long RD = (long)rows * D;
+  w->x = c.take(RD);
+  w->a = c.take(RD);
+  w->stat = c.take(2L * rows);
+  w->h = c.take(RD);                                        // (T <= 4 bytes)
+  w->hT = nullptr;
+}
+static inline void pred_carve_bwd(StashCarver& c, int rows, int D, PredWs* w) {
+  const long RD = (long)rows * D;
+  w->dh = c.take(RD);
+  w->da = c.take(RD);
+  w->dx = c.take(RD);
+  w->lnpart = c.take((long)cdiv(rows, PRED_ROWS_PER_BLK) * 3 * D);
+}
+// gather xn[idx] into w.x, a = x Wt^T + bt (exact fp32), h (and hT where w.hT is set) = LayerNorm(GELU(a)) in `dtype`, statistics in w.stat
+int pred_transform_forward(const PredTransform& t, const float* params, const float* xn, const int* idx, const int* count, int rows, int dtype,
+                           const PredWs& w, hipStream_t s);
+// from w.dh: da; G != NULL: dgamma / dbeta / dbt and dWt accumulated into G; dxn != NULL: dx = da Wt stored to dxn[idx[r]] (else no dx GEMM)
+int pred_transform_backward(const PredTransform& t, const float* params, const PredWs& w, const int* idx, const int* count, int rows, float* G,
+                            float* dxn, hipStream_t s);

@@ -5,9 +5,8 @@
 // The loss reads only the rows whose label is not -100 (~15 % of B x L), so the training path works on those rows, COMPACTED, and never
 // holds a [rows, V] logits tensor:
 //   compact    one workgroup: ascending list of the rows with a label, their labels, the count n (stays on the device)
-//   gather     x [rows, D] = text rows of xn (rows >= n: zeros, so everything behind them is finite)
-//   transform  a = x Wt^T + bt (exact fp32 GEMM), h = LayerNorm(GELU(a)) in one row pass; h is kept in the decoder's operand type
-//              (bf16 / fp32) twice: [rows, D] and transposed [D, rows]
+//   gather + transform   the prediction-head transform shared with the MPP head (head_transform.hip: pred_transform_forward) on the text
+//              rows of xn; h is kept in the decoder's operand type (bf16 / fp32) twice: [rows, D] and transposed [D, rows]
 //   decoder + CE forward   z = W h^T + bias tile by tile on the matrix cores (32 vocabulary x 32 rows per wave), every lane keeps the
 //              running (max, sum exp, first argmax, label logit) of ONE row; the vocabulary is split over workgroups, the partials per
 //              (vocabulary chunk, row) are merged in chunk order
@@ -16,7 +15,7 @@
 //              * workgroups that own 32 token rows and one vocabulary chunk:    dh_part[chunk][r,:] = sum_v dz[r,v] W[v,:]
 //                (operand W^T [D, V]: a transposed shadow of the decoder weight), then dh = sum over chunks in chunk order
 //              every output element has ONE owner and a fixed summation order: no float atomics anywhere, identical bits per call
-//   transform backward (one row pass + fixed-order partials) and the scatter of dx into the zero-filled dxn of the encoder backward.
+//   transform backward and the scatter of dx into the zero-filled dxn of the encoder backward: pred_transform_backward.
 // Operand type T: bf16 (v_mfma_f32_32x32x16_bf16) or fp32 (v_mfma_f32_32x32x2_f32, the parity engine); accumulation and all softmax
 // statistics are fp32.  V need not be a multiple of the tile: columns >= V are masked to -inf / dz = 0.
 #include <algorithm>
@@ -27,7 +26,6 @@
 
 namespace {
 
-#define MLM_ROWS_PER_BLK 16     // rows of one transform-backward workgroup (one partial of dgamma / dbeta / dbias per workgroup)
 #define MLM_RG 128              // rows (dW kernel) / vocabulary columns (dh kernel) per iteration: one 32 x 32 z tile per wave
 
 typedef __bf16 mbf16x8 __attribute__((ext_vector_type(8)));
@@ -104,146 +102,6 @@ __global__ __launch_bounds__(256) void mlm_compact_kernel(const long* __restrict
   __syncthreads();
   const int n = count[0];
   for (int i = n + t; i < M; i += 256) { idx[i] = -1; lab[i] = -100; }
-}
-
-// x [rows, D] = xn[idx[r]] for r < n, else 0
-__global__ __launch_bounds__(256) void mlm_gather_kernel(const float* __restrict__ xn, const int* __restrict__ idx, const int* __restrict__ count,
-                                                         float* __restrict__ x, int rows, int D) {
-  const int n = count[0], per_row = D / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < (long)rows * per_row; i += (long)gridDim.x * 256) {
-    const int r = (int)(i / per_row), c = (int)(i - (long)r * per_row) * 4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < n) v = *reinterpret_cast<const float4*>(xn + (long)idx[r] * D + c);
-    *reinterpret_cast<float4*>(x + (long)r * D + c) = v;
-  }
-}
-
-// dxn[idx[r]] = dx[r] for r < n (every masked row has exactly one destination; dxn was zero-filled by the caller)
-__global__ __launch_bounds__(256) void mlm_scatter_kernel(const float* __restrict__ dx, const int* __restrict__ idx, const int* __restrict__ count,
-                                                          float* __restrict__ dxn, int rows, int D) {
-  const int n = min(count[0], rows), per_row = D / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < (long)n * per_row; i += (long)gridDim.x * 256) {
-    const int r = (int)(i / per_row), c = (int)(i - (long)r * per_row) * 4;
-    *reinterpret_cast<float4*>(dxn + (long)idx[r] * D + c) = *reinterpret_cast<const float4*>(dx + (long)r * D + c);
-  }
-}
-
-// ---- transform: h = LayerNorm(GELU(a)), eps 1e-12 ---------------------------------------------------------------------------------------
-// One wave per row, D = 256 NV.  h [rows, D] and hT [D, rows] in T; stat[2 row] = (mean, rstd) of GELU(a).
-template <typename T, int NV>
-__global__ __launch_bounds__(256) void mlm_gelu_ln_fwd_kernel(const float* __restrict__ a, const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, T* __restrict__ h, T* __restrict__ hT,
-                                                              float* __restrict__ stat, int rows) {
-  constexpr int D = 256 * NV;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  float4 v[NV];
-  float s = 0.f, mu, rs;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float4 x = *reinterpret_cast<const float4*>(a + (long)row * D + (lane + 64 * i) * 4);
-    v[i] = make_float4(gelu_erf(x.x), gelu_erf(x.y), gelu_erf(x.z), gelu_erf(x.w));
-    s += sum4_pairwise(v[i]);
-  }
-  ln_row_stats<NV>(v, s, 1e-12f, mu, rs);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    const float4 w = *reinterpret_cast<const float4*>(gamma + c), bb = *reinterpret_cast<const float4*>(beta + c);
-    const float o[4] = {(v[i].x - mu) * rs * w.x + bb.x, (v[i].y - mu) * rs * w.y + bb.y, (v[i].z - mu) * rs * w.z + bb.z,
-                        (v[i].w - mu) * rs * w.w + bb.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const T t = from_f32<T>(o[j]);
-      h[(long)row * D + c + j] = t;
-      hT[(long)(c + j) * rows + row] = t;
-    }
-  }
-  if (lane == 0) {
-    stat[2 * row] = mu;
-    stat[2 * row + 1] = rs;
-  }
-}
-
-// da = GELU'(a) * LayerNorm'(dh) per row (GELU(a) and xhat recomputed from a and the stashed statistics).  part[blk][3][D]: this
-// workgroup's sums over its rows of dh * xhat (-> dgamma), dh (-> dbeta) and da (-> the dense bias); the four waves meet in LDS in a fixed order.
-template <int NV>
-__global__ __launch_bounds__(256) void mlm_gelu_ln_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ a,
-                                                              const float* __restrict__ stat, const float* __restrict__ gamma,
-                                                              float* __restrict__ da, float* __restrict__ part, int rows) {
-  constexpr int D = 256 * NV;
-  __shared__ float red[3][D];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float4 w[NV], pg[NV], pb[NV], pa[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    w[i] = *reinterpret_cast<const float4*>(gamma + (lane + 64 * i) * 4);
-    pg[i] = pb[i] = pa[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  const int r0 = blockIdx.x * MLM_ROWS_PER_BLK;
-  for (int r = r0 + wave; r < min(r0 + MLM_ROWS_PER_BLK, rows); r += 4) {
-    const float mu = stat[2 * r], rs = stat[2 * r + 1];
-    float4 xh[NV], dx[NV], av[NV];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (lane + 64 * i) * 4;
-      av[i] = *reinterpret_cast<const float4*>(a + (long)r * D + c);
-      const float4 dy = *reinterpret_cast<const float4*>(dh + (long)r * D + c);
-      xh[i] = make_float4((gelu_erf(av[i].x) - mu) * rs, (gelu_erf(av[i].y) - mu) * rs, (gelu_erf(av[i].z) - mu) * rs,
-                          (gelu_erf(av[i].w) - mu) * rs);
-      ln_bwd_acc(dy, xh[i], w[i], pg[i], pb[i], dx[i], s1, s2);
-    }
-    float m1, m2;
-    ln_bwd_means(s1, s2, D, m1, m2);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (lane + 64 * i) * 4;
-      float4 o;
-      o.x = ln_bwd_dx(dx[i].x, xh[i].x, m1, m2, rs) * gelu_erf_grad(av[i].x);
-      o.y = ln_bwd_dx(dx[i].y, xh[i].y, m1, m2, rs) * gelu_erf_grad(av[i].y);
-      o.z = ln_bwd_dx(dx[i].z, xh[i].z, m1, m2, rs) * gelu_erf_grad(av[i].z);
-      o.w = ln_bwd_dx(dx[i].w, xh[i].w, m1, m2, rs) * gelu_erf_grad(av[i].w);
-      pa[i].x += o.x; pa[i].y += o.y; pa[i].z += o.z; pa[i].w += o.w;
-      *reinterpret_cast<float4*>(da + (long)r * D + c) = o;
-    }
-  }
-  // (this merge stays literal in the kernel - behind a shared helper the row loop above compiles to other bits: DESIGN "Head row primitives")
-  for (int ph = 0; ph < 4; ++ph) {
-    if (wave == ph) {
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        const float x0[4] = {pg[i].x, pg[i].y, pg[i].z, pg[i].w}, x1[4] = {pb[i].x, pb[i].y, pb[i].z, pb[i].w},
-                    x2[4] = {pa[i].x, pa[i].y, pa[i].z, pa[i].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          red[0][c + j] = ph == 0 ? x0[j] : red[0][c + j] + x0[j];
-          red[1][c + j] = ph == 0 ? x1[j] : red[1][c + j] + x1[j];
-          red[2][c + j] = ph == 0 ? x2[j] : red[2][c + j] + x2[j];
-        }
-      }
-    }
-    __syncthreads();
-  }
-  float* out = part + (long)blockIdx.x * 3 * D;
-  for (int c = threadIdx.x; c < 3 * D; c += 256) out[c] = (&red[0][0])[c];
-}
-
-// dgamma[c] += sum_blk part[blk][0][c], dbeta[c] += ...[1][c], dbt[c] += ...[2][c], in workgroup order
-__global__ __launch_bounds__(256) void mlm_param_grad_kernel(const float* __restrict__ part, int nblk, int D, float* __restrict__ dgamma,
-                                                             float* __restrict__ dbeta, float* __restrict__ dbt) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= D) return;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  for (int k = 0; k < nblk; ++k) {
-    s0 += part[(long)k * 3 * D + c];
-    s1 += part[(long)k * 3 * D + D + c];
-    s2 += part[(long)k * 3 * D + 2 * D + c];
-  }
-  dgamma[c] += s0;
-  dbeta[c] += s1;
-  dbt[c] += s2;
 }
 
 // WT [D, ldv] (T) = W^T of the fp32 master W [V, D]; columns V..ldv-1 zero.  32 x 32 tiles through LDS.
@@ -537,12 +395,12 @@ __global__ __launch_bounds__(256) void mlm_logits_kernel(const T* __restrict__ h
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 struct MlmWs {
-  float *x, *a, *stat, *lse_unused, *dh, *da, *dx, *lnpart, *dhp;
-  void *h, *hT;
+  PredWs t;                                                 // the transform's slices (head_rows.h); t.hT: the dW kernel's operand
+  float* dhp;
   float4* part;
   int* parti;
-  int nchunk;
 };
+PredTransform transform_of(const rmcl_mlm_head* h) { return PredTransform{h->D, h->tw, h->tb, h->lg, h->lb}; }
 // vocabulary chunks of the dh kernel: enough workgroups to fill 256 CUs twice at the usual ~384 rows (12 row tiles x 32), fewer when the
 // row tiles alone do that (the slab costs chunks x rows x D x 4 bytes written and read once)
 int h_chunks(int rows) { return rows <= 512 ? 32 : (rows <= 1024 ? 16 : 8); }
@@ -552,53 +410,28 @@ int fwd_chunks(int rows) {                                // vocabulary chunks o
 }
 long carve(const rmcl_mlm_head& hd, int rows, float* base, MlmWs* w) {
   StashCarver c{base};
-  const long RD = (long)rows * hd.D;
-  w->nchunk = 64;                                         // (capacity of the partial table; the launch uses fwd_chunks(rows) <= 64)
-  w->x = c.take(RD);
-  w->a = c.take(RD);
-  w->stat = c.take(2L * rows);
-  w->h = c.take(RD);                                        // (T <= 4 bytes)
-  w->hT = c.take(RD);
-  w->part = reinterpret_cast<float4*>(c.take(4L * 64 * rows));
+  pred_carve_fwd(c, rows, hd.D, &w->t);
+  w->t.hT = c.take((long)rows * hd.D);
+  w->part = reinterpret_cast<float4*>(c.take(4L * 64 * rows));   // (64: capacity of the partial table; the launch uses fwd_chunks(rows) <= 64)
   w->parti = reinterpret_cast<int*>(c.take(64L * rows));
-  w->dh = c.take(RD);
-  w->da = c.take(RD);
-  w->dx = c.take(RD);
-  w->lnpart = c.take((long)cdiv(rows, MLM_ROWS_PER_BLK) * 3 * hd.D);
+  pred_carve_bwd(c, rows, hd.D, &w->t);
   // (monotone in rows and >= h_chunks(rows) x rows in each of its three regimes: buffers sized for a larger extent fit a smaller one)
   w->dhp = c.take(std::max({32L * std::min(rows, 512), 16L * std::min(rows, 1024), 8L * rows}) * hd.D);
   return c.used;
 }
-bool head_ok(const rmcl_mlm_head* h) { return h && (h->D == 256 || h->D == 768) && h->V >= 1; }
-bool rows_ok(int rows) { return rows >= MLM_RG && rows % MLM_RG == 0 && rows <= (1 << 20); }
+bool head_ok(const rmcl_mlm_head* h) { return h && pred_head_ok(h->D) && h->V >= 1; }
 
 template <typename T>
 int lds_bytes(int D, bool with_dz) { return (32 * (D + Mma<T>::PAD) + (with_dz ? 32 * (MLM_RG + Mma<T>::PAD) : 0)) * (int)sizeof(T); }
 
-template <typename T>
-int transform_fwd(const rmcl_mlm_head* h, const float* params, const MlmWs& w, int rows, hipStream_t s) {
-  GemmArgs g0 = head_gemm(w.x, params + h->tw, w.a, rows, h->D, h->D, h->D, h->D, h->D, GEMM_TAG_HEAD);                    // a = x Wt^T + bt
-  g0.epi = EPI_BIAS;
-  g0.bias = params + h->tb;
-  RMCL_TRY(rmcl_launch_gemm(g0, RMCL_F32, RMCL_F32, 1, 1, 1, s));
-  if (h->D == 768)
-    RMCL_LAUNCH((mlm_gelu_ln_fwd_kernel<T, 3>), dim3(cdiv(rows, 4)), dim3(256), 0, s, w.a, params + h->lg, params + h->lb, (T*)w.h, (T*)w.hT, w.stat, rows);
-  else
-    RMCL_LAUNCH((mlm_gelu_ln_fwd_kernel<T, 1>), dim3(cdiv(rows, 4)), dim3(256), 0, s, w.a, params + h->lg, params + h->lb, (T*)w.h, (T*)w.hT, w.stat, rows);
-  RMCL_CHECK_LAUNCH();
-  return 0;
-}
-
 template <typename T, int NT>
 int forward_t(const rmcl_mlm_head* h, const float* params, const T* W, const float* xn, const int* idx, const int* lab, const int* count, int rows,
               const MlmWs& w, float* lse, float* rowloss, int* argmax, float* stats, hipStream_t s) {
-  RMCL_LAUNCH(mlm_gather_kernel, dim3(std::min(1024, cdiv((long)rows * h->D / 4, 256))), dim3(256), 0, s, xn, idx, count, w.x, rows, h->D);
-  RMCL_CHECK_LAUNCH();
-  RMCL_TRY(transform_fwd<T>(h, params, w, rows, s));
+  RMCL_TRY(pred_transform_forward(transform_of(h), params, xn, idx, count, rows, sizeof(T) == 2 ? RMCL_BF16 : RMCL_F32, w.t, s));
   const int nch = fwd_chunks(rows), lds = lds_bytes<T>(h->D, false);
   static RmclLdsOnce once;
   RMCL_TRY(rmcl_set_max_lds(once, (const void*)mlm_dec_fwd_kernel<T, NT>, lds));
-  RMCL_LAUNCH((mlm_dec_fwd_kernel<T, NT>), dim3(rows / 32, nch), dim3(256), lds, s, (const T*)w.h, W, params + h->db, lab, count, h->V, rows, w.part,
+  RMCL_LAUNCH((mlm_dec_fwd_kernel<T, NT>), dim3(rows / 32, nch), dim3(256), lds, s, (const T*)w.t.h, W, params + h->db, lab, count, h->V, rows, w.part,
               w.parti);
   RMCL_CHECK_LAUNCH();
   RMCL_LAUNCH(mlm_dec_finish_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, s, w.part, w.parti, nch, rows, count, h->V, lse, rowloss, argmax);
@@ -615,35 +448,17 @@ int backward_t(const rmcl_mlm_head* h, const float* params, const T* W, const T*
   static RmclLdsOnce once_w, once_h;
   if (G) {
     RMCL_TRY(rmcl_set_max_lds(once_w, (const void*)mlm_dec_bwd_w_kernel<T, NT>, lds));
-    RMCL_LAUNCH((mlm_dec_bwd_w_kernel<T, NT>), dim3(cdiv(V, 32)), dim3(256), lds, s, (const T*)w.h, (const T*)w.hT, W, params + h->db, lab, lse, count,
+    RMCL_LAUNCH((mlm_dec_bwd_w_kernel<T, NT>), dim3(cdiv(V, 32)), dim3(256), lds, s, (const T*)w.t.h, (const T*)w.t.hT, W, params + h->db, lab, lse, count,
                 gscale, gscale_dev, V, rows, G + h->dw, G + h->db);
     RMCL_CHECK_LAUNCH();
   }
   RMCL_TRY(rmcl_set_max_lds(once_h, (const void*)mlm_dec_bwd_h_kernel<T, NT>, lds));
-  RMCL_LAUNCH((mlm_dec_bwd_h_kernel<T, NT>), dim3(rows / 32, h_chunks(rows)), dim3(256), lds, s, (const T*)w.h, W, WT, params + h->db, lab, lse, count,
+  RMCL_LAUNCH((mlm_dec_bwd_h_kernel<T, NT>), dim3(rows / 32, h_chunks(rows)), dim3(256), lds, s, (const T*)w.t.h, W, WT, params + h->db, lab, lse, count,
               gscale, gscale_dev, V, ldv, rows, w.dhp);
   RMCL_CHECK_LAUNCH();
-  RMCL_LAUNCH(mlm_dh_reduce_kernel, dim3(std::min(1024, cdiv((long)rows * D / 4, 256))), dim3(256), 0, s, w.dhp, h_chunks(rows), rows, D, count, w.dh);
+  RMCL_LAUNCH(mlm_dh_reduce_kernel, dim3(std::min(1024, cdiv((long)rows * D / 4, 256))), dim3(256), 0, s, w.dhp, h_chunks(rows), rows, D, count, w.t.dh);
   RMCL_CHECK_LAUNCH();
-  const int nblk = cdiv(rows, MLM_ROWS_PER_BLK);
-  if (D == 768)
-    RMCL_LAUNCH(mlm_gelu_ln_bwd_kernel<3>, dim3(nblk), dim3(256), 0, s, w.dh, w.a, w.stat, params + h->lg, w.da, w.lnpart, rows);
-  else
-    RMCL_LAUNCH(mlm_gelu_ln_bwd_kernel<1>, dim3(nblk), dim3(256), 0, s, w.dh, w.a, w.stat, params + h->lg, w.da, w.lnpart, rows);
-  RMCL_CHECK_LAUNCH();
-  if (G) {
-    RMCL_LAUNCH(mlm_param_grad_kernel, dim3(cdiv(D, 256)), dim3(256), 0, s, w.lnpart, nblk, D, G + h->lg, G + h->lb, G + h->tb);
-    RMCL_CHECK_LAUNCH();
-    GemmArgs gw = head_gemm(w.da, w.x, G + h->tw, D, D, rows, D, D, D, GEMM_TAG_HEAD);                                      // dWt += da^T x
-    gw.epi = EPI_ACCUM;
-    RMCL_TRY(rmcl_launch_gemm(gw, RMCL_F32, RMCL_F32, 0, 0, 1, s));
-  }
-  RMCL_TRY(rmcl_launch_gemm(head_gemm(w.da, params + h->tw, w.dx, rows, D, D, D, D, D, GEMM_TAG_HEAD), RMCL_F32, RMCL_F32, 1, 0, 1, s));   // dx = da Wt
-  if (dxn) {
-    RMCL_LAUNCH(mlm_scatter_kernel, dim3(std::min(1024, cdiv((long)rows * D / 4, 256))), dim3(256), 0, s, w.dx, idx, count, dxn, rows, D);
-    RMCL_CHECK_LAUNCH();
-  }
-  return 0;
+  return pred_transform_backward(transform_of(h), params, w.t, idx, count, rows, G, dxn, s);
 }
 
 template <typename T, int NT>
@@ -651,7 +466,7 @@ int logits_t(const rmcl_mlm_head* h, const float* params, const T* W, const MlmW
   const int lds = lds_bytes<T>(h->D, false);
   static RmclLdsOnce once;
   RMCL_TRY(rmcl_set_max_lds(once, (const void*)mlm_logits_kernel<T, NT>, lds));
-  RMCL_LAUNCH((mlm_logits_kernel<T, NT>), dim3(cdiv(rows_out, 32), fwd_chunks(rows)), dim3(256), lds, s, (const T*)w.h, W, params + h->db, h->V, rows,
+  RMCL_LAUNCH((mlm_logits_kernel<T, NT>), dim3(cdiv(rows_out, 32), fwd_chunks(rows)), dim3(256), lds, s, (const T*)w.t.h, W, params + h->db, h->V, rows,
               rows_out, logits, ldl);
   RMCL_CHECK_LAUNCH();
   return 0;
@@ -687,7 +502,7 @@ int rmcl_mlm_weight_transpose(const rmcl_mlm_head* h, const float* params, void*
 int rmcl_mlm_forward(const rmcl_mlm_head* h, const float* params, const void* params_lp, int dtype, const float* xn, const int32_t* idx,
                      const int32_t* lab, const int32_t* count, int rows, float* ws, float* lse, float* rowloss, int32_t* argmax, float* stats,
                      void* stream) {
-  RMCL_REQUIRE(head_ok(h) && rows_ok(rows), "mlm_forward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
+  RMCL_REQUIRE(head_ok(h) && pred_rows_ok(rows), "mlm_forward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
   RMCL_REQUIRE(params && xn && idx && lab && count && ws && lse && rowloss && argmax && stats && (dtype == RMCL_F32 || params_lp),
                "mlm_forward: NULL argument");
   MlmWs w;
@@ -705,7 +520,7 @@ int rmcl_mlm_forward(const rmcl_mlm_head* h, const float* params, const void* pa
 int rmcl_mlm_backward(const rmcl_mlm_head* h, const float* params, const void* params_lp, const void* WT, int dtype, const int32_t* idx,
                       const int32_t* lab, const int32_t* count, int rows, float* ws, const float* lse, float grad_scale,
                       const float* grad_scale_dev, float* G, float* dxn, void* stream) {
-  RMCL_REQUIRE(head_ok(h) && rows_ok(rows), "mlm_backward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
+  RMCL_REQUIRE(head_ok(h) && pred_rows_ok(rows), "mlm_backward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
   RMCL_REQUIRE(params && WT && idx && lab && count && ws && lse && (dtype == RMCL_F32 || params_lp), "mlm_backward: NULL argument");
   MlmWs w;
   carve(*h, rows, ws, &w);
@@ -722,7 +537,7 @@ int rmcl_mlm_backward(const rmcl_mlm_head* h, const float* params, const void* p
 
 int rmcl_mlm_logits(const rmcl_mlm_head* h, const float* params, const void* params_lp, int dtype, float* ws, int rows, int rows_out, float* logits,
                     int64_t ldl, void* stream) {
-  RMCL_REQUIRE(head_ok(h) && rows_ok(rows) && rows_out >= 1 && rows_out <= rows && ldl >= h->V, "mlm_logits: bad shape");
+  RMCL_REQUIRE(head_ok(h) && pred_rows_ok(rows) && rows_out >= 1 && rows_out <= rows && ldl >= h->V, "mlm_logits: bad shape");
   RMCL_REQUIRE(params && ws && logits && (dtype == RMCL_F32 || params_lp), "mlm_logits: NULL argument");
   MlmWs w;
   carve(*h, rows, ws, &w);

@@ -5,12 +5,12 @@
 //   loss      = cross_entropy(logits.view(-1, 256), labels.view(-1), ignore_index = -100): the mean over the labelled (row, channel) pairs
 // Only the masked valid image slots carry labels (~15 % of B x P), so the training path works on those rows, COMPACTED:
 //   compact    one workgroup: ascending list of the masked valid slots as rows of xn, their three labels, the count n (on the device)
-//   gather     x [rows, D] = image rows of xn (rows >= n: zeros, so everything behind them is finite)
-//   transform  a = x Wt^T + bt (exact fp32 GEMM), h = LayerNorm(GELU(a)) in one row pass, kept in the decoder's operand type
+//   gather + transform   the prediction-head transform shared with the MLM head (head_transform.hip: pred_transform_forward) on the image
+//              rows of xn; h is kept in the decoder's operand type
 //   decoder    z [rows, 768] = h W^T + bias through the library's GEMM launcher (the logits of 768 columns are small: kept dense)
 //   CE         one wave per row: three 256-way softmax cross-entropies (4 columns per lane), lse / first argmax per group, the row loss
 //   backward   dz = s (softmax - onehot) / (3 n) from z and lse; dW += dz^T h, dbias += column sums (per 32-row chunk, then the chunks in
-//              ascending order), dh = dz W, the transform backward and the scatter of dx into the zero-filled dxn of the encoder backward
+//              ascending order), dh = dz W, then pred_transform_backward (the scatter of dx into the zero-filled dxn of the encoder backward included)
 // Every output has ONE owner and a fixed summation order (no float atomics): two identical calls give identical bits.
 #include <algorithm>
 #include "rmcl_common.h"
@@ -21,7 +21,6 @@
 namespace {
 
 #define MPP_V 768               // decoder width: 3 channels x 256 intensity classes
-#define MPP_ROWS_PER_BLK 16     // rows of one transform-backward workgroup (one partial of dgamma / dbeta / dbias per workgroup)
 
 // ---- labels ---------------------------------------------------------------------------------------------------------------------------
 // One wave per (sample, slot): lane l reads the float4 l + 64 k (k < 4) of the 256 float4 of a channel's 32 x 32 patch (row = i / 8),
@@ -181,141 +180,6 @@ __global__ __launch_bounds__(256) void mpp_compact_kernel(const int* __restrict_
   for (int i = n + t; i < cap; i += 256) { idx[i] = -1; lab[3 * i] = -100; lab[3 * i + 1] = -100; lab[3 * i + 2] = -100; }
 }
 
-// x [rows, D] = xn[idx[r]] for r < n, else 0
-__global__ __launch_bounds__(256) void mpp_gather_kernel(const float* __restrict__ xn, const int* __restrict__ idx, const int* __restrict__ count,
-                                                         float* __restrict__ x, int rows, int D) {
-  const int n = min(count[0], rows), per_row = D / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < (long)rows * per_row; i += (long)gridDim.x * 256) {
-    const int r = (int)(i / per_row), c = (int)(i - (long)r * per_row) * 4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < n) v = *reinterpret_cast<const float4*>(xn + (long)idx[r] * D + c);
-    *reinterpret_cast<float4*>(x + (long)r * D + c) = v;
-  }
-}
-
-// dxn[idx[r]] = dx[r] for r < n (every listed row has exactly one destination; dxn was zero-filled by the caller)
-__global__ __launch_bounds__(256) void mpp_scatter_kernel(const float* __restrict__ dx, const int* __restrict__ idx, const int* __restrict__ count,
-                                                          float* __restrict__ dxn, int rows, int D) {
-  const int n = min(count[0], rows), per_row = D / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < (long)n * per_row; i += (long)gridDim.x * 256) {
-    const int r = (int)(i / per_row), c = (int)(i - (long)r * per_row) * 4;
-    *reinterpret_cast<float4*>(dxn + (long)idx[r] * D + c) = *reinterpret_cast<const float4*>(dx + (long)r * D + c);
-  }
-}
-
-// ---- transform: h = LayerNorm(GELU(a)), eps 1e-12.  One wave per row, D = 256 NV.  h [rows, D] in T; stat[2 row] = (mean, rstd) ----------
-template <typename T, int NV>
-__global__ __launch_bounds__(256) void mpp_gelu_ln_fwd_kernel(const float* __restrict__ a, const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, T* __restrict__ h, float* __restrict__ stat,
-                                                              int rows) {
-  constexpr int D = 256 * NV;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  float4 v[NV];
-  float s = 0.f, mu, rs;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float4 x = *reinterpret_cast<const float4*>(a + (long)row * D + (lane + 64 * i) * 4);
-    v[i] = make_float4(gelu_erf(x.x), gelu_erf(x.y), gelu_erf(x.z), gelu_erf(x.w));
-    s += sum4_pairwise(v[i]);
-  }
-  ln_row_stats<NV>(v, s, 1e-12f, mu, rs);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    const float4 w = *reinterpret_cast<const float4*>(gamma + c), bb = *reinterpret_cast<const float4*>(beta + c);
-    T* o = h + (long)row * D + c;
-    o[0] = from_f32<T>((v[i].x - mu) * rs * w.x + bb.x);
-    o[1] = from_f32<T>((v[i].y - mu) * rs * w.y + bb.y);
-    o[2] = from_f32<T>((v[i].z - mu) * rs * w.z + bb.z);
-    o[3] = from_f32<T>((v[i].w - mu) * rs * w.w + bb.w);
-  }
-  if (lane == 0) {
-    stat[2 * row] = mu;
-    stat[2 * row + 1] = rs;
-  }
-}
-
-// da = GELU'(a) * LayerNorm'(dh) per row (GELU(a) and xhat recomputed from a and the stashed statistics).  part[blk][3][D]: this
-// workgroup's sums over its rows of dh * xhat (-> dgamma), dh (-> dbeta) and da (-> the dense bias); the four waves meet in LDS in wave order.
-template <int NV>
-__global__ __launch_bounds__(256) void mpp_gelu_ln_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ a,
-                                                              const float* __restrict__ stat, const float* __restrict__ gamma,
-                                                              float* __restrict__ da, float* __restrict__ part, int rows) {
-  constexpr int D = 256 * NV;
-  __shared__ float red[3][D];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  float4 w[NV], pg[NV], pb[NV], pa[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    w[i] = *reinterpret_cast<const float4*>(gamma + (lane + 64 * i) * 4);
-    pg[i] = pb[i] = pa[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  const int r0 = blockIdx.x * MPP_ROWS_PER_BLK;
-  for (int r = r0 + wave; r < min(r0 + MPP_ROWS_PER_BLK, rows); r += 4) {
-    const float mu = stat[2 * r], rs = stat[2 * r + 1];
-    float4 xh[NV], dx[NV], av[NV];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (lane + 64 * i) * 4;
-      av[i] = *reinterpret_cast<const float4*>(a + (long)r * D + c);
-      const float4 dy = *reinterpret_cast<const float4*>(dh + (long)r * D + c);
-      xh[i] = make_float4((gelu_erf(av[i].x) - mu) * rs, (gelu_erf(av[i].y) - mu) * rs, (gelu_erf(av[i].z) - mu) * rs,
-                          (gelu_erf(av[i].w) - mu) * rs);
-      ln_bwd_acc(dy, xh[i], w[i], pg[i], pb[i], dx[i], s1, s2);
-    }
-    float m1, m2;
-    ln_bwd_means(s1, s2, D, m1, m2);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (lane + 64 * i) * 4;
-      float4 o;
-      o.x = ln_bwd_dx(dx[i].x, xh[i].x, m1, m2, rs) * gelu_erf_grad(av[i].x);
-      o.y = ln_bwd_dx(dx[i].y, xh[i].y, m1, m2, rs) * gelu_erf_grad(av[i].y);
-      o.z = ln_bwd_dx(dx[i].z, xh[i].z, m1, m2, rs) * gelu_erf_grad(av[i].z);
-      o.w = ln_bwd_dx(dx[i].w, xh[i].w, m1, m2, rs) * gelu_erf_grad(av[i].w);
-      pa[i].x += o.x; pa[i].y += o.y; pa[i].z += o.z; pa[i].w += o.w;
-      *reinterpret_cast<float4*>(da + (long)r * D + c) = o;
-    }
-  }
-  for (int ph = 0; ph < 4; ++ph) {
-    if (wave == ph) {
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        const float x0[4] = {pg[i].x, pg[i].y, pg[i].z, pg[i].w}, x1[4] = {pb[i].x, pb[i].y, pb[i].z, pb[i].w},
-                    x2[4] = {pa[i].x, pa[i].y, pa[i].z, pa[i].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          red[0][c + j] = ph == 0 ? x0[j] : red[0][c + j] + x0[j];
-          red[1][c + j] = ph == 0 ? x1[j] : red[1][c + j] + x1[j];
-          red[2][c + j] = ph == 0 ? x2[j] : red[2][c + j] + x2[j];
-        }
-      }
-    }
-    __syncthreads();
-  }
-  float* out = part + (long)blockIdx.x * 3 * D;
-  for (int c = threadIdx.x; c < 3 * D; c += 256) out[c] = (&red[0][0])[c];
-}
-
-// dgamma[c] += sum_blk part[blk][0][c], dbeta[c] += ...[1][c], dbt[c] += ...[2][c], in workgroup order
-__global__ __launch_bounds__(256) void mpp_param_grad_kernel(const float* __restrict__ part, int nblk, int D, float* __restrict__ dgamma,
-                                                             float* __restrict__ dbeta, float* __restrict__ dbt) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= D) return;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  for (int k = 0; k < nblk; ++k) {
-    s0 += part[(long)k * 3 * D + c];
-    s1 += part[(long)k * 3 * D + D + c];
-    s2 += part[(long)k * 3 * D + 2 * D + c];
-  }
-  dgamma[c] += s0;
-  dbeta[c] += s1;
-  dbt[c] += s2;
-}
-
 // ---- three 256-way softmax cross-entropies per row: one wave per row, lane l holds columns 4 l .. 4 l + 3 of a group ------------------
 // lse [rows, 3], argmax [rows, 3] (first maximum), rowloss [rows] = sum over the labelled groups of lse - z[label].  A label of -100
 // (the dense-logits pass) leaves its group out of the row loss.  Rows >= n: 0 / -1 / 0.
@@ -419,45 +283,30 @@ __global__ __launch_bounds__(256) void mpp_logits_copy_kernel(const float* __res
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 struct MppWs {
-  float *x, *a, *stat, *z, *dh, *da, *dx, *lnpart, *dbpart;
-  void *h, *dz;
+  PredWs t;                                                 // the transform's slices (head_rows.h); no hT
+  float *z, *dbpart;
+  void* dz;
 };
+PredTransform transform_of(const rmcl_mpp_head* h) { return PredTransform{h->D, h->tw, h->tb, h->lg, h->lb}; }
 long carve(const rmcl_mpp_head& hd, int rows, float* base, MppWs* w) {
   StashCarver c{base};
-  const long RD = (long)rows * hd.D, RV = (long)rows * MPP_V;
-  w->x = c.take(RD);
-  w->a = c.take(RD);
-  w->stat = c.take(2L * rows);
-  w->h = c.take(RD);                                        // (T <= 4 bytes)
+  const long RV = (long)rows * MPP_V;
+  pred_carve_fwd(c, rows, hd.D, &w->t);
   w->z = c.take(RV);
   w->dz = c.take(RV);
-  w->dh = c.take(RD);
-  w->da = c.take(RD);
-  w->dx = c.take(RD);
-  w->lnpart = c.take((long)cdiv(rows, MPP_ROWS_PER_BLK) * 3 * hd.D);
+  pred_carve_bwd(c, rows, hd.D, &w->t);
   w->dbpart = c.take((long)cdiv(rows, MPP_DB_ROWS) * MPP_V);
   return c.used;
 }
-bool head_ok(const rmcl_mpp_head* h) { return h && (h->D == 256 || h->D == 768); }
-bool rows_ok(int rows) { return rows >= 128 && rows % 128 == 0 && rows <= (1 << 20); }
+bool head_ok(const rmcl_mpp_head* h) { return h && pred_head_ok(h->D); }
 int grid_for(long elems) { return (int)std::min<long>(1024, (elems + 255) / 256); }
 
 template <typename T>
 int forward_t(const rmcl_mpp_head* h, const float* params, const T* W, int dtype, const float* xn, const int* idx, const int* lab,
               const int* count, int rows, const MppWs& w, float* lse, float* rowloss, int* argmax, float* stats, hipStream_t s) {
   const int D = h->D;
-  RMCL_LAUNCH(mpp_gather_kernel, dim3(grid_for((long)rows * D / 4)), dim3(256), 0, s, xn, idx, count, w.x, rows, D);
-  RMCL_CHECK_LAUNCH();
-  GemmArgs g0 = head_gemm(w.x, params + h->tw, w.a, rows, D, D, D, D, D, GEMM_TAG_HEAD);                                   // a = x Wt^T + bt
-  g0.epi = EPI_BIAS;
-  g0.bias = params + h->tb;
-  RMCL_TRY(rmcl_launch_gemm(g0, RMCL_F32, RMCL_F32, 1, 1, 1, s));
-  if (D == 768)
-    RMCL_LAUNCH((mpp_gelu_ln_fwd_kernel<T, 3>), dim3(cdiv(rows, 4)), dim3(256), 0, s, w.a, params + h->lg, params + h->lb, (T*)w.h, w.stat, rows);
-  else
-    RMCL_LAUNCH((mpp_gelu_ln_fwd_kernel<T, 1>), dim3(cdiv(rows, 4)), dim3(256), 0, s, w.a, params + h->lg, params + h->lb, (T*)w.h, w.stat, rows);
-  RMCL_CHECK_LAUNCH();
-  GemmArgs g1 = head_gemm(w.h, W, w.z, rows, MPP_V, D, D, D, MPP_V, GEMM_TAG_HEAD);                                          // z = h W^T + bias
+  RMCL_TRY(pred_transform_forward(transform_of(h), params, xn, idx, count, rows, dtype, w.t, s));
+  GemmArgs g1 = head_gemm(w.t.h, W, w.z, rows, MPP_V, D, D, D, MPP_V, GEMM_TAG_HEAD);                                          // z = h W^T + bias
   g1.epi = EPI_BIAS;
   g1.bias = params + h->db;
   RMCL_TRY(rmcl_launch_gemm(g1, dtype, RMCL_F32, 1, 1, dtype == RMCL_F32, s));
@@ -475,7 +324,7 @@ int backward_t(const rmcl_mpp_head* h, const float* params, const T* W, int dtyp
   RMCL_LAUNCH(mpp_ce_bwd_kernel<T>, dim3(grid_for((long)rows * MPP_V)), dim3(256), 0, s, w.z, lab, lse, count, gscale, gscale_dev, rows, (T*)w.dz);
   RMCL_CHECK_LAUNCH();
   if (G) {
-    GemmArgs gw = head_gemm(w.dz, w.h, G + h->dw, MPP_V, D, rows, MPP_V, D, D, GEMM_TAG_HEAD);                                // dW += dz^T h
+    GemmArgs gw = head_gemm(w.dz, w.t.h, G + h->dw, MPP_V, D, rows, MPP_V, D, D, GEMM_TAG_HEAD);                                // dW += dz^T h
     gw.epi = EPI_ACCUM;
     RMCL_TRY(rmcl_launch_gemm(gw, dtype, RMCL_F32, 0, 0, exact, s));
     RMCL_LAUNCH(mpp_dbias_part_kernel<T>, dim3(cdiv(MPP_V, 256), cdiv(rows, MPP_DB_ROWS)), dim3(256), 0, s, (const T*)w.dz, count, rows, w.dbpart);
@@ -483,26 +332,8 @@ int backward_t(const rmcl_mpp_head* h, const float* params, const T* W, int dtyp
     RMCL_LAUNCH(mpp_dbias_merge_kernel, dim3(cdiv(MPP_V, 256)), dim3(256), 0, s, w.dbpart, count, rows, G + h->db);
     RMCL_CHECK_LAUNCH();
   }
-  RMCL_TRY(rmcl_launch_gemm(head_gemm(w.dz, W, w.dh, rows, D, MPP_V, MPP_V, D, D, GEMM_TAG_HEAD), dtype, RMCL_F32, 1, 0, exact, s));   // dh = dz W
-  const int nblk = cdiv(rows, MPP_ROWS_PER_BLK);
-  if (D == 768)
-    RMCL_LAUNCH(mpp_gelu_ln_bwd_kernel<3>, dim3(nblk), dim3(256), 0, s, w.dh, w.a, w.stat, params + h->lg, w.da, w.lnpart, rows);
-  else
-    RMCL_LAUNCH(mpp_gelu_ln_bwd_kernel<1>, dim3(nblk), dim3(256), 0, s, w.dh, w.a, w.stat, params + h->lg, w.da, w.lnpart, rows);
-  RMCL_CHECK_LAUNCH();
-  if (G) {
-    RMCL_LAUNCH(mpp_param_grad_kernel, dim3(cdiv(D, 256)), dim3(256), 0, s, w.lnpart, nblk, D, G + h->lg, G + h->lb, G + h->tb);
-    RMCL_CHECK_LAUNCH();
-    GemmArgs gt = head_gemm(w.da, w.x, G + h->tw, D, D, rows, D, D, D, GEMM_TAG_HEAD);                                        // dWt += da^T x
-    gt.epi = EPI_ACCUM;
-    RMCL_TRY(rmcl_launch_gemm(gt, RMCL_F32, RMCL_F32, 0, 0, 1, s));
-  }
-  if (dxn) {
-    RMCL_TRY(rmcl_launch_gemm(head_gemm(w.da, params + h->tw, w.dx, rows, D, D, D, D, D, GEMM_TAG_HEAD), RMCL_F32, RMCL_F32, 1, 0, 1, s));   // dx = da Wt
-    RMCL_LAUNCH(mpp_scatter_kernel, dim3(grid_for((long)rows * D / 4)), dim3(256), 0, s, w.dx, idx, count, dxn, rows, D);
-    RMCL_CHECK_LAUNCH();
-  }
-  return 0;
+  RMCL_TRY(rmcl_launch_gemm(head_gemm(w.dz, W, w.t.dh, rows, D, MPP_V, MPP_V, D, D, GEMM_TAG_HEAD), dtype, RMCL_F32, 1, 0, exact, s));   // dh = dz W
+  return pred_transform_backward(transform_of(h), params, w.t, idx, count, rows, G, dxn, s);
 }
 }  // namespace
 
@@ -552,7 +383,7 @@ int rmcl_mpp_compact(const int32_t* labels, const int32_t* masked, int B, int P,
 int rmcl_mpp_forward(const rmcl_mpp_head* h, const float* params, const void* params_lp, int dtype, const float* xn, const int32_t* idx,
                      const int32_t* lab, const int32_t* count, int rows, float* ws, float* lse, float* rowloss, int32_t* argmax, float* stats,
                      void* stream) {
-  RMCL_REQUIRE(head_ok(h) && rows_ok(rows), "mpp_forward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
+  RMCL_REQUIRE(head_ok(h) && pred_rows_ok(rows), "mpp_forward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
   RMCL_REQUIRE(params && xn && idx && lab && count && ws && lse && rowloss && argmax && stats && (dtype == RMCL_F32 || params_lp),
                "mpp_forward: NULL argument");
   MppWs w;
@@ -566,7 +397,7 @@ int rmcl_mpp_forward(const rmcl_mpp_head* h, const float* params, const void* pa
 int rmcl_mpp_backward(const rmcl_mpp_head* h, const float* params, const void* params_lp, int dtype, const int32_t* idx, const int32_t* lab,
                       const int32_t* count, int rows, float* ws, const float* lse, float grad_scale, const float* grad_scale_dev, float* G,
                       float* dxn, void* stream) {
-  RMCL_REQUIRE(head_ok(h) && rows_ok(rows), "mpp_backward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
+  RMCL_REQUIRE(head_ok(h) && pred_rows_ok(rows), "mpp_backward: unsupported head (D in {256, 768}) / rows not a multiple of 128");
   RMCL_REQUIRE(params && idx && lab && count && ws && lse && (dtype == RMCL_F32 || params_lp), "mpp_backward: NULL argument");
   MppWs w;
   carve(*h, rows, ws, &w);
@@ -577,7 +408,7 @@ int rmcl_mpp_backward(const rmcl_mpp_head* h, const float* params, const void* p
 }
 
 int rmcl_mpp_logits(const rmcl_mpp_head* h, float* ws, int rows, int rows_out, float* logits, void* stream) {
-  RMCL_REQUIRE(head_ok(h) && rows_ok(rows) && rows_out >= 1 && rows_out <= rows, "mpp_logits: bad shape");
+  RMCL_REQUIRE(head_ok(h) && pred_rows_ok(rows) && rows_out >= 1 && rows_out <= rows, "mpp_logits: bad shape");
   RMCL_REQUIRE(ws && logits, "mpp_logits: NULL argument");
   MppWs w;
   carve(*h, rows, ws, &w);

@@ -208,33 +208,47 @@ class Nlvr2Buffers(ClassifierBuffers):
         self.labels = torch.empty(B, dtype=torch.int32, device=eng.device)
 
 
+def _transform_rows(n: str, D: int):
+    """the four `_pack` rows of a prediction head's BertPredictionHeadTransform (heads.py: dense, LayerNorm) under the module name `n`"""
+    return [("tw", n + "transform.dense.weight", (D, D), None), ("tb", n + "transform.dense.bias", (D,), None),
+            ("lg", n + "transform.LayerNorm.weight", (D,), None), ("lb", n + "transform.LayerNorm.bias", (D,), None)]
+
+
 def mlm_layout(cfg: dict, base: int):
     """mlm_score (heads.py:183-195, built WITHOUT a tied weight at vilt_module.py:56: decoder.weight [vocab, D] is a parameter of its
     own) appended to the parameter arena at element offset `base`: returns (rmcl_mlm_head struct, specs, elements used)."""
     D, V = int(cfg["hidden_size"]), int(cfg["vocab_size"])
     n = "mlm_score."
-    offs, specs, used = _pack(base, [("tw", n + "transform.dense.weight", (D, D), None), ("tb", n + "transform.dense.bias", (D,), None),
-                                     ("lg", n + "transform.LayerNorm.weight", (D,), None), ("lb", n + "transform.LayerNorm.bias", (D,), None),
-                                     ("dw", n + "decoder.weight", (V, D), None), ("db", n + "bias", (V,), None)])
+    offs, specs, used = _pack(base, _transform_rows(n, D) + [("dw", n + "decoder.weight", (V, D), None), ("db", n + "bias", (V,), None)])
     return L.MlmHead(D=D, V=V, **offs), specs, used
 
 
-class MlmBuffers:
-    """Per-(batch, tag) buffers of the MLM head for M = B x L text positions: the compaction (row list, labels, device-side count),
-    the per-row outputs and the workspace the forward leaves for the backward.  ``rows``: launch extent of the compacted buffers for
-    the bound batch (a multiple of 128 >= the number of labelled rows)."""
+class CompactedHeadBuffers:
+    """What the per-pass buffers of the prediction heads (MLM, MPP) share: the compaction of at most `max_rows` rows (row list, `groups`
+    labels per row, `ncount` device-side counts), the per-row outputs and the workspace the forward leaves for the backward.  ``cap``:
+    `max_rows` rounded up to 128; ``rows``: launch extent for the bound batch (``bind_rows``)."""
+
+    def __init__(self, eng: "Engine", max_rows: int, groups: tuple, ncount: int, ws_floats, head):
+        self.cap = (max_rows + 127) // 128 * 128
+        i32 = lambda *n: torch.empty(*n, dtype=torch.int32, device=eng.device)
+        f32 = lambda *n: torch.empty(*n, dtype=torch.float32, device=eng.device)
+        self.idx, self.lab, self.count = i32(self.cap), i32(self.cap, *groups), i32(ncount)
+        self.lse, self.rowloss, self.argmax = f32(self.cap, *groups), f32(self.cap), i32(self.cap, *groups)
+        self.ws = f32(int(ws_floats(C.byref(head), self.cap)))
+        self.rows = self.cap
+
+    def bind_rows(self, n: int, all_rows: bool):
+        """the launch extent for a batch with (at most) n listed rows, known on the host: a multiple of 128, at least 128; all_rows: cap"""
+        self.rows = self.cap if all_rows else min(self.cap, max(128, (n + 127) // 128 * 128))
+
+
+class MlmBuffers(CompactedHeadBuffers):
+    """Per-(batch, tag) buffers of the MLM head for M = B x L text positions (``rows`` >= the number of labelled rows)."""
 
     def __init__(self, eng: "Engine", B: int):
-        dev = eng.device
         self.B, self.L = B, int(eng.cfg["max_text_len"])
         self.M = B * self.L
-        self.cap = (self.M + 127) // 128 * 128
-        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
-        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
-        self.idx, self.lab, self.count = i32(self.cap), i32(self.cap), i32(1)
-        self.lse, self.rowloss, self.argmax = f32(self.cap), f32(self.cap), i32(self.cap)
-        self.ws = f32(int(lib.rmcl_mlm_ws_floats(C.byref(eng.mlm), self.cap)))
-        self.rows = self.cap
+        super().__init__(eng, self.M, (), 1, lib.rmcl_mlm_ws_floats, eng.mlm)
         self.labels = None                                      # the bound [B, L] int64 labels on the device
 
 
@@ -244,10 +258,8 @@ def mpp_layout(cfg: dict, base: int):
     struct, specs, elements used)."""
     D = int(cfg["hidden_size"])
     n = "mpp_score."
-    offs, specs, used = _pack(base, [("mt", "transformer.mask_token", (1, 1, D), None),
-                                     ("tw", n + "transform.dense.weight", (D, D), None), ("tb", n + "transform.dense.bias", (D,), None),
-                                     ("lg", n + "transform.LayerNorm.weight", (D,), None), ("lb", n + "transform.LayerNorm.bias", (D,), None),
-                                     ("dw", n + "decoder.weight", (768, D), None), ("db", n + "decoder.bias", (768,), None)])
+    offs, specs, used = _pack(base, [("mt", "transformer.mask_token", (1, 1, D), None)] + _transform_rows(n, D) +
+                              [("dw", n + "decoder.weight", (768, D), None), ("db", n + "decoder.bias", (768,), None)])
     return L.MppHead(D=D, reserved=0, **offs), specs, used
 
 
@@ -260,23 +272,17 @@ def mpp_draw_masks(B: int, G: int):
     return masked, replaced
 
 
-class MppBuffers:
-    """Per-(batch, tag, image length) buffers of the MPP head for B x P image slots: the slot labels, the masks gathered through the
-    batch's patch selection, the compaction (row list, labels, device-side counts), the per-row outputs and the workspace the forward
-    leaves for the backward.  ``rows``: launch extent for the bound batch (a multiple of 128 >= the host-known number of masked slots)."""
+class MppBuffers(CompactedHeadBuffers):
+    """Per-(batch, tag, image length) buffers of the MPP head for B x P image slots: the slot labels and the masks gathered through the
+    batch's patch selection, then the compacted set (three labels per row; ``rows`` >= the host-known number of masked slots)."""
 
     def __init__(self, eng: "Engine", B: int, Pn: int):
-        dev = eng.device
         self.B, self.P = B, Pn
-        self.cap = (B * (Pn + 1) + 127) // 128 * 128            # (all image rows, the cls rows included: the dense-logits pass)
-        i32 = lambda *n: torch.empty(*n, dtype=torch.int32, device=dev)
-        f32 = lambda *n: torch.empty(*n, dtype=torch.float32, device=dev)
-        self.labels = i32(B, Pn, 3)
-        self.idx, self.lab, self.count = i32(self.cap), i32(self.cap, 3), i32(2)
-        self.lse, self.rowloss, self.argmax = f32(self.cap, 3), f32(self.cap), i32(self.cap, 3)
-        self.ws = f32(int(lib.rmcl_mpp_ws_floats(C.byref(eng.mpp), self.cap)))
-        self.rows = self.cap
+        # (all image rows, the cls rows included: the dense-logits pass)
+        super().__init__(eng, B * (Pn + 1), (3,), 2, lib.rmcl_mpp_ws_floats, eng.mpp)
+        self.labels = torch.empty(B, Pn, 3, dtype=torch.int32, device=eng.device)
         self.masked = self.replaced = None                      # [B, P] int32 on the device, of the bound batch
+        self.n_masked = self.cap                                # host-known bound of the listed rows (mpp_labels_masks)
 
 
 class PassBuffers:
@@ -1192,26 +1198,32 @@ class Engine:
         if n_bad:
             raise ValueError(f"text_labels_mlm: {n_bad} label(s) outside [0, {V}) (vocab_size) other than the ignore index -100")
         mb.labels = lab.to(self.device).contiguous()
-        mb.rows = mb.cap if all_rows else min(mb.cap, max(128, (n + 127) // 128 * 128))
+        mb.bind_rows(n, all_rows)
         check(lib.rmcl_mlm_compact(P(mb.labels), mb.M, mb.L, int(N), V, int(all_rows), P(mb.idx), P(mb.lab), P(mb.count), stream_ptr()),
               "mlm_compact")
         return mb
 
-    def mlm_forward(self, mb: MlmBuffers, xn: torch.Tensor, stats: torch.Tensor = None) -> torch.Tensor:
-        """stats = (mlm_loss, rows with argmax == label, n) of the bound batch; per compacted row mb.lse / .rowloss / .argmax."""
+    def _pred_forward(self, fn, what: str, head, hb: CompactedHeadBuffers, xn: torch.Tensor, stats: torch.Tensor) -> torch.Tensor:
+        """rmcl_mlm_forward / rmcl_mpp_forward (one argument list) on the bound compacted buffers `hb`"""
         if self.lp_stale:
             self.refresh_shadows()
         stats = torch.empty(3, dtype=torch.float32, device=self.device) if stats is None else stats
-        check(lib.rmcl_mlm_forward(C.byref(self.mlm), P(self.q32), P(self.q_lp), self.dtype, P(xn), P(mb.idx), P(mb.lab), P(mb.count), mb.rows,
-                                   P(mb.ws), P(mb.lse), P(mb.rowloss), P(mb.argmax), P(stats), stream_ptr()), "mlm_forward")
+        check(fn(C.byref(head), P(self.q32), P(self.q_lp), self.dtype, P(xn), P(hb.idx), P(hb.lab), P(hb.count), hb.rows,
+                 P(hb.ws), P(hb.lse), P(hb.rowloss), P(hb.argmax), P(stats), stream_ptr()), what)
         return stats
+
+    def _pred_backward(self, fn, what: str, head, hb: CompactedHeadBuffers, grad_scale, scale_dev, dxn, with_grads, *operands):
+        """rmcl_mlm_backward / rmcl_mpp_backward; `operands`: what the head passes between the shadow arena and the dtype (MLM: W^T)"""
+        check(fn(C.byref(head), P(self.q32), P(self.q_lp), *(P(o) for o in operands), self.dtype, P(hb.idx), P(hb.lab), P(hb.count), hb.rows,
+                 P(hb.ws), P(hb.lse), F(grad_scale), P(scale_dev), P(self.g32 if with_grads else None), P(dxn), stream_ptr()), what)
+
+    def mlm_forward(self, mb: MlmBuffers, xn: torch.Tensor, stats: torch.Tensor = None) -> torch.Tensor:
+        """stats = (mlm_loss, rows with argmax == label, n) of the bound batch; per compacted row mb.lse / .rowloss / .argmax."""
+        return self._pred_forward(lib.rmcl_mlm_forward, "mlm_forward", self.mlm, mb, xn, stats)
 
     def mlm_backward(self, mb: MlmBuffers, grad_scale: float, scale_dev: torch.Tensor, dxn: torch.Tensor, with_grads: bool = True):
         """CE gradient (recomputed) -> decoder -> transform -> stored into the zero-filled dxn [B N, D]; head gradients into the arena."""
-        wT = self.mlm_weights_T()
-        check(lib.rmcl_mlm_backward(C.byref(self.mlm), P(self.q32), P(self.q_lp), P(wT), self.dtype, P(mb.idx), P(mb.lab), P(mb.count), mb.rows,
-                                    P(mb.ws), P(mb.lse), F(grad_scale), P(scale_dev), P(self.g32 if with_grads else None), P(dxn),
-                                    stream_ptr()), "mlm_backward")
+        self._pred_backward(lib.rmcl_mlm_backward, "mlm_backward", self.mlm, mb, grad_scale, scale_dev, dxn, with_grads, self.mlm_weights_T())
 
     def mlm_logits(self, mb: MlmBuffers, rows_out: int) -> torch.Tensor:
         """dense logits [rows_out, vocab] of the first rows_out compacted rows of the last mlm_forward on `mb`"""
@@ -1229,10 +1241,16 @@ class Engine:
 
     def mpp_bind(self, mp: MppBuffers, img: torch.Tensor, pb: PassBuffers, masked: torch.Tensor, replaced: torch.Tensor,
                  all_rows: bool = False) -> MppBuffers:
-        """Labels of the batch's image slots from the float image `img` [B, 3, H, W] (on the device), the two full-grid masks [B, G]
-        gathered through `pb`'s patch selection into [B, P] (pad slots: 0), and the compaction of the masked valid slots.  The launch
-        extent comes from the host-known number of masked patches; n stays on the device.  A pixel mean outside [0, 1] (pixels outside
-        [-1, 1]) is a ValueError, like the reference's cross_entropy raising on a label outside 0..255.
+        """``mpp_labels_masks``, then ``mpp_compact``: the labels and gathered masks of the batch, and the compaction of its masked valid
+        slots.  A pixel mean outside [0, 1] (pixels outside [-1, 1]) is a ValueError (``mpp_check_labels``), like the reference's
+        cross_entropy raising on a label outside 0..255."""
+        self.mpp_labels_masks(mp, img, pb, masked, replaced)
+        return self.mpp_compact(mp, pb, all_rows)
+
+    def mpp_labels_masks(self, mp: MppBuffers, img: torch.Tensor, pb: PassBuffers, masked: torch.Tensor, replaced: torch.Tensor):
+        """Labels of the batch's image slots from the float image `img` [B, 3, H, W] (on the device) into mp.labels, and the two full-grid
+        masks [B, G] gathered through `pb`'s patch selection into mp.masked / mp.replaced [B, P] (pad slots: 0).  mp.n_masked: the
+        host-known number of masked patches (it only sizes the launches; n stays on the device).
         `img` may be a ``Uint8Batch`` / ``RawUint8Batch`` instead: the labels then come from the bytes (rmcl_mpp_labels_u8: the same
         integers as from ``float_image()``, which is never built), G from the batch's ``shape``."""
         u8 = None
@@ -1269,10 +1287,15 @@ class Engine:
             valid = (torch.arange(Pn, device=self.device)[None, :] < geom.counts[:, None]).to(torch.int32)
             mp.masked = (torch.gather(mk, 1, sel) * valid).contiguous()
             mp.replaced = (torch.gather(rp, 1, sel) * valid).contiguous()
-        mp.rows = mp.cap if all_rows else min(mp.cap, max(128, (min(n_host, B * Pn) + 127) // 128 * 128))
-        N = d.L + 1 + d.P
-        check(lib.rmcl_mpp_compact(P(mp.labels), P(mp.masked), B, Pn, d.L, N, int(all_rows), mp.cap, P(mp.idx), P(mp.lab), P(mp.count), stream_ptr()),
-              "mpp_compact")
+        mp.n_masked = min(n_host, B * Pn)
+
+    def mpp_compact(self, mp: MppBuffers, pb: PassBuffers, all_rows: bool = False) -> MppBuffers:
+        """The compaction of mp.labels / mp.masked for `pb`'s row layout: the masked valid slots, or (all_rows, the dense-logits pass) every
+        image row.  The launch extent comes from mp.n_masked."""
+        d = pb.d
+        mp.bind_rows(mp.n_masked, all_rows)
+        check(lib.rmcl_mpp_compact(P(mp.labels), P(mp.masked), mp.B, d.P, d.L, d.L + 1 + d.P, int(all_rows), mp.cap, P(mp.idx), P(mp.lab), P(mp.count),
+                                   stream_ptr()), "mpp_compact")
         return mp
 
     def mpp_check_labels(self, mp: MppBuffers):
@@ -1284,18 +1307,11 @@ class Engine:
 
     def mpp_forward(self, mp: MppBuffers, xn: torch.Tensor, stats: torch.Tensor = None) -> torch.Tensor:
         """stats = (mpp_loss, correct (row, channel) pairs, labelled pairs) of the bound batch; per listed row mp.lse / .rowloss / .argmax."""
-        if self.lp_stale:
-            self.refresh_shadows()
-        stats = torch.empty(3, dtype=torch.float32, device=self.device) if stats is None else stats
-        check(lib.rmcl_mpp_forward(C.byref(self.mpp), P(self.q32), P(self.q_lp), self.dtype, P(xn), P(mp.idx), P(mp.lab), P(mp.count), mp.rows,
-                                   P(mp.ws), P(mp.lse), P(mp.rowloss), P(mp.argmax), P(stats), stream_ptr()), "mpp_forward")
-        return stats
+        return self._pred_forward(lib.rmcl_mpp_forward, "mpp_forward", self.mpp, mp, xn, stats)
 
     def mpp_backward(self, mp: MppBuffers, grad_scale: float, scale_dev: torch.Tensor, dxn: torch.Tensor, with_grads: bool = True):
         """CE gradient -> decoder -> transform -> stored into the zero-filled dxn [B N, D]; head gradients into the arena."""
-        check(lib.rmcl_mpp_backward(C.byref(self.mpp), P(self.q32), P(self.q_lp), self.dtype, P(mp.idx), P(mp.lab), P(mp.count), mp.rows,
-                                    P(mp.ws), P(mp.lse), F(grad_scale), P(scale_dev), P(self.g32 if with_grads else None), P(dxn),
-                                    stream_ptr()), "mpp_backward")
+        self._pred_backward(lib.rmcl_mpp_backward, "mpp_backward", self.mpp, mp, grad_scale, scale_dev, dxn, with_grads)
 
     def mpp_logits(self, mp: MppBuffers, rows_out: int) -> torch.Tensor:
         """dense logits [rows_out, 768] of the first rows_out listed rows of the last mpp_forward on `mp`"""

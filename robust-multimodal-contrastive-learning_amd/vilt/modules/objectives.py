@@ -224,6 +224,44 @@ def compute_itm_wpa(pl_module, batch):
     return ret
 
 
+def _pred_head_backward(pl_module, value, pb, op, head_backward, replaced=None):
+    """Gives the loss of a prediction head (MLM, MPP) its ``.backward()``: the head's backward (``head_backward(g, dxn)``: Engine.mlm_backward /
+    mpp_backward on the incoming gradient g [1] and a zero-filled dxn [B N, D]), then the full-row encoder backward and the step's
+    gradient reduction."""
+    eng = pl_module.engine
+    rows = pb.B * (pb.d.L + 1 + pb.d.P)
+
+    def backward(grad_out):
+        g = grad_out.to(torch.float32).reshape(1).contiguous()
+        dxn = torch.zeros(rows, pb.d.D, dtype=torch.float32, device=eng.device)
+        head_backward(g, dxn)
+        eng.encoder_backward(pb, L.MODE_FULL, op, dxn, cls_only=False, dpatches=None, replaced=replaced)
+        pl_module.after_backward()
+
+    return _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+
+
+def _pred_head_report(pl_module, task, value, stats):
+    """What compute_mlm and compute_mpp do with stats = (loss, correct, labelled) once the loss stands - Accuracy (gadgets/my_metrics.py:5-28):
+    correct / total over the labelled rows (MPP: (row, channel) pairs), per step and accumulated over the epoch; the two logs; the epoch
+    metrics."""
+    phase = "train" if pl_module.training else "val"
+    acc = getattr(pl_module, f"{task}_epoch_counts", None)
+    if acc is None:
+        acc = {}
+        setattr(pl_module, f"{task}_epoch_counts", acc)
+    if phase not in acc:
+        acc[phase] = torch.zeros(2, dtype=torch.float32, device=stats.device)
+    acc[phase] += stats[1:3]
+    pl_module.log(f"{task}/{phase}/loss", value.detach())
+    pl_module.log(f"{task}/{phase}/accuracy", stats[1] / stats[2])
+    if _em(pl_module) is not None:
+        # (a batch without a labelled row has a NaN loss, here as in the reference; gated on the row count it leaves the epoch loss alone)
+        _metric(pl_module, f"{phase}_{task}_accuracy").update_counts(stats[1:2], stats[2:3])
+        _metric(pl_module, f"{phase}_{task}_loss").update(value.detach(), gate=stats[2:3])
+        _em(pl_module).flush()
+
+
 def compute_mlm(pl_module, batch):
     """objectives.compute_mlm (:604-630): one FULL-mode encoder pass on the masked ids (no cls-only tail: the loss reads text rows), then
     mlm_score and the cross-entropy over the positions whose label is not -100 - on those rows only, compacted, with the decoder and
@@ -244,36 +282,14 @@ def compute_mlm(pl_module, batch):
     stats = eng.mlm_forward(mb, pb.xn)                                      # (loss, correct rows, rows with a label), all on the device
     value = _scalar(stats[0:1].clone())
     if need_grad:
-        def backward(grad_out, pb=pb, mb=mb, op=op, N=N):
-            g = grad_out.to(torch.float32).reshape(1).contiguous()
-            dxn = torch.zeros(pb.B * N, pb.d.D, dtype=torch.float32, device=eng.device)
-            eng.mlm_backward(mb, 1.0, g, dxn, with_grads=True)
-            eng.encoder_backward(pb, L.MODE_FULL, op, dxn, cls_only=False, dpatches=None)
-            pl_module.after_backward()
-
-        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+        value = _pred_head_backward(pl_module, value, pb, op, lambda g, dxn: eng.mlm_backward(mb, 1.0, g, dxn, with_grads=True))
     logits = None
     if cfg.get("mlm_return_logits", False) or not (torch.is_grad_enabled() or pl_module.training):
         ma = eng.mlm_bind(eng.mlm_bufs(pb.B, "mlm_dense"), labels, N, all_rows=True)
         eng.mlm_forward(ma, pb.xn)
         logits = eng.mlm_logits(ma, ma.M).view(pb.B, d.L, eng.mlm.V)
-    ret = {"mlm_loss": value, "mlm_logits": logits, "mlm_labels": labels, "mlm_ids": ids}
-    phase = "train" if pl_module.training else "val"
-    # Accuracy (gadgets/my_metrics.py:5-28): correct / total over the rows with a label, per step and accumulated over the epoch
-    acc = getattr(pl_module, "mlm_epoch_counts", None)
-    if acc is None:
-        acc = pl_module.mlm_epoch_counts = {}
-    if phase not in acc:
-        acc[phase] = torch.zeros(2, dtype=torch.float32, device=eng.device)
-    acc[phase] += stats[1:3]
-    pl_module.log(f"mlm/{phase}/loss", value.detach())
-    pl_module.log(f"mlm/{phase}/accuracy", stats[1] / stats[2])
-    if _em(pl_module) is not None:
-        # (a batch without a labelled row has a NaN loss, here as in the reference; gated on the row count it leaves the epoch loss alone)
-        _metric(pl_module, f"{phase}_mlm_accuracy").update_counts(stats[1:2], stats[2:3])
-        _metric(pl_module, f"{phase}_mlm_loss").update(value.detach(), gate=stats[2:3])
-        _em(pl_module).flush()
-    return ret
+    _pred_head_report(pl_module, "mlm", value, stats)
+    return {"mlm_loss": value, "mlm_logits": logits, "mlm_labels": labels, "mlm_ids": ids}
 
 
 def _mpp_pass(pl_module, batch, text_ids, tag, mode):
@@ -326,45 +342,22 @@ def compute_mpp(pl_module, batch):
     need_grad = torch.is_grad_enabled() and pl_module.training
     pb, mp, op, img = _mpp_pass(pl_module, batch, batch["text_ids"], "mpp", L.MODE_FULL if need_grad else L.MODE_INFER)
     d = pb.d
-    N = d.L + 1 + d.P
     stats = eng.mpp_forward(mp, pb.xn)                                      # (loss, correct pairs, labelled pairs), all on the device
     value = _scalar(stats[0:1].clone())
     if need_grad:
-        def backward(grad_out, pb=pb, mp=mp, op=op, N=N):
-            g = grad_out.to(torch.float32).reshape(1).contiguous()
-            dxn = torch.zeros(pb.B * N, pb.d.D, dtype=torch.float32, device=eng.device)
-            eng.mpp_backward(mp, 1.0, g, dxn, with_grads=True)
-            eng.encoder_backward(pb, L.MODE_FULL, op, dxn, cls_only=False, dpatches=None, replaced=mp.replaced)
-            pl_module.after_backward()
-
-        value = _DeferredBackward.apply(pl_module.grad_anchor, value, backward, pl_module.grad_prescale())
+        value = _pred_head_backward(pl_module, value, pb, op, lambda g, dxn: eng.mpp_backward(mp, 1.0, g, dxn, with_grads=True),
+                                    replaced=mp.replaced)
     labels = mpp_image_labels(mp)
     logits = None
     if cfg.get("mpp_return_logits", False) or not (torch.is_grad_enabled() or pl_module.training):
         ma = eng.mpp_bufs(pb.B, "mpp_dense", d.P)
         ma.labels.copy_(mp.labels)
         ma.masked, ma.replaced = mp.masked, mp.replaced
-        ma.rows = ma.cap
-        check(lib.rmcl_mpp_compact(P(ma.labels), P(ma.masked), pb.B, d.P, d.L, N, 1, ma.cap, P(ma.idx), P(ma.lab), P(ma.count), stream_ptr()),
-              "mpp_compact")
+        eng.mpp_compact(ma, pb, all_rows=True)
         eng.mpp_forward(ma, pb.xn)
         logits = eng.mpp_logits(ma, pb.B * (d.P + 1)).view(pb.B, d.P + 1, 3, 256)
-    ret = {"mpp_loss": value, "mpp_logits": logits, "mpp_labels": labels}
-    phase = "train" if pl_module.training else "val"
-    # Accuracy (gadgets/my_metrics.py:5-28): correct / total over the labelled (row, channel) pairs, per step and over the epoch
-    acc = getattr(pl_module, "mpp_epoch_counts", None)
-    if acc is None:
-        acc = pl_module.mpp_epoch_counts = {}
-    if phase not in acc:
-        acc[phase] = torch.zeros(2, dtype=torch.float32, device=eng.device)
-    acc[phase] += stats[1:3]
-    pl_module.log(f"mpp/{phase}/loss", value.detach())
-    pl_module.log(f"mpp/{phase}/accuracy", stats[1] / stats[2])
-    if _em(pl_module) is not None:
-        _metric(pl_module, f"{phase}_mpp_accuracy").update_counts(stats[1:2], stats[2:3])
-        _metric(pl_module, f"{phase}_mpp_loss").update(value.detach(), gate=stats[2:3])
-        _em(pl_module).flush()
-    return ret
+    _pred_head_report(pl_module, "mpp", value, stats)
+    return {"mpp_loss": value, "mpp_logits": logits, "mpp_labels": labels}
 
 
 def compute_moco_contrastive(pl_module, batch):

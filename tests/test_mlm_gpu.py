@@ -65,7 +65,7 @@ def _kernel_case(n, V, seed, tie=False, D=D):
     return h, specs, arena, w, xn, labels.view(B, Lt), N
 
 
-def _run_kernels(h, arena, xn, labels, N, dtype, gscale=1.0, want_logits=True):
+def _run_kernels(h, arena, xn, labels, N, dtype, gscale=1.0, want_logits=True, with_dxn=True):
     B, Lt = labels.shape
     Mt = B * Lt
     n = int((labels != -100).sum())
@@ -81,7 +81,7 @@ def _run_kernels(h, arena, xn, labels, N, dtype, gscale=1.0, want_logits=True):
     ldv = (h.V + 127) // 128 * 128
     wT = torch.empty(h.D, ldv, dtype=torch.bfloat16 if dt == L.BF16 else torch.float32, device=DEV)
     G = torch.zeros_like(a)
-    dxn = torch.zeros(xn.shape, device=DEV)
+    dxn = torch.zeros(xn.shape, device=DEV) if with_dxn else None
     x, lb = xn.to(DEV), labels.to(DEV).contiguous()
     gs = torch.tensor([gscale], device=DEV)
     check(lib.rmcl_mlm_compact(P(lb), Mt, Lt, N, h.V, 0, P(idx), P(lab), P(cnt), stream_ptr()))
@@ -205,6 +205,20 @@ def test_all_ignored_batch_kernels(dtype):
     assert int(r["cnt"]) == 0 and bool(torch.isnan(r["stats"][0])) and float(r["stats"][2]) == 0
     assert torch.count_nonzero(r["G"]) == 0 and torch.count_nonzero(r["dxn"]) == 0
     assert bool(torch.isfinite(r["G"]).all()) and bool(torch.isfinite(r["dxn"]).all())
+
+
+def test_backward_without_dxn_leaves_the_same_gradient_arena():
+    """dxn = NULL: the transform backward launches neither the dx = da Wt GEMM nor the scatter (nobody reads dx), and every head
+    gradient holds the bits of a call with dxn.  The module's smallest case: one labelled row, rows = 128, V = 1000, D = 256."""
+    h, specs, arena, w, xn, labels, N = _kernel_case(1, 1000, 1000 + 1 + 1000 + 256, D=256)
+    for dtype in ("f32", "bf16"):
+        a = _run_kernels(h, arena, xn, labels, N, dtype, want_logits=False)
+        b = _run_kernels(h, arena, xn, labels, N, dtype, want_logits=False, with_dxn=False)
+        assert a["rows"] == 128 and b["dxn"] is None and torch.count_nonzero(a["dxn"]) > 0
+        for name, off, shape in specs:
+            sl = slice(off, off + w[name].numel())
+            assert torch.count_nonzero(a["G"][sl]) > 0, name
+        assert torch.equal(a["G"], b["G"]), dtype
 
 
 # ---- module -------------------------------------------------------------------------------------------------------------

@@ -13,8 +13,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robust-multimodal-contrastive-learning_amd", "csrc", "mlm.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-x", "hip", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include")]
-KERNELS = ("mlm_compact_kernel", "mlm_gather_kernel", "mlm_scatter_kernel", "mlm_gelu_ln_fwd_kernel", "mlm_gelu_ln_bwd_kernel",
-           "mlm_param_grad_kernel", "mlm_transpose_kernel", "mlm_dec_fwd_kernel", "mlm_dec_finish_kernel", "mlm_stats_kernel",
+# (the gather / scatter and the transform kernels are csrc/head_transform.hip's: tests/test_head_transform_isa_cpu.py)
+KERNELS = ("mlm_compact_kernel", "mlm_transpose_kernel", "mlm_dec_fwd_kernel", "mlm_dec_finish_kernel", "mlm_stats_kernel",
            "mlm_dec_bwd_w_kernel", "mlm_dec_bwd_h_kernel", "mlm_dh_reduce_kernel", "mlm_logits_kernel")
 # the bf16 instantiations (operand type unsigned short: "It" in the mangled name) of the kernels that multiply by decoder.weight
 DECODER_BF16 = ("mlm_dec_fwd_kernelItLi6E", "mlm_dec_bwd_w_kernelItLi6E", "mlm_dec_bwd_h_kernelItLi6E", "mlm_logits_kernelItLi6E")
