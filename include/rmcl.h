@@ -467,6 +467,29 @@ int rmcl_mpp_logits(const rmcl_mpp_head* h, float* ws, int rows, int rows_out, f
  * 1 <= B <= 65536, 1 <= W <= 4096, 1 <= L <= 4096, 4 <= D <= 8192 with D % 4 == 0, row0 >= 0, row_step >= 1.                      */
 int rmcl_word_saliency(const float* g, const int32_t* spans, float* out, int B, int W, int L, int D, int row0, int row_step, void* stream);
 
+/* ---- Row top-k (the prediction API: masked-token candidates, VQA answers, retrieval lists) ---------------------------------
+ * For every row of the row-major fp32 matrix x [R, C] with pitch ld >= C (in elements): the k largest entries in descending order into
+ * idx [R, k] (column, int32) and val [R, k] (the selected inputs, bit for bit).
+ *   order   larger value first; equal values go to the smaller column; -inf is an ordinary value that sorts last; a NaN is never
+ *           selected.  A row with fewer than k selectable columns fills the remaining slots with idx -1, val -inf, prob 0.
+ *   mode    RMCL_TOPK_RAW      prob is not written.
+ *           RMCL_TOPK_SOFTMAX  prob = exp(val - lse_row), lse_row the log-sum-exp of the row's selectable columns, formed in the same
+ *                              launch with a running maximum in fp32 and a fixed order (entries of +-80 in one row do not overflow);
+ *                              written to lse [R] when that pointer is given.  A row without a finite column has lse -inf; a selected
+ *                              -inf column has prob 0.
+ *           RMCL_TOPK_SIGMOID  prob = 1 / (1 + exp(-val)).
+ *           prob [R, k] may be NULL in every mode; lse is written in SOFTMAX mode only.
+ * Any ld >= C and any 4-byte aligned x are accepted: 16-byte loads are taken from the first 16-byte boundary of each row, the ragged head
+ * and tail are read column by column, and nothing outside [row, row + C) is read.  One workgroup per row, one owner per output, no
+ * atomics, no scratch, no workspace: two calls on the same input give the same bytes.  R == 0 returns 0 without a launch.  Returns -1
+ * before any launch for a NULL x / idx / val, an unknown mode, C < 1, ld < C, k outside 1 .. min(C, RMCL_TOPK_MAX), R < 0 or a
+ * misaligned x.                                                                                                                       */
+#define RMCL_TOPK_MAX 32
+#define RMCL_TOPK_RAW 0
+#define RMCL_TOPK_SOFTMAX 1
+#define RMCL_TOPK_SIGMOID 2
+int rmcl_rows_topk(const float* x, int64_t ld, int R, int C, int k, int mode, int32_t* idx, float* val, float* prob, float* lse, void* stream);
+
 /* One joint text+image encoder forward up to transformer.norm: replaces ViLTransformerSS.infer /
  * infer_k (vilt_module.py:275-418) minus the pooler.  params32: fp32 arena; params_lp: bf16
  * shadow arena (NULL when dtype is F32).  text_ids/text_mask [B,L] int64; patches [B*P,patch_k]

@@ -4,3 +4,11 @@
 used for device memory, streams and ``torch.distributed`` only.  There is no CPU fallback:
 importing :mod:`rmcl_amd.runtime` fails loudly when the HIP library is missing."""
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # ``from rmcl_amd import Predictor``: resolved on first use, so that importing the package alone still loads neither torch nor the library
+    if name == "Predictor":
+        from .predict import Predictor
+        return Predictor
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

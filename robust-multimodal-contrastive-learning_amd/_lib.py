@@ -95,6 +95,7 @@ class StepCtl(C.Structure):
 
 METRIC_SCALAR, METRIC_PAIR, METRIC_ROWSUM, METRIC_ROWMEAN, METRIC_MATCH, METRIC_ARGMAX_MATCH = range(6)   # include/rmcl.h RMCL_METRIC_*
 METRIC_INVERT, METRIC_MAX_OPS, METRIC_MAX_GROUPS = 1, 8, 4
+TOPK_RAW, TOPK_SOFTMAX, TOPK_SIGMOID, TOPK_MAX = 0, 1, 2, 32                                              # include/rmcl.h RMCL_TOPK_*
 
 
 class MetricOp(C.Structure):
@@ -131,6 +132,7 @@ def _load():
     lib.rmcl_mpp_labels_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]
     lib.rmcl_metrics_update.argtypes = [C.c_void_p, C.c_int, C.POINTER(MetricOps), C.c_void_p]
+    lib.rmcl_rows_topk.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -155,6 +157,7 @@ EXPORTS = (
     "rmcl_encoder_forward_mpp", "rmcl_encoder_backward_mpp", "rmcl_visual_embed_mpp",
     "rmcl_word_saliency",
     "rmcl_metrics_update",
+    "rmcl_rows_topk",
 )
 
 

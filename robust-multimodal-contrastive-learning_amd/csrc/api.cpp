@@ -565,4 +565,14 @@ int rmcl_word_saliency(const float* g, const int32_t* spans, float* out, int B, 
   return rmcl_word_saliency_launch(g, spans, out, B, W, L, D, row0, row_step, (hipStream_t)stream);
 }
 
+int rmcl_rows_topk(const float* x, int64_t ld, int R, int C, int k, int mode, int32_t* idx, float* val, float* prob, float* lse, void* stream) {
+  RMCL_REQUIRE(x && idx && val, "rows_topk: NULL argument");
+  RMCL_REQUIRE(mode == RMCL_TOPK_RAW || mode == RMCL_TOPK_SOFTMAX || mode == RMCL_TOPK_SIGMOID, "rows_topk: unknown mode");
+  RMCL_REQUIRE(R >= 0 && C >= 1 && ld >= C && k >= 1 && k <= RMCL_TOPK_MAX && k <= C,
+               "rows_topk: bad shape (R >= 0, 1 <= C <= ld, 1 <= k <= min(C, RMCL_TOPK_MAX))");
+  RMCL_REQUIRE(((uintptr_t)x & 3) == 0, "rows_topk: x is not 4-byte aligned");
+  if (R == 0) return 0;
+  return rmcl_rows_topk_launch(x, (long)ld, R, C, k, mode, idx, val, prob, lse, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -191,3 +191,5 @@ int rmcl_rank_assemble(const float* embeds, const int* masks, const int* img_of,
                        const float* vtype1, float* x, int* co, int B, int P, int L, int N, int D, hipStream_t s);
 // txtatk.hip: word saliency of the text attack on the fine-tuning tasks (one wave per (sentence, word))
 int rmcl_word_saliency_launch(const float* g, const int* spans, float* out, int B, int W, int L, int D, int row0, int row_step, hipStream_t s);
+// topk.hip: the k first maxima of every row (one workgroup per row; the caller has checked the arguments, R >= 1)
+int rmcl_rows_topk_launch(const float* x, long ld, int R, int C, int k, int mode, int* idx, float* val, float* prob, float* lse, hipStream_t s);

@@ -1167,6 +1167,39 @@ class Engine:
         check(lib.rmcl_word_saliency(P(g), P(spans), P(out), B, W, L_, D, row0, row_step, stream_ptr()), "word_saliency")
         return out
 
+    # ---- row top-k of the prediction API (include/rmcl.h rmcl_rows_topk) -----------------------------------------------------
+    TOPK_MODES = {"raw": L.TOPK_RAW, "softmax": L.TOPK_SOFTMAX, "sigmoid": L.TOPK_SIGMOID}
+
+    def rows_topk(self, x: torch.Tensor, k: int, mode: str = "raw", want_lse: bool = False):
+        """(idx [R, k] int32, val [R, k], prob [R, k] or None for "raw"[, lse [R] with want_lse]) of a 2-D fp32 device tensor whose last
+        dimension is contiguous; the row stride is read from the tensor, so a column slice or a pitched view needs no copy.  Larger
+        value first, ties to the smaller column, NaN never selected; slots a row cannot fill hold idx -1, val -inf, prob 0.  No host
+        synchronisation.  Shape and argument errors are ValueErrors raised here, before the launch."""
+        if mode not in Engine.TOPK_MODES:
+            raise ValueError(f"rows_topk: mode must be one of {sorted(Engine.TOPK_MODES)} (got {mode!r})")
+        if want_lse and mode != "softmax":
+            raise ValueError("rows_topk: want_lse needs mode='softmax' (the log-sum-exp is formed by that mode's launch)")
+        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError("rows_topk: x must be a 2-D fp32 tensor")
+        if not x.is_cuda:
+            raise ValueError("rows_topk: x must be on the device (rmcl_amd has no CPU path)")
+        R, Cn = int(x.shape[0]), int(x.shape[1])
+        k = int(k)
+        if Cn < 1 or k < 1 or k > min(Cn, L.TOPK_MAX):
+            raise ValueError(f"rows_topk: k must be in 1 .. min(columns, {L.TOPK_MAX}) (k = {k}, columns = {Cn})")
+        if Cn > 1 and x.stride(1) != 1:
+            raise ValueError("rows_topk: the last dimension of x must be contiguous (take the top-k of a transposed matrix on a contiguous copy)")
+        ld = int(x.stride(0)) if R > 1 else Cn
+        if ld < Cn:
+            raise ValueError(f"rows_topk: rows of x overlap (row stride {ld} < {Cn} columns)")
+        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=x.device)
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)
+        idx, val = i32(R, k), f32(R, k)
+        prob = None if mode == "raw" else f32(R, k)
+        lse = f32(R) if want_lse else None
+        check(lib.rmcl_rows_topk(P(x), I64(ld), R, Cn, k, Engine.TOPK_MODES[mode], P(idx), P(val), P(prob), P(lse), stream_ptr()), "rows_topk")
+        return (idx, val, prob, lse) if want_lse else (idx, val, prob)
+
     # ---- MLM head (include/rmcl.h rmcl_mlm_*) ------------------------------------------------------------------------
     def mlm_bufs(self, B: int, tag: str) -> MlmBuffers:
         return self._head_buffers(MlmBuffers, B, tag)
