@@ -490,6 +490,40 @@ int rmcl_word_saliency(const float* g, const int32_t* spans, float* out, int B, 
 #define RMCL_TOPK_SIGMOID 2
 int rmcl_rows_topk(const float* x, int64_t ld, int R, int C, int k, int mode, int32_t* idx, float* val, float* prob, float* lse, void* stream);
 
+/* ---- Word-patch alignment maps (the prediction API: the heat map of the reference's demo.py:86-151) --------------------------
+ * rmcl_ipot_plan_f32: IPOT (objectives.py:46-76 with k = 1) shaped for long runs (the demo's 1000 iterations).  Inputs and output
+ * are those of rmcl_ipot_f32: cost [B, Lt, ld] f32 as rmcl_wpa_cost_finish leaves it (ld >= Li), txt_valid [B, Lt] / img_valid [B, Li]
+ * int32, T [B, Li, Lt] like the reference's ipot().  Every joint-pad position of T is exactly zero; a sample without a valid text
+ * token or without a valid image slot gets T = 0.  One 256-thread workgroup per sample, the plan in registers (thread n owns row n,
+ * and row n + 256 when Li > 256), two barriers per iteration, no atomics, no scratch, no workspace, a fixed summation order
+ * (csrc/align.hip; tests/align_ref.py restates it): two calls give the same bytes.  T <- (delta * (A * T)) * sigma.
+ * Returns -1 before any launch, with a message naming the limit, unless 1 <= Lt <= RMCL_IPOT_PLAN_MAX_LT,
+ * 1 <= Li <= RMCL_IPOT_PLAN_MAX_LI, 1 <= iters <= RMCL_IPOT_PLAN_MAX_ITERS and beta > 0.  B == 0 returns 0 without a launch.      */
+#define RMCL_IPOT_PLAN_MAX_LT 40
+#define RMCL_IPOT_PLAN_MAX_LI 512
+#define RMCL_IPOT_PLAN_MAX_ITERS 10000
+int rmcl_ipot_plan_f32(const float* cost, const int32_t* txt_valid, const int32_t* img_valid, float* T, int B, int Lt, int Li, int ld,
+                       float beta, int iters, void* stream);
+/* rmcl_align_heat: a plan T [B, Li, Lt] to patch grids, heat maps and alpha bytes.  patch_index [B, Li - 1] int32: the grid cell
+ * h * W + w of image slot 1 + i (slot 0, the image cls row, is dropped); an entry outside [0, H W) writes nothing, and the entries
+ * inside it must be distinct per sample.
+ *   grid [B, Lt, H, W] f32   T[b, 1 + i, m] at cell patch_index[b, i]; every other cell 0.
+ *   heat [B, Lt, H, W] f32   the demo's arithmetic over the whole grid: z = (grid - mean) / std (unbiased), clip(z, 1, 3),
+ *                            (c - min) / (max - min).  Mean, variance and extrema are accumulated in fp64 from the fp32 cells in a
+ *                            fixed order; heat is rounded to fp32 once.
+ *   flat [B, Lt] int32       1 where the demo would divide by zero: txt_valid[b, m] == 0, H W < 2, std == 0, or all clipped values
+ *                            equal.  Such a position has heat = 0 (a deviation from the demo, which produces NaN there).
+ *   alpha [B, Hout, Wout] uint8 (may be NULL; then token / tables are not read)   for position m = token[b] of sample b:
+ *                            uint8(heat * 255) - the fp32 product, truncated like np.uint8 - of cell (tables[y], tables[Hout + x]):
+ *                            tables [Hout + Wout] int32 are PIL's NEAREST source indices of the rows, then of the columns (entries are
+ *                            clamped to the grid).  alpha[b] is written only when 0 <= token[b] < Lt.
+ * One workgroup per (sample, position), one owner per output, no atomics, no scratch.  Returns -1 before any launch for a NULL
+ * operand, B outside 0 .. 65535, Lt < 1, Li < 1, H W outside 1 .. RMCL_ALIGN_MAX_CELLS or an alpha extent outside 1 .. 16384.     */
+#define RMCL_ALIGN_MAX_CELLS 4096
+int rmcl_align_heat(const float* T, const int32_t* patch_index, const int32_t* txt_valid, int B, int Lt, int Li, int H, int W, float* grid,
+                    float* heat, int32_t* flat, const int32_t* token, const int32_t* tables, int Hout, int Wout, uint8_t* alpha,
+                    void* stream);
+
 /* One joint text+image encoder forward up to transformer.norm: replaces ViLTransformerSS.infer /
  * infer_k (vilt_module.py:275-418) minus the pooler.  params32: fp32 arena; params_lp: bf16
  * shadow arena (NULL when dtype is F32).  text_ids/text_mask [B,L] int64; patches [B*P,patch_k]

@@ -96,6 +96,7 @@ class StepCtl(C.Structure):
 METRIC_SCALAR, METRIC_PAIR, METRIC_ROWSUM, METRIC_ROWMEAN, METRIC_MATCH, METRIC_ARGMAX_MATCH = range(6)   # include/rmcl.h RMCL_METRIC_*
 METRIC_INVERT, METRIC_MAX_OPS, METRIC_MAX_GROUPS = 1, 8, 4
 TOPK_RAW, TOPK_SOFTMAX, TOPK_SIGMOID, TOPK_MAX = 0, 1, 2, 32                                              # include/rmcl.h RMCL_TOPK_*
+IPOT_PLAN_MAX_LT, IPOT_PLAN_MAX_LI, IPOT_PLAN_MAX_ITERS, ALIGN_MAX_CELLS = 40, 512, 10000, 4096           # include/rmcl.h RMCL_IPOT_PLAN_* / RMCL_ALIGN_*
 
 
 class MetricOp(C.Structure):
@@ -158,6 +159,7 @@ EXPORTS = (
     "rmcl_word_saliency",
     "rmcl_metrics_update",
     "rmcl_rows_topk",
+    "rmcl_ipot_plan_f32", "rmcl_align_heat",
 )
 
 

@@ -575,4 +575,32 @@ int rmcl_rows_topk(const float* x, int64_t ld, int R, int C, int k, int mode, in
   return rmcl_rows_topk_launch(x, (long)ld, R, C, k, mode, idx, val, prob, lse, (hipStream_t)stream);
 }
 
+int rmcl_ipot_plan_f32(const float* cost, const int32_t* txt_valid, const int32_t* img_valid, float* T, int B, int Lt, int Li, int ld,
+                       float beta, int iters, void* stream) {
+  RMCL_REQUIRE(cost && txt_valid && img_valid && T, "ipot_plan: NULL argument");
+  RMCL_REQUIRE(Lt >= 1 && Lt <= RMCL_IPOT_PLAN_MAX_LT, "ipot_plan: Lt must be in 1 .. 40 (RMCL_IPOT_PLAN_MAX_LT)");
+  RMCL_REQUIRE(Li >= 1 && Li <= RMCL_IPOT_PLAN_MAX_LI, "ipot_plan: Li must be in 1 .. 512 (RMCL_IPOT_PLAN_MAX_LI)");
+  RMCL_REQUIRE(iters >= 1 && iters <= RMCL_IPOT_PLAN_MAX_ITERS, "ipot_plan: iters must be in 1 .. 10000 (RMCL_IPOT_PLAN_MAX_ITERS)");
+  RMCL_REQUIRE(beta > 0.f, "ipot_plan: beta must be > 0");                                  // (a NaN fails too)
+  RMCL_REQUIRE(B >= 0 && ld >= Li, "ipot_plan: bad shape (B >= 0, ld >= Li)");
+  if (B == 0) return 0;
+  return rmcl_ipot_plan_launch(cost, txt_valid, img_valid, T, B, Lt, Li, ld, beta, iters, (hipStream_t)stream);
+}
+
+int rmcl_align_heat(const float* T, const int32_t* patch_index, const int32_t* txt_valid, int B, int Lt, int Li, int H, int W, float* grid,
+                    float* heat, int32_t* flat, const int32_t* token, const int32_t* tables, int Hout, int Wout, uint8_t* alpha,
+                    void* stream) {
+  RMCL_REQUIRE(T && txt_valid && grid && heat && flat, "align_heat: NULL argument");
+  RMCL_REQUIRE(B >= 0 && B <= 65535 && Lt >= 1 && Lt <= 65535 && Li >= 1, "align_heat: bad shape (0 <= B <= 65535, 1 <= Lt <= 65535, Li >= 1)");
+  RMCL_REQUIRE(patch_index || Li == 1, "align_heat: NULL patch_index");
+  RMCL_REQUIRE(H >= 1 && W >= 1 && (long)H * W <= RMCL_ALIGN_MAX_CELLS, "align_heat: the grid must have 1 .. 4096 cells (RMCL_ALIGN_MAX_CELLS)");
+  if (alpha) {
+    RMCL_REQUIRE(token && tables, "align_heat: alpha needs token and tables (NULL argument)");
+    RMCL_REQUIRE(Hout >= 1 && Wout >= 1 && Hout <= 16384 && Wout <= 16384, "align_heat: the alpha extent must be in 1 .. 16384 per side");
+  }
+  if (B == 0) return 0;
+  return rmcl_align_heat_launch(T, patch_index, txt_valid, B, Lt, Li, H, W, grid, heat, flat, token, tables, Hout, Wout, alpha,
+                                (hipStream_t)stream);
+}
+
 }  // extern "C"

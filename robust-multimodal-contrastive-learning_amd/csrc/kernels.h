@@ -193,3 +193,10 @@ int rmcl_rank_assemble(const float* embeds, const int* masks, const int* img_of,
 int rmcl_word_saliency_launch(const float* g, const int* spans, float* out, int B, int W, int L, int D, int row0, int row_step, hipStream_t s);
 // topk.hip: the k first maxima of every row (one workgroup per row; the caller has checked the arguments, R >= 1)
 int rmcl_rows_topk_launch(const float* x, long ld, int R, int C, int k, int mode, int* idx, float* val, float* prob, float* lse, hipStream_t s);
+// align.hip: IPOT with the plan in registers (one workgroup per sample) and the heat maps of a plan (one workgroup per (sample, text
+// position)); the callers have checked the arguments
+int rmcl_ipot_plan_launch(const float* cost, const int* txt_valid, const int* img_valid, float* T, int B, int Lt, int Li, int ld, float beta,
+                          int iters, hipStream_t s);
+int rmcl_align_heat_launch(const float* T, const int* patch_index, const int* txt_valid, int B, int Lt, int Li, int H, int W, float* grid,
+                           float* heat, int* flat, const int* token, const int* tables, int Hout, int Wout, unsigned char* alpha,
+                           hipStream_t s);

@@ -1,7 +1,9 @@
-"""Using a trained model: the predictions of the reference's ``demo.py`` (greedy ``[MASK]`` filling) and ``demo_vqa.py`` (the best VQA
-answer), and the ranked retrieval lists behind ``compute_irtr_recall`` - on the passes and head launchers the training path already
-runs (``Engine.mlm_bind(all_rows=True)`` -> ``mlm_forward`` -> ``mlm_logits``, ``vqa_forward``) plus one row kernel that all of them
-share, ``Engine.rows_topk`` (include/rmcl.h rmcl_rows_topk).  DESIGN.md "Prediction API", INTEGRATION.md "Predictions".
+"""Using a trained model: the predictions of the reference's ``demo.py`` (greedy ``[MASK]`` filling, word-patch alignment heat maps) and
+``demo_vqa.py`` (the best VQA answer), and the ranked retrieval lists behind ``compute_irtr_recall`` - on the passes and head launchers
+the training path already runs (``Engine.mlm_bind(all_rows=True)`` -> ``mlm_forward`` -> ``mlm_logits``, ``vqa_forward``, the cost chain
+of compute_itm_wpa) plus one row kernel that the first three share, ``Engine.rows_topk`` (include/rmcl.h rmcl_rows_topk), and the two
+alignment kernels ``Engine.ipot_plan`` / ``Engine.align_heat`` (rmcl_ipot_plan_f32, rmcl_align_heat).  DESIGN.md "Prediction API",
+INTEGRATION.md "Predictions".
 
 Every call runs under ``torch.no_grad()`` with the model in eval mode and puts the model's mode flags, the engine's dropout switch and
 its pass counter back afterwards: a training step taken after a prediction is the step that would have been taken without it."""
@@ -14,6 +16,7 @@ import torch
 
 from . import _lib as L
 from .attack.word_substitution import load_tokenizer
+from .runtime import stream_ptr
 from .task_loss import HEAD_ROWS
 
 
@@ -213,6 +216,83 @@ class Predictor:
         ret = {"ids": out_i, "logits": out_z, "scores": out_p}
         if self.id2answer is not None:
             ret["answers"] = [[self.id2answer[int(a)] for a in row] for row in out_i.tolist()]
+        return ret
+
+    # ---- word-patch alignment ----------------------------------------------------------------------------------------------
+    def align(self, image, text=None, text_ids=None, text_masks=None, token=None, iterations: int = 1000, beta: float = 0.1, size=None):
+        """Where the words of a sentence land on the image: the heat maps of the reference's demo.py:86-151.  One MODE_INFER pass, the
+        demo's masks (``[CLS]``, the last valid text token and the image cls slot are dropped), the masked cosine cost of compute_itm_wpa
+        on the normalised features, the transport plan of ``ipot(cost, ..., beta, iterations, k = 1)`` (``Engine.ipot_plan``), and per text
+        position its plan column scattered to the patch grid, standardised, clipped to [1, 3] sigma and min-max normalised
+        (``Engine.align_heat``).  Needs no head.
+
+        Returns a dict, tensors on the device: ``plan`` [B, Li, Lt]; ``cost`` [B, Lt, Li] (the masked cosine cost behind it); ``grid`` / ``heat`` [B, Lt, H, W]; ``flat`` [B, Lt] int32 - 1 where
+        the demo's arithmetic divides by zero (a position the masks drop, or a map whose clipped values are all equal): ``heat`` is 0
+        there, not NaN; ``grid_hw`` = (H, W); ``tokens`` (per sample the token strings; with a tokenizer); and with ``token`` (a text
+        position, or one per sample) ``alpha`` [B, Hout, Wout] uint8: ``uint8(heat * 255)`` of that position enlarged like PIL's NEAREST
+        to ``size`` = (height, width), default the pixel extent of the bound image batch."""
+        ids, masks = self._text(text, text_ids, text_masks)
+        B, Lt = int(ids.shape[0]), int(ids.shape[1])
+        iterations, beta = int(iterations), float(beta)
+        if not 1 <= iterations <= L.IPOT_PLAN_MAX_ITERS:
+            raise ValueError(f"iterations must be in 1 .. {L.IPOT_PLAN_MAX_ITERS} (got {iterations})")
+        if not beta > 0.0:
+            raise ValueError(f"beta must be > 0 (got {beta})")
+        if Lt > L.IPOT_PLAN_MAX_LT:
+            raise ValueError(f"align takes a max_text_len of at most {L.IPOT_PLAN_MAX_LT} (this model: {Lt})")
+        if token is not None:
+            token = [int(token)] * B if isinstance(token, int) else [int(v) for v in token]
+            if len(token) != B or any(not 0 <= v < Lt for v in token):
+                raise ValueError(f"token must be a text position in 0 .. {Lt - 1}, or one per sample ({B} samples; got {token})")
+        if size is not None and not (len(size) == 2 and all(1 <= int(v) <= 16384 for v in size)):
+            raise ValueError(f"size must be (height, width) with both in 1 .. 16384 (got {size})")
+        eng = self.eng
+        with self._eval():
+            pb = eng.bind_batch(ids, masks, self._image(image, B), tag="predict")
+            d = pb.d
+            Li, D = d.P + 1, d.D
+            N = Lt + Li
+            if Li > L.IPOT_PLAN_MAX_LI:
+                raise ValueError(f"align takes at most {L.IPOT_PLAN_MAX_LI - 1} image patches (this batch: {d.P})")
+            op = eng.make_operand(pb, out=pb.patchesT_full)
+            eng.encoder_forward(pb, key=False, mode=L.MODE_INFER, patchesT=op)
+            dev = eng.device
+            # masks (demo.py:97-105): drop [CLS], the last valid text token and the image cls slot
+            txt_mask = pb.text_mask.bool().clone()
+            lens = txt_mask.sum(dim=1)
+            txt_mask[torch.arange(B, device=dev), lens - 1] = False
+            txt_mask[:, 0] = False
+            img_mask = pb.co_mask[:, Lt:].bool().clone()
+            img_mask[:, 0] = False
+            txt_valid, img_valid = txt_mask.to(torch.int32).contiguous(), img_mask.to(torch.int32).contiguous()
+            # the cost chain of compute_itm_wpa (vilt/modules/objectives.py), launch for launch
+            st = stream_ptr()
+            ld, M = (Li + 3) // 4 * 4, B * N
+            xhat, norms = torch.empty(M, D, device=dev), torch.empty(M, device=dev)
+            L.check(L.lib.rmcl_l2norm_rows_fwd(L.P(pb.xn), L.P(xhat), L.P(norms), M, D, L.F(1e-5), st), "l2norm")
+            cost = torch.zeros(B, Lt, ld, device=dev)
+            L.check(L.lib.rmcl_gemm_batched(L.P(xhat), L.P(xhat[Lt:]), L.P(cost), Lt, Li, D, L.I64(D), L.I64(D), ld, L.F(1.0), B, L.I64(N * D),
+                                            L.I64(N * D), L.I64(Lt * ld), L.F32, L.F32, 1, 1, st), "cosine sim")
+            L.check(L.lib.rmcl_wpa_cost_finish(L.P(cost), L.P(txt_valid), L.P(img_valid), B, Lt, Li, ld, st), "cost_finish")
+            plan = eng.ipot_plan(cost, txt_valid, img_valid, beta, iterations)
+            # the grid cell of every image slot, as infer builds patch_index (vilt_module.py:462-470)
+            geom = pb.geom
+            if geom is None:
+                gh = gw = int(eng.cfg["image_size"]) // int(eng.cfg["patch_size"])
+                pidx = torch.arange(gh * gw, dtype=torch.int32, device=dev).repeat(B, 1)
+                extent = (int(eng.cfg["image_size"]),) * 2
+            else:
+                gh, gw = int(geom.gh), int(geom.gw)
+                kept = torch.arange(d.P, device=dev)[None, :] < geom.counts[:, None]
+                pidx = torch.where(kept, geom.sel[:, :d.P], torch.full_like(geom.sel[:, :d.P], -1))
+                extent = (int(geom.shape[2]), int(geom.shape[3]))
+            grid, heat, flat, alpha = eng.align_heat(plan, pidx.contiguous(), txt_valid, (gh, gw), token,
+                                                     (extent if size is None else size) if token is not None else None)
+        ret = {"plan": plan, "grid": grid, "heat": heat, "flat": flat, "grid_hw": (gh, gw), "cost": cost[:, :, :Li]}
+        if alpha is not None:
+            ret["alpha"] = alpha
+        if self.tokenizer is not None:
+            ret["tokens"] = [self.tokenizer.convert_ids_to_tokens(row) for row in ids.tolist()]
         return ret
 
     # ---- retrieval ---------------------------------------------------------------------------------------------------------

@@ -1200,6 +1200,77 @@ class Engine:
         check(lib.rmcl_rows_topk(P(x), I64(ld), R, Cn, k, Engine.TOPK_MODES[mode], P(idx), P(val), P(prob), P(lse), stream_ptr()), "rows_topk")
         return (idx, val, prob, lse) if want_lse else (idx, val, prob)
 
+    # ---- word-patch alignment maps of the prediction API (include/rmcl.h rmcl_ipot_plan_f32, rmcl_align_heat) -----------------
+    def ipot_plan(self, cost: torch.Tensor, txt_valid: torch.Tensor, img_valid: torch.Tensor, beta: float, iters: int) -> torch.Tensor:
+        """The transport plan T [B, Li, Lt] of ``ipot(cost, ..., beta, iters, k = 1)``: cost [B, Lt, ld >= Li] fp32 as
+        rmcl_wpa_cost_finish leaves it, txt_valid [B, Lt] / img_valid [B, Li] int32, all contiguous on the device.  Limit errors are
+        ValueErrors raised here, before the launch."""
+        if not (torch.is_tensor(cost) and cost.dim() == 3 and cost.dtype == torch.float32 and cost.is_cuda and cost.is_contiguous()):
+            raise ValueError("ipot_plan: cost must be a contiguous fp32 device tensor [B, Lt, ld]")
+        B, Lt, ld = (int(v) for v in cost.shape)
+        for name, t in (("txt_valid", txt_valid), ("img_valid", img_valid)):
+            if not (torch.is_tensor(t) and t.dim() == 2 and t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.shape[0] == B):
+                raise ValueError(f"ipot_plan: {name} must be a contiguous int32 device tensor [B = {B}, ...]")
+        Li, iters, beta = int(img_valid.shape[1]), int(iters), float(beta)
+        if txt_valid.shape[1] != Lt or not 1 <= Lt <= L.IPOT_PLAN_MAX_LT:
+            raise ValueError(f"ipot_plan: the text length must be in 1 .. {L.IPOT_PLAN_MAX_LT} and that of txt_valid (cost has {Lt}, txt_valid {txt_valid.shape[1]})")
+        if not 1 <= Li <= min(ld, L.IPOT_PLAN_MAX_LI):
+            raise ValueError(f"ipot_plan: the image length must be in 1 .. {L.IPOT_PLAN_MAX_LI} and at most the pitch of cost (got {Li}, pitch {ld})")
+        if not 1 <= iters <= L.IPOT_PLAN_MAX_ITERS:
+            raise ValueError(f"ipot_plan: iterations must be in 1 .. {L.IPOT_PLAN_MAX_ITERS} (got {iters})")
+        if not beta > 0.0:
+            raise ValueError(f"ipot_plan: beta must be > 0 (got {beta})")
+        T = torch.empty(B, Li, Lt, dtype=torch.float32, device=cost.device)
+        check(lib.rmcl_ipot_plan_f32(P(cost), P(txt_valid), P(img_valid), P(T), B, Lt, Li, ld, F(beta), iters, stream_ptr()), "ipot_plan")
+        return T
+
+    @staticmethod
+    def nearest_table(src: int, dst: int) -> List[int]:
+        """source index of every output pixel of PIL's NEAREST resize of `src` pixels to `dst`: the centre 0.5 * src / dst advanced by
+        src / dst per pixel IN DOUBLE, accumulated, truncated and cut at src - 1.  (The closed form floor((x + 0.5) * src / dst) differs
+        from PIL's accumulation at some sizes.)"""
+        step = float(src) / float(dst)
+        xo, out = 0.5 * step, []
+        for _ in range(dst):
+            out.append(min(int(xo), src - 1))
+            xo += step
+        return out
+
+    def align_heat(self, plan: torch.Tensor, patch_index: torch.Tensor, txt_valid: torch.Tensor, grid_hw, token=None, size=None):
+        """(grid, heat [B, Lt, H, W] fp32, flat [B, Lt] int32, alpha [B, Hout, Wout] uint8 or None) of a plan [B, Li, Lt] (include/rmcl.h
+        rmcl_align_heat).  patch_index [B, Li - 1] int32: the flat grid cell of every image slot behind the cls slot (negative: none);
+        token: None, or one text position per sample (a list of B ints, on the host) whose alpha bytes are wanted at size = (Hout, Wout)."""
+        H, W = int(grid_hw[0]), int(grid_hw[1])
+        if not (torch.is_tensor(plan) and plan.dim() == 3 and plan.dtype == torch.float32 and plan.is_cuda and plan.is_contiguous()):
+            raise ValueError("align_heat: plan must be a contiguous fp32 device tensor [B, Li, Lt]")
+        B, Li, Lt = (int(v) for v in plan.shape)
+        if H < 1 or W < 1 or H * W > L.ALIGN_MAX_CELLS:
+            raise ValueError(f"align_heat: the grid must have 1 .. {L.ALIGN_MAX_CELLS} cells (got {H} x {W})")
+        if not (patch_index.dtype == torch.int32 and patch_index.is_cuda and patch_index.is_contiguous() and tuple(patch_index.shape) == (B, Li - 1)):
+            raise ValueError(f"align_heat: patch_index must be a contiguous int32 device tensor [{B}, {Li - 1}]")
+        if not (txt_valid.dtype == torch.int32 and txt_valid.is_cuda and txt_valid.is_contiguous() and tuple(txt_valid.shape) == (B, Lt)):
+            raise ValueError(f"align_heat: txt_valid must be a contiguous int32 device tensor [{B}, {Lt}]")
+        dev = plan.device
+        grid = torch.empty(B, Lt, H, W, dtype=torch.float32, device=dev)
+        heat = torch.empty(B, Lt, H, W, dtype=torch.float32, device=dev)
+        flat = torch.empty(B, Lt, dtype=torch.int32, device=dev)
+        alpha = tok = tab = None
+        Ho = Wo = 0
+        if token is not None:
+            token = [int(v) for v in token]
+            if len(token) != B or any(not 0 <= v < Lt for v in token):
+                raise ValueError(f"align_heat: token must hold one text position in 0 .. {Lt - 1} per sample ({B} samples; got {token})")
+            Ho, Wo = (int(size[0]), int(size[1])) if size is not None and len(size) == 2 else (0, 0)
+            if not (1 <= Ho <= 16384 and 1 <= Wo <= 16384):
+                raise ValueError(f"align_heat: size must be (height, width) with both in 1 .. 16384 (got {size})")
+            # the position of every sample and the two index tables: one upload
+            up = self._h2d(torch.tensor(token + Engine.nearest_table(H, Ho) + Engine.nearest_table(W, Wo), dtype=torch.int32))
+            tok, tab = up[:B], up[B:]
+            alpha = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=dev)
+        check(lib.rmcl_align_heat(P(plan), P(patch_index), P(txt_valid), B, Lt, Li, H, W, P(grid), P(heat), P(flat), P(tok), P(tab), Ho, Wo,
+                                  P(alpha), stream_ptr()), "align_heat")
+        return grid, heat, flat, alpha
+
     # ---- MLM head (include/rmcl.h rmcl_mlm_*) ------------------------------------------------------------------------
     def mlm_bufs(self, B: int, tag: str) -> MlmBuffers:
         return self._head_buffers(MlmBuffers, B, tag)
