@@ -663,6 +663,55 @@ int rmcl_pgd_step(const void* grad, int dtype, float* delta, uint32_t* amax_scra
 #define RMCL_PGD_SUM_PREV 2
 int rmcl_pgd_step_fused(const void* grad, int dtype, float* delta, uint32_t* amax_scratch, int B, int64_t per_sample, float lr,
                         float eps, const float* base, void* operand, int operand_dtype, int flags, void* stream);
+/* ---- PGD threat models (csrc/pgd_ball.hip) ------------------------------------------------------------------------------------
+ * Configurable forms of the step above, in the same patch layout: B samples of per_sample fp32 delta elements (per_sample % 4 == 0).
+ * valid (int32 [B], optional): the number of LEADING elements of each sample that belong to real patches (RaggedGeometry.counts[b] *
+ * patch_k); NULL: all of them.  Elements at or beyond valid[b] are pad slots: they always get delta = 0 and operand = cast(base), and
+ * they take part in no maximum and no norm.
+ * scratch: rmcl_pgd_ball_scratch_bytes(B) bytes, 8-byte aligned, need not be cleared: per-block partials (at most 64 per sample and
+ * statistic; slots beyond a launch's block count are neither written nor read).  Sums of squares are accumulated in double in a fixed
+ * order and nothing is accumulated atomically: a repeated call writes the same bytes.
+ *
+ * rmcl_pgd_step_ball: one ascent step, the projection and the next forward's operand.  Per sample, g = grad on the valid elements:
+ *   direction d   RMCL_PGD_DIR_NORMALISED  g / max(max|g|, 1e-8)   (the reference's, the arithmetic of rmcl_pgd_step_fused)
+ *                 RMCL_PGD_DIR_SIGN        sign(g), sign(0) = 0
+ *                 RMCL_PGD_DIR_L2          g / max(||g||_2, 1e-12)
+ *   t = delta_old + lr d                   (flag RMCL_PGD_DELTA_ZERO: delta_old = 0, the buffer is not read)
+ *   projection t' RMCL_PGD_BALL_LINF       clamp(t, +-eps)
+ *                 RMCL_PGD_BALL_L2         t min(1, eps / ||t||_2)
+ *                 eps <= 0                 none
+ *   box, when lo < hi:   x = clamp(base + t', lo, hi), delta_new = x - base, operand = cast(x)
+ *   without a box:       delta_new = t', operand = cast(base + t')
+ * The box runs AFTER the ball: where base lies inside [lo, hi] (the pixelbert normalisation gives [-1, 1] on every valid element)
+ * clamping base + t' moves each element towards base, |delta_new| <= |t'| element by element, so the result stays inside either ball.
+ * The kernel does not check base.  There is no SUM_PREV form: a configured threat model is evaluated on img + delta_K.
+ * base is required with an operand or a box; operand is optional.  The L2 ball takes one more pass over grad and delta (the norm of t).
+ *
+ * rmcl_pgd_random_start: delta_0 and the first operand.  With h = rmcl_rng_hash(rmcl_rng_hash(seed, sample0 + b), i) (csrc/rmcl_common.h)
+ * for element i of sample b, u = (h >> 8) 2^-24 and v = 2u - 1:  L-inf: delta = eps v;  L2: delta = eps v / ||v||_2 over the valid
+ * elements - a point ON the sphere: the radius draw U^(1/n) of a uniform point of the ball is left out, since in n >= 3072 dimensions
+ * P(radius <= 0.99 eps) = 0.99^n < 4e-14.  The box is applied as above.  sample0: global index of the call's first sample, so a
+ * half-batch lane draws what the whole batch would; a restart number is mixed into seed by the caller.
+ *
+ * rmcl_pgd_keep_worst: the per-sample worst case over restarts, decided on the device.  score_new[j * score_stride] is decision j's
+ * score after restart `restart`; decision j owns the rows_per_decision (1 or 2: NLVR2's pair pass) consecutive sample rows
+ * j * G .. j * G + G - 1 of delta / operand.  It takes the new result iff restart == 0 or score_new > best_score[j] (strict; a NaN
+ * never takes except at restart 0): its delta (and operand) rows are copied into best_delta (best_operand) and best_score / best_restart
+ * are updated; every other row and score is left untouched.                                                                        */
+#define RMCL_PGD_DIR_NORMALISED 0
+#define RMCL_PGD_DIR_SIGN 1
+#define RMCL_PGD_DIR_L2 2
+#define RMCL_PGD_BALL_LINF 0
+#define RMCL_PGD_BALL_L2 1
+int64_t rmcl_pgd_ball_scratch_bytes(int B);
+int rmcl_pgd_step_ball(const void* grad, int dtype, float* delta, void* scratch, const int32_t* valid, int B, int64_t per_sample,
+                       float lr, float eps, int direction, int ball, float lo, float hi, const float* base, void* operand,
+                       int operand_dtype, int flags, void* stream);
+int rmcl_pgd_random_start(float* delta, void* scratch, const int32_t* valid, int B, int64_t per_sample, int sample0, uint32_t seed,
+                          float eps, int ball, float lo, float hi, const float* base, void* operand, int operand_dtype, void* stream);
+int rmcl_pgd_keep_worst(const float* score_new, int64_t score_stride, float* best_score, int32_t* best_restart, int restart, int D,
+                        int rows_per_decision, const float* delta, float* best_delta, const void* operand, void* best_operand,
+                        int operand_dtype, int64_t per_sample, void* stream);
 /* sum over (row, pixel) of the channel-wise L2 norm of delta (objectives.py:184); out += sum     */
 int rmcl_delta_channel_norm(const float* delta, float* out, int64_t rows, int C, int pp, void* stream);
 

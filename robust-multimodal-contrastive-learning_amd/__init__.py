@@ -11,4 +11,7 @@ def __getattr__(name):
     if name == "Predictor":
         from .predict import Predictor
         return Predictor
+    if name == "RobustEval":
+        from .robust import RobustEval
+        return RobustEval
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

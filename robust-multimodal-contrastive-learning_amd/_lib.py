@@ -16,6 +16,8 @@ MODE_INFER, MODE_DATA, MODE_FULL = 0, 1, 2
 MODE_CLS_TAIL = 16        # include/rmcl.h RMCL_MODE_CLS_TAIL
 MODE_STREAM_ATTN = 32     # include/rmcl.h RMCL_MODE_STREAM_ATTN
 PGD_DELTA_ZERO, PGD_SUM_PREV = 1, 2   # include/rmcl.h RMCL_PGD_*
+PGD_DIR_NORMALISED, PGD_DIR_SIGN, PGD_DIR_L2 = 0, 1, 2   # include/rmcl.h RMCL_PGD_DIR_*
+PGD_BALL_LINF, PGD_BALL_L2 = 0, 1                        # include/rmcl.h RMCL_PGD_BALL_*
 HEADS_NO_WGRAD = 1                    # include/rmcl.h RMCL_HEADS_NO_WGRAD
 OPTIM_ADAM, OPTIM_SGD = 1, 2          # include/rmcl.h RMCL_OPTIM_*
 EPI_BIAS, EPI_GELU, EPI_SAVE_PREACT, EPI_RESIDUAL, EPI_DGELU, EPI_ATOMIC, EPI_ACCUM, EPI_TANH = 1, 2, 4, 8, 16, 32, 64, 128
@@ -125,7 +127,8 @@ def _load():
     lib.rmcl_last_error.restype = C.c_char_p
     for name in ("rmcl_stash_bytes", "rmcl_workspace_bytes", "rmcl_heads_stash_bytes", "rmcl_infonce_ws_bytes",
                  "rmcl_attention_scratch_elems", "rmcl_attention_stream_stat_elems", "rmcl_ln_fold_elems", "rmcl_bt_stash_floats", "rmcl_bt_loss_ws_floats",
-                 "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats", "rmcl_mpp_ws_floats", "rmcl_randaug_scratch_bytes", "rmcl_grad_stats_ws_bytes"):
+                 "rmcl_vqa_stash_floats", "rmcl_mlm_ws_floats", "rmcl_mpp_ws_floats", "rmcl_randaug_scratch_bytes", "rmcl_grad_stats_ws_bytes",
+                 "rmcl_pgd_ball_scratch_bytes"):
         getattr(lib, name).restype = C.c_int64
     lib.rmcl_grad_stats_ws_bytes.argtypes = [C.c_int64]
     lib.rmcl_randaug_scratch_bytes.argtypes = [C.c_int, C.c_int]
@@ -134,6 +137,12 @@ def _load():
                                        C.c_void_p, C.c_void_p]
     lib.rmcl_metrics_update.argtypes = [C.c_void_p, C.c_int, C.POINTER(MetricOps), C.c_void_p]
     lib.rmcl_rows_topk.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rmcl_pgd_step_ball.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int,
+                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.rmcl_pgd_random_start.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_float,
+                                          C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.rmcl_pgd_keep_worst.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
     return lib
 
 
@@ -144,6 +153,7 @@ EXPORTS = (
     "rmcl_last_error", "rmcl_version", "rmcl_prof_begin", "rmcl_prof_end", "rmcl_tune_set", "rmcl_grad_ready_wait", "rmcl_set_side_stream", "rmcl_set_prefetch_stream", "rmcl_dropout_mask_apply", "rmcl_param_layout", "rmcl_ln_fold_elems", "rmcl_ln_fold", "rmcl_linear_rowstat", "rmcl_linear_lnfold", "rmcl_linear_rowstat_c", "rmcl_linear_lnfold_c", "rmcl_weight_transpose_bf16", "rmcl_stash_bytes", "rmcl_workspace_bytes",
     "rmcl_heads_stash_bytes", "rmcl_im2patch_f32", "rmcl_patch_select", "rmcl_im2patch_sel", "rmcl_image_u8_to_patches", "rmcl_image_resize_u8", "rmcl_randaug_scratch_bytes", "rmcl_randaug_u8", "rmcl_add_cast_f32", "rmcl_shard_sum", "rmcl_encoder_forward", "rmcl_encoder_backward",
     "rmcl_heads_forward", "rmcl_heads_forward2", "rmcl_heads_backward", "rmcl_infonce_ws_bytes", "rmcl_infonce_f32", "rmcl_infonce_split_bf16", "rmcl_pgd_step", "rmcl_pgd_step_fused",
+    "rmcl_pgd_ball_scratch_bytes", "rmcl_pgd_step_ball", "rmcl_pgd_random_start", "rmcl_pgd_keep_worst",
     "rmcl_delta_channel_norm", "rmcl_ema_f32", "rmcl_enqueue_f32", "rmcl_cast_f32", "rmcl_adamw_f32", "rmcl_grad_stats_ws_bytes", "rmcl_grad_stats_f32", "rmcl_adamw_guarded_f32", "rmcl_optim_step_f32", "rmcl_ipot_f32", "rmcl_gemm_batched", "rmcl_l2norm_rows_fwd", "rmcl_l2norm_rows_bwd",
     "rmcl_wpa_cost_finish", "rmcl_wpa_distance", "rmcl_itm_fwd", "rmcl_itm_bwd",
     "rmcl_gemm", "rmcl_gemm_rows_bf16", "rmcl_rows_gather_f32", "rmcl_gemm_chain", "rmcl_l2_prefetch_experiment", "rmcl_gemm_route", "rmcl_gemm_kblk", "rmcl_layernorm_fwd", "rmcl_layernorm_bwd", "rmcl_attention_scratch_elems", "rmcl_attention_fwd",

@@ -316,6 +316,7 @@ class PassBuffers:
         self.delta = f32(B * d.P, d.patch_k)
         self.delta_prev = f32(B * d.P, d.patch_k)
         self.amax = torch.empty(64 * B, dtype=torch.int32, device=dev)      # include/rmcl.h rmcl_pgd_step: 64 partial maxima per sample
+        self.ball = torch.empty(int(lib.rmcl_pgd_ball_scratch_bytes(B)), dtype=torch.uint8, device=dev)   # rmcl_pgd_step_ball's partials
         self.cls = f32(B, d.D)
         self.q = f32(B, d.proj)
         self.k = f32(B, d.proj)
@@ -355,6 +356,8 @@ class PassBuffers:
         self.patches32, self.patchesT, self.patchesT_full = rows(par.patches32, d.P), rows(par.patchesT, d.P), rows(par.patchesT_full, d.P)
         self.gpatch, self.delta, self.delta_prev = rows(par.gpatch, d.P), rows(par.delta, d.P), rows(par.delta_prev, d.P)
         self.amax = rows(par.amax, 64)
+        # (the threat-model scratch is laid out per array, not per sample: a lane has its own 1 280 bytes per sample)
+        self.ball = torch.empty(int(lib.rmcl_pgd_ball_scratch_bytes(B)), dtype=torch.uint8, device=eng.device)
         self.cls, self.q, self.k, self.dq, self.dcls, self.rows = (rows(t, 1) for t in (par.cls, par.q, par.k, par.dq, par.dcls, par.rows))
 
 
@@ -1582,6 +1585,61 @@ class Engine:
         odt = L.F32 if (out is not None and out.dtype == torch.float32) else L.BF16
         check(lib.rmcl_pgd_step_fused(P(pb.gpatch), pb.dtype, P(pb.delta), P(pb.amax), pb.B, I64(per), F(lr), F(eps), P(pb.patches32),
                                       P(out), odt, flags, stream_ptr()), "pgd_step_fused")
+
+    # ---- PGD threat models (include/rmcl.h "PGD threat models", csrc/pgd_ball.hip) ----------------------------------------------
+    def pgd_valid(self, pb: PassBuffers) -> torch.Tensor:
+        """int32 [B]: the leading delta elements of each sample that belong to real patches (None: dense batch, all of them)"""
+        if pb.geom is None:
+            return None
+        if getattr(pb, "_valid_of", None) is not pb.geom:                     # once per bound batch (a bind sets a new geometry object)
+            pb._valid = (pb.geom.counts.to(torch.int64) * pb.d.patch_k).clamp_(max=pb.d.P * pb.d.patch_k).to(torch.int32)
+            pb._valid_of = pb.geom
+        return pb._valid
+
+    @staticmethod
+    def _box(box):
+        return (0.0, 0.0) if box is None else (float(box[0]), float(box[1]))
+
+    def pgd_step_ball(self, pb: PassBuffers, lr: float, eps: float, direction: int, ball: int, box=None, first: bool = False,
+                      out: torch.Tensor = None, valid: torch.Tensor = None):
+        """One step of a configured threat model on ``pb.gpatch``: delta <- project(delta + lr d) with d = g / max|g|, sign(g) or
+        g / ||g||_2 and the L-inf or L2 ball of radius eps, then the pixel box (lo, hi) on patches32 + delta; ``out`` receives the cast of
+        the boxed image in the same pass.  ``first``: the incoming delta is 0 and is not read.  ``valid``: int32 [B] valid element counts
+        (default: the batch's ragged geometry); elements behind them keep delta 0.  There is no sum_prev form."""
+        per = pb.d.P * pb.d.patch_k
+        valid = self.pgd_valid(pb) if valid is None else valid
+        lo, hi = self._box(box)
+        odt = L.F32 if (out is not None and out.dtype == torch.float32) else L.BF16
+        check(lib.rmcl_pgd_step_ball(P(pb.gpatch), pb.dtype, P(pb.delta), P(pb.ball), P(valid), pb.B, I64(per), F(lr), F(eps), int(direction), int(ball),
+                                     F(lo), F(hi), P(pb.patches32), P(out), odt, L.PGD_DELTA_ZERO if first else 0, stream_ptr()), "pgd_step_ball")
+        return out
+
+    def pgd_random_start(self, pb: PassBuffers, eps: float, ball: int, seed: int, box=None, out: torch.Tensor = None, valid: torch.Tensor = None):
+        """delta_0 of a random start into ``pb.delta`` - uniform in the L-inf cube, or on the L2 sphere, of radius eps, a pure function of
+        (seed, sample index in the whole batch, element) - and cast(box(patches32 + delta_0)) into ``out`` (default ``pb.patchesT``),
+        which is returned.  A lane draws what its samples would draw in the whole batch."""
+        per = pb.d.P * pb.d.patch_k
+        out = pb.patchesT if out is None else out
+        valid = self.pgd_valid(pb) if valid is None else valid
+        lo, hi = self._box(box)
+        odt = L.F32 if out.dtype == torch.float32 else L.BF16
+        check(lib.rmcl_pgd_random_start(P(pb.delta), P(pb.ball), P(valid), pb.B, I64(per), int(getattr(pb, "lane", 0)) * pb.B, int(seed) & 0xFFFFFFFF,
+                                        F(eps), int(ball), F(lo), F(hi), P(pb.patches32), P(out), odt, stream_ptr()), "pgd_random_start")
+        return out
+
+    def pgd_keep_worst(self, score_new: torch.Tensor, best_score: torch.Tensor, best_restart: torch.Tensor, restart: int, delta: torch.Tensor,
+                       best_delta: torch.Tensor, operand: torch.Tensor = None, best_operand: torch.Tensor = None, rows_per_decision: int = 1):
+        """Worst case over restarts, decided on the device: decision j (``score_new[j]``, a 1-d view of any stride - a column of a task's
+        row terms) takes restart `restart` iff restart == 0 or score_new[j] > best_score[j]; its rows_per_decision rows of delta /
+        operand are then copied into best_delta / best_operand and best_score / best_restart updated.  No synchronisation."""
+        D = int(best_score.numel())
+        rows = D * rows_per_decision
+        if score_new.dim() != 1 or score_new.numel() != D or score_new.dtype != torch.float32 or delta.numel() % max(rows, 1):
+            raise L.RmclError("pgd_keep_worst: score_new must be a 1-d fp32 view with one entry per decision, delta [decisions * rows_per_decision, per]")
+        odt = L.F32 if (operand is None or operand.dtype == torch.float32) else L.BF16
+        check(lib.rmcl_pgd_keep_worst(P(score_new), I64(score_new.stride(0)), P(best_score), P(best_restart), int(restart), D, int(rows_per_decision),
+                                      P(delta), P(best_delta), P(operand), P(best_operand), odt, I64(delta.numel() // max(rows, 1)), stream_ptr()),
+              "pgd_keep_worst")
 
     def enqueue(self, keys_all: torch.Tensor, ptr: int):
         check(lib.rmcl_enqueue_f32(P(self.queue), P(keys_all), keys_all.shape[0], 128, I64(self.num_negative), I64(ptr),

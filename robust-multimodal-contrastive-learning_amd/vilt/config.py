@@ -10,6 +10,17 @@ def _loss_names(d):
     return ret
 
 
+# Not reference keys: the PGD threat model of the image attack (attack/pgd_attack_vilt.py ThreatModel, DESIGN.md "PGD threat models").
+# The defaults are the reference's loop, bit for bit: L-inf ball, step g / max|g|, delta_0 = 0, no pixel box.
+#   adv_norm_img          "linf" | "l2"
+#   adv_step_rule_img     "normalised" | "sign"   (ignored for "l2": the step is g / ||g||_2)
+#   adv_random_start_img  bool
+#   adv_pixel_box_img     None | (lo, hi)         ((-1.0, 1.0) for the pixelbert normalisation)
+#   adv_seed_img          int                     mixed with the engine's pass counter for each step's random start
+# Unknown values raise a ValueError when the attacker is built.
+ADV_IMG_THREAT = dict(adv_norm_img="linf", adv_step_rule_img="normalised", adv_random_start_img=False, adv_pixel_box_img=None, adv_seed_img=0)
+
+
 def default_config(**over):
     cfg = dict(
         exp_name="vilt", seed=0, loss_names=_loss_names({"itm": 1, "mlm": 1}), batch_size=4096,
@@ -36,7 +47,7 @@ def task_moco(**over):
         exp_name="moco", Multimodal=True, num_negative=65536, momentum=0.999, temperature=0.07,
         augmentation=False, text_view=False, image_view=False, loss_names=_loss_names({"moco": 1}),
         batch_size=128, max_epoch=1, max_image_len=200, test_only=False,
-        adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005,
+        adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005, **ADV_IMG_THREAT,
         n_candidates=5, max_loops=10, sim_thred=0.5, cos_sim=True, synonym="cos_sim",
         # reference config.py:161-162; the word-level text attack is active when `tokenizer` is a LOCAL vocab path (or an
         # object) and embedding_path exists - with the hub name "bert-base-uncased" it runs at token level
@@ -53,7 +64,7 @@ def task_barlowtwins(**over):
     cfg = default_config(
         exp_name="barlowtwins", Multimodal=True, augmentation=False, text_view=False, image_view=False,
         loss_names=_loss_names({"barlowtwins": 1}), adv_lr=0.0051, batch_size=128, max_epoch=1, max_image_len=200, test_only=False,
-        adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005,
+        adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005, **ADV_IMG_THREAT,
         n_candidates=5, max_loops=10, sim_thred=0.5, cos_sim=True, synonym="cos_sim",
         embedding_path="../attack/counter-fitted-vectors.txt", sim_path="../attack/cos_sim_counter_fitting.npy", stopwords=None,
         TSNE_vizualisation=False, img_save_path="", barlowtwins_dims=(8192, 8192, 8192),
@@ -88,7 +99,7 @@ def task_finetune_vqa_randaug_attacked(**over):
         exp_name="finetune_vqa_randaug_attacked", datasets=["vqa"], train_transform_keys=["pixelbert_randaug"],
         loss_names=_loss_names({"vqa_attacked": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,
         draw_false_image=0, learning_rate=1e-4, val_check_interval=0.1, lr_mult=10,
-        text_view=False, image_view=False, adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005,
+        text_view=False, image_view=False, adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005, **ADV_IMG_THREAT,
         n_candidates=5, max_loops=10, sim_thred=0.5, cos_sim=True, synonym="cos_sim",
         embedding_path="../attack/counter-fitted-vectors.txt", sim_path="../attack/cos_sim_counter_fitting.npy",
     )
@@ -124,7 +135,7 @@ def task_finetune_nlvr2_randaug_attacked(**over):
         exp_name="finetune_nlvr2_randaug_attacked", datasets=["nlvr2"], train_transform_keys=["pixelbert_randaug"],
         loss_names=_loss_names({"nlvr2_attacked": 1}), batch_size=128, max_epoch=10, max_steps=None, warmup_steps=0.1,
         draw_false_image=0, learning_rate=1e-4, test_only=False, text_view=False, image_view=False,
-        adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005, attack_idx=[True, True],
+        adv_steps_img=5, adv_lr_img=0.05, adv_max_norm_img=0.005, **ADV_IMG_THREAT, attack_idx=[True, True],
         n_candidates=5, max_loops=10, sim_thred=0.5, cos_sim=True, synonym="cos_sim",
         embedding_path="../attack/counter-fitted-vectors.txt", sim_path="../attack/cos_sim_counter_fitting.npy", nlvr2_pair_pass=True,
     )
